@@ -18,7 +18,12 @@ carries a one-step weak measurement and the 1-GPU rate of the same box (`scaling
 Weights are the seeded hot-init recipe of capdec_amd/synth.py (no checkpoints offline), which
 never emits the stop token, so every caption runs all 67 steps -- fixed, reproducible work.
 
-Rank 0 prints ONE JSON line (metric/value/... + "roofline" + "cpu_baseline").
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, warms up, times
+--steps steps and prints metric / value / unit / higher_is_better / dtype / ms_per_step (+ config, per_rank).
+`--full` adds everything else this file measures or checks, as part of the same line: per-kernel hipEvent timing of
+the timed steps ("kernels", "roofline"), rocm-smi clock / power, the untimed checks against the oracle, the stop
+profile, entry_length 12, the other BASELINE configurations, the scaling check (N > 1) and "cpu_baseline".
+`--dump-outputs DIR` writes what the last timed step returned (ids / lengths / scores) as DIR/*.npy.
 """
 from __future__ import annotations
 
@@ -43,6 +48,42 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA (not the 
 F16_MFMA_AT_POWER_CAP_TFLOPS = 1650.0
 STOP_ID, D_EMB = 13, 768
 PMC_TRAFFIC_FILE = "r6_pmc_traffic.json"   # rocprofv3 --pmc summary the `roofline.traffic` field is read from
+DUMP_LIMIT_BYTES = 64 << 20                # --dump-outputs: at most this much in all
+F32_VIA_F16X2 = "f32 (GEMMs: fp32 emulated with 3 fp16 MFMAs per product, fp32 accumulate)"
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy per array (float32; float64
+    arrays, and integer arrays whose values float32 would not hold exactly, go to float64).  The arrays share their leading (row) dimension;
+    when they would take more than `limit` bytes in all, every array keeps the same fixed, seeded sample of rows, whose
+    indices are written as DIR/rows.npy.  Returns {name: shape written}."""
+    import numpy as np
+    host = {}
+    for k, v in arrays.items():
+        if v is None:
+            continue
+        a = (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v))
+        if a.ndim == 0:
+            a = a.reshape(1)
+        if a.dtype.kind == "f":
+            exact32 = a.dtype.itemsize <= 4
+        else:
+            exact32 = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)
+        host[k] = a.astype(np.float32 if exact32 else np.float64)
+    rows_n = {a.shape[0] for a in host.values()}
+    total = sum(a.nbytes for a in host.values())
+    if total > limit:
+        assert len(rows_n) == 1, "--dump-outputs: a row sample needs one leading dimension, got %s" % sorted(rows_n)
+        n = rows_n.pop()
+        per_row = total / n + 8
+        k = max(1, int(limit // per_row))
+        rows = np.sort(torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].numpy())
+        host = {name: a[rows] for name, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 def algorithmic_flops_per_caption(P, T, beam, mapper, dims=synth.GPT2_SMALL, D=512, clip_len=10):
@@ -401,14 +442,26 @@ def side_workload(args, world, rank, dev, emit=print):
 
     for _ in range(args.warmup):
         step()
-    cm._engine.profile_enable(max(1, args.profile_every))
-    cm._engine.profile_reset()
+    if args.full:
+        cm._engine.profile_enable(max(1, args.profile_every))
+        cm._engine.profile_reset()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"prefix_embeddings": out} if text else
+                     {"ids": out[0], "lengths": out[1], "scores": out[2]})
+    if rank == 0 and not args.full:
+        emit(json.dumps({"metric": f"{'captions' if text else 'images'}/sec, side workload {args.workload}",
+                         "value": round(n_global * args.steps / dt, 2), "unit": "items/s", "n_gpus": world,
+                         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+                         "higher_is_better": True, "data": "synthetic", "dtype": tower_dtype(prec),
+                         "config": side_config(args, text, rn, n_global, prec, model, inp)}))
+    if not args.full:
+        return
     prof = cm._engine.profile_get()
     if rank == 0:
         # ---- roofline of the tower's dominant kernel family (hipEvent-timed launches on the launch stream)
@@ -477,17 +530,25 @@ def side_workload(args, world, rank, dev, emit=print):
                           "value": round(n_global * args.steps / dt, 2), "unit": "items/s", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
                           "higher_is_better": True, "data": "synthetic",
-                          "dtype": {"fp16": "f16 towers (one fp16 plane per GEMM operand, fp32 accumulate: the reference's CLIP arithmetic on a GPU)",
-                                    "bf16": "bf16 towers"}.get(prec, "f32 towers (two fp16 planes, 3 MFMAs per product)"),
+                          "dtype": tower_dtype(prec),
                           "roofline": roof, "cpu_baseline": cpu,
-                          "config": {"workload": args.workload, "clip": "RN50x4" if rn else "ViT-B/32",
-                                     "items_per_step": n_global, "clip_precision": prec,
-                                     "gemm_mode": model.engine.gemm_mode(),
-                                     **({"token_rows": "clip.tokenize-shaped: SOT + 8-20 random ids + EOT, zero-padded to 77 "
-                                                       "(synth.synthetic_clip_tokens; mean EOT position %.1f) -- the tower computes the "
-                                                       "positions up to each chunk's last EOT, so the rate depends on caption length "
-                                                       "(CAPDEC_CLIP_TRUNC=0: all 77 positions)" % float(inp.argmax(dim=-1).float().mean())}
-                                        if text else {})}}))
+                          "config": side_config(args, text, rn, n_global, prec, model, inp)}))
+
+
+def tower_dtype(prec):
+    return {"fp16": "f16 towers (one fp16 plane per GEMM operand, fp32 accumulate: the reference's CLIP arithmetic on a GPU)",
+            "bf16": "bf16 towers"}.get(prec, "f32 towers (two fp16 planes, 3 MFMAs per product)")
+
+
+def side_config(args, text, rn, n_global, prec, model, inp):
+    return {"workload": args.workload, "clip": "RN50x4" if rn else "ViT-B/32",
+            "items_per_step": n_global, "clip_precision": prec,
+            "gemm_mode": model.engine.gemm_mode(),
+            **({"token_rows": "clip.tokenize-shaped: SOT + 8-20 random ids + EOT, zero-padded to 77 "
+                              "(synth.synthetic_clip_tokens; mean EOT position %.1f) -- the tower computes the "
+                              "positions up to each chunk's last EOT, so the rate depends on caption length "
+                              "(CAPDEC_CLIP_TRUNC=0: all 77 positions)" % float(inp.argmax(dim=-1).float().mean())}
+               if text else {})}
 
 
 def other_configs(args, dev, note):
@@ -505,7 +566,7 @@ def other_configs(args, dev, note):
         try:
             note("other configs: " + name)
             a = copy.copy(args)
-            a.steps, a.warmup, a.cpu_seconds, a.profile_every = 2, 1, 0.0, 1
+            a.steps, a.warmup, a.cpu_seconds, a.profile_every, a.dump_outputs = 2, 1, 0.0, 1, None
             for k, v in over.items():
                 setattr(a, k, v)
             got = []
@@ -588,8 +649,9 @@ def train_workload(args, world, rank, dev, emit=print):
     first = None
     for _ in range(max(1, args.warmup)):
         first = step(True)
-    eng.profile_enable(1)
-    eng.profile_reset()
+    if args.full:
+        eng.profile_enable(1)
+        eng.profile_reset()
     eng.train_loss(reset=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -598,6 +660,18 @@ def train_workload(args, world, rank, dev, emit=print):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     last, loss_sum, nsteps = eng.train_loss()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": [last]})
+    what = "full model: GPT-2 trained too, dropout 0.1, reference train.py:344-354 default" if full else \
+        "frozen GPT-2, reference train.py:344-354 --only_prefix"
+    head = {"metric": f"train steps/sec, side workload train_step ({what})",
+            "value": round(args.steps / dt, 3), "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True}
+    if not args.full:
+        # (the train step's GEMMs run on the two-fp16-plane kernels unless CAPDEC_TRAIN_F16X2=0: what --full's roofline finds)
+        f16x2 = os.environ.get("CAPDEC_TRAIN_F16X2", "1").strip() != "0"
+        emit(json.dumps(dict(head, dtype=F32_VIA_F16X2 if f16x2 else "f32", data="synthetic")))
+        return
     prof = eng.profile_get()
     eng.profile_enable(False)
     kern = {k: {"ms_per_step": round(v["ms"] / args.steps, 3), "launches_per_step": round(v["calls"] / args.steps, 1),
@@ -630,12 +704,8 @@ def train_workload(args, world, rank, dev, emit=print):
         cpu = {"value": round(n_cpu / cdt, 4), "unit": "steps/s", "cores": torch.get_num_threads(), "kind": "port",
                "sample": f"{n_cpu} step(s) of the oracle's hand-written forward + backward (no optimizer update, no dropout) on the "
                          f"same batch, {cdt:.1f} s wall"}
-    what = "full model: GPT-2 trained too, dropout 0.1, reference train.py:344-354 default" if full else \
-        "frozen GPT-2, reference train.py:344-354 --only_prefix"
-    emit(json.dumps({"metric": f"train steps/sec, side workload train_step ({what})",
-                     "value": round(args.steps / dt, 3), "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-                     "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-                     "dtype": "f32 (GEMMs: fp32 emulated with 3 fp16 MFMAs per product, fp32 accumulate)" if roof and "f16x2" in roof["kernel"] else "f32",
+    emit(json.dumps({**head,
+                     "dtype": F32_VIA_F16X2 if roof and "f16x2" in roof["kernel"] else "f32",
                      "data": "synthetic",
                      "samples_per_s": round(B * args.steps / dt, 1),
                      "loss_first_last_mean": [round(first, 4), round(last, 4), round(loss_sum / max(1, nsteps), 4)],
@@ -724,6 +794,8 @@ def dry_run(args, world, rank, emit):
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
     lo, hi = cdist.shard_bounds(n_global, rank, world)
     table = per_rank_table(world, rank, hi - lo, t_local / max(args.steps, 1), rank, all_gather_floats)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ids": out[0], "lengths": out[1], "scores": out[2]})
     wd.note("scaling check")
     one = fake_step(0, 1)
     same = all(bool((a == b).all()) for a, b in zip(one, out))
@@ -808,7 +880,19 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU (CPU tests): join a gloo group, all-gather the ranks, print "
                          "{n_gpus, ranks} and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel hipEvent timing inside the timed region "
+                         "(`kernels`, `roofline`), rocm-smi clock / power, the untimed checks and extras after it (ids_check, "
+                         "oracle_check, stop_profile, entry_length_12, the diverged-beam step, match_vs_fp32, other_configs, "
+                         "scaling_check, capi_collective) and the CPU baseline; the options above that switch those off "
+                         "act only with --full.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (beam / greedy: ids, lengths, "
+                         "scores of every caption) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed "
+                         "seeded sample of rows, DIR/rows.npy, beyond that); same arguments, same inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(respawn_under_torchrun(args.gpus))
@@ -858,7 +942,7 @@ def main():
     model = ClipCaptionModel(P, clip_length=10, prefix_dim=512, num_layers=8,
                              mapping_type=MappingType.TransformerEncoder if beam else MappingType.MLP).to(dev).eval()
     model.load_state_dict(synth.hot_state_dict(42, mapper, 512, P))
-    n_alloc = max(n_global, args.captions * world) if (world > 1 and not args.no_scaling_check) else n_global
+    n_alloc = max(n_global, args.captions * world) if (args.full and world > 1 and not args.no_scaling_check) else n_global
     emb_all = synth.synthetic_clip_embeddings(n_alloc, 512, seed=0, normalize=False).to(dev)   # resident in HBM
     emb = emb_all[:n_global]
     eng = model.engine
@@ -903,10 +987,11 @@ def main():
     note("weights loaded, warm-up")
     for _ in range(args.warmup):
         out = step()
-    eng.decode_counters()                       # reset the saturation counter: the timed region reports its own
-    eng.profile_enable(max(1, args.profile_every))
-    eng.profile_reset()
-    smi = SmiSampler(local_rank) if (rank == 0 and not args.no_smi) else None
+    if args.full:
+        eng.decode_counters()                   # reset the saturation counter: the timed region reports its own
+        eng.profile_enable(max(1, args.profile_every))
+        eng.profile_reset()
+    smi = SmiSampler(local_rank) if (args.full and rank == 0 and not args.no_smi) else None
     barrier()
     note("timed region: %d steps" % args.steps)
     if smi:
@@ -921,12 +1006,49 @@ def main():
     note("timed region done")
     lo_r, hi_r = cdist.shard_bounds(n_global, rank, world)
     per_rank = per_rank_table(world, rank, hi_r - lo_r, t_local / max(args.steps, 1), local_rank, all_gather_floats)
+    assert out[0].shape[0] == n_global and int(out[1].min()) >= 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ids": out[0], "lengths": out[1], "scores": out[2]})
+    value = n_global * args.steps / dt
+    n_local = cdist.shard_size(n_global, world)
+    mode_name = eng.gemm_mode()
+    head = {
+        "metric": "captions/sec (whole node), COCO-val 5k, prefix_len=10 beam=5, 1/2/4/8 GPUs",
+        "value": round(value, 2), "unit": "captions/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+        "scaling": args.scaling, "vs_baseline": None,
+        "dtype": {"f32": "f32", "bf16": "bf16 (GEMM operands and KV cache bf16, fp32 accumulate; residual stream / LayerNorm / softmax f32)",
+                  "f16": "f16 (GEMM operands fp16, fp32 accumulate; residual stream / LayerNorm / softmax / KV cache f32)",
+                  "bf16x3": "f32 (operands split into 3 bf16 planes, 6 bf16 MFMAs per product, fp32 accumulate)",
+                  "f16x2": "f32 (operands split into 2 fp16 planes, 3 fp16 MFMAs per product, fp32 accumulate)"}[mode_name],
+        "data": "synthetic",
+        "config": {"workload": ("COCO-val-5k-shaped: %d x 512-d synthetic CLIP embeddings %s -> normalise -> "
+                                "%s -> GPT-2 small KV-cached %s, prefix_len %d, entry_length %d, hot-init seeded "
+                                "weights (never emit the stop id: all %d steps run)")
+                   % (args.captions, "per GPU" if args.scaling == "weak" else "in total (sharded over the ranks)",
+                      "TransformerMapper(8 layers)" if beam else "MLP mapper",
+                      "beam-5 decode" if beam else "greedy decode", P, T, T),
+                   "captions_per_step": n_global, "captions_per_gpu": n_local, "beam": B,
+                   "parallelism": f"caption-shard dp{world}", "tokens_per_s": round(value * T, 1)},
+        "per_gpu_value": round(value / world, 2),
+    }
+
+    def finish():
+        if use_dist:
+            import torch.distributed as dist
+            wd.note("final barrier")
+            dist.barrier()
+            dist.destroy_process_group()
+        wd.stop()
+    if not args.full:               # the headline alone: everything below is --full
+        if rank == 0:
+            emit(json.dumps(dict(head, per_rank=per_rank)))
+        return finish()
     power = smi.stop() if smi else None
     prof = eng.profile_get()
     eng.profile_enable(False)
     counters = eng.decode_counters()
     second_pass = (eng.second_pass_rows(), eng.decode_stats()["row_steps"]) if beam else None   # of the last timed step
-    assert out[0].shape[0] == n_global and int(out[1].min()) >= 1
 
     # ---- untimed checks (rank 0, N = 1): (a) ids_check -- the whole batch decoded once more in BATCH-INVARIANT mode (one
     # summation order whatever the launch size) and captions [0:16] decoded ALONE in that mode: those 16 must reproduce
@@ -1067,7 +1189,6 @@ def main():
                              "weak_value": round(vw, 2), "weak_captions_per_gpu": args.captions,
                              "weak_efficiency": round(vw / (world * v1), 4)}
 
-    mode_name = eng.gemm_mode()
     # ---- one more step with beams that never share history: the worst-case K/V traffic of the decode attention.  The hook
     # lives in the MEASUREMENT build of the library only (libcapdec_hip_measure.so, -DCAPDEC_MEASURE): the model moves to
     # a context of that library for this last, untimed step (the product context and its KV cache are released first)
@@ -1094,7 +1215,6 @@ def main():
             diverged = {"error": str(ex)[:300]}
 
     if rank == 0:
-        value = n_global * args.steps / dt
         mode = mode_name
         est = lambda f: f["ms"] * f["calls"] / f["launches"] if f and f["launches"] else 0.0
         if mode in ("bf16", "f16"):
@@ -1131,27 +1251,9 @@ def main():
             pass
         gemm_ms = fam["ms"] / max(fam["launches"], 1)
         achieved = fam["flops"] / (fam["ms"] * 1e-3) / 1e12 if fam["ms"] > 0 else 0.0
-        n_local = cdist.shard_size(n_global, world)
         alg = algorithmic_flops_per_caption(P, T, B, "transformer" if beam else "mlp") * n_local * args.steps
         rec = {
-            "metric": "captions/sec (whole node), COCO-val 5k, prefix_len=10 beam=5, 1/2/4/8 GPUs",
-            "value": round(value, 2), "unit": "captions/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None,
-            "dtype": {"f32": "f32", "bf16": "bf16 (GEMM operands and KV cache bf16, fp32 accumulate; residual stream / LayerNorm / softmax f32)",
-                      "f16": "f16 (GEMM operands fp16, fp32 accumulate; residual stream / LayerNorm / softmax / KV cache f32)",
-                      "bf16x3": "f32 (operands split into 3 bf16 planes, 6 bf16 MFMAs per product, fp32 accumulate)",
-                      "f16x2": "f32 (operands split into 2 fp16 planes, 3 fp16 MFMAs per product, fp32 accumulate)"}[mode],
-            "data": "synthetic",
-            "config": {"workload": ("COCO-val-5k-shaped: %d x 512-d synthetic CLIP embeddings %s -> normalise -> "
-                                    "%s -> GPT-2 small KV-cached %s, prefix_len %d, entry_length %d, hot-init seeded "
-                                    "weights (never emit the stop id: all %d steps run)")
-                       % (args.captions, "per GPU" if args.scaling == "weak" else "in total (sharded over the ranks)",
-                          "TransformerMapper(8 layers)" if beam else "MLP mapper",
-                          "beam-5 decode" if beam else "greedy decode", P, T, T),
-                       "captions_per_step": n_global, "captions_per_gpu": n_local, "beam": B,
-                       "parallelism": f"caption-shard dp{world}", "tokens_per_s": round(value * T, 1)},
-            "per_gpu_value": round(value / world, 2),
+            **head,
             "roofline": {"bound": "mfma", "kernel": kname + " (dominant GEMM family; the other projections and the fused "
                          "lm_head variant are listed in `kernels`)",
                          "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
@@ -1218,12 +1320,7 @@ def main():
         else:
             rec["cpu_baseline"] = None
         emit(json.dumps(rec))
-    if use_dist:
-        import torch.distributed as dist
-        wd.note("final barrier")
-        dist.barrier()
-        dist.destroy_process_group()
-    wd.stop()
+    finish()
 
 
 if __name__ == "__main__":

@@ -331,36 +331,39 @@ def test_state_dict_loading_rules():
         mm.load_state_dict(sd)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
 @pytest.mark.parametrize("variant", ["train_mlp", "eval_transformer"])
-def test_loads_checkpoint_written_by_the_reference(tmp_path, variant):
+def test_loads_checkpoint_written_by_the_reference(tmp_path, variant, golden):
     """Real-artefact readiness without the artefacts: a checkpoint written the way the reference writes it --
-    instantiate ITS ClipCaptionModel (train.py:246-284 with ``prefix_size`` / gpt2_prefix.py:139-171 with ``prefix_dim``),
+    ITS ClipCaptionModel (train.py:246-284 with ``prefix_size`` / gpt2_prefix.py:139-171 with ``prefix_dim``),
     ``torch.save(model.state_dict(), path)`` (train.py:359-371) -- is read back with ``torch.load(map_location=...)``
     (predictions_runner.py:461) and loaded STRICT by ``capdec_amd.gpt2_prefix.ClipCaptionModel``: every tensor the
     reference saved arrives bit for bit, the tied ``gpt.lm_head.weight`` is accepted, and the transformers-4.24 buffers
-    (``attn.bias`` / ``attn.masked_bias``; 5.x no longer writes them) are tolerated when present"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_golden as G
-    from transformers import GPT2Config, GPT2LMHeadModel
+    (``attn.bias`` / ``attn.masked_bias``; 5.x no longer writes them) are tolerated when present.  The reference's state
+    dict is rebuilt from tests/golden/reference_checkpoints.npz (tools/gen_golden.py: every key, shape and dtype the
+    reference model's state_dict() holds, and which keys share storage) with seeded values"""
+    from collections import OrderedDict
     from capdec_amd import synth
     from capdec_amd import gpt2_prefix as ours
-    refs = G.import_reference()
-    ref_gpt2_prefix, ref_train = refs[0], refs[3]
+    man = golden("reference_checkpoints")
     dims = synth.GPT2Dims(n_layer=2, vocab=1531, n_pos=128)
-    cfg = GPT2Config(n_layer=dims.n_layer, n_head=dims.n_head, n_embd=dims.n_embd, vocab_size=dims.vocab, n_positions=dims.n_pos)
-    GPT2LMHeadModel.from_pretrained = staticmethod(lambda name, *a, **k: GPT2LMHeadModel(cfg))
-    torch.manual_seed(3)
     if variant == "train_mlp":
-        ref = ref_train.ClipCaptionModel(10, clip_length=10, prefix_size=512, num_layers=8, mapping_type=ref_train.MappingType.MLP)
         mine = ours.ClipCaptionModel(10, clip_length=10, prefix_size=512, mapping_type=ours.MappingType.MLP, gpt2_dims=dims)
     else:
-        ref = ref_gpt2_prefix.ClipCaptionModel(10, clip_length=10, prefix_dim=640, num_layers=3,
-                                               mapping_type=ref_gpt2_prefix.MappingType.TransformerEncoder)
         mine = ours.ClipCaptionModel(10, clip_length=10, prefix_dim=640, num_layers=3,
                                      mapping_type=ours.MappingType.TransformerEncoder, gpt2_dims=dims)
+    g = torch.Generator().manual_seed(3)
+    tied = {str(a): str(b) for a, b in man[f"tied_{variant}"]}
+    ref_sd, shapes, at = OrderedDict(), man[f"shapes_{variant}"], 0
+    for k, dt, nd in zip(man[f"keys_{variant}"], man[f"dtypes_{variant}"], man[f"ndim_{variant}"]):
+        shape = tuple(int(s) for s in shapes[at:at + nd])
+        at += int(nd)
+        if str(k) in tied:
+            ref_sd[str(k)] = ref_sd[tied[str(k)]]                            # one storage, as the reference saves it
+        else:
+            ref_sd[str(k)] = (torch.randn(shape, generator=g) * 0.02).to(getattr(torch, str(dt)))
+    assert at == len(shapes) and tied
     path = str(tmp_path / "coco_prefix_latest.pt")
-    torch.save(ref.state_dict(), path)                                      # train.py:359-371
+    torch.save(ref_sd, path)                                                # train.py:359-371
     sd = torch.load(path, map_location=torch.device("cpu"))                 # predictions_runner.py:461
     assert "gpt.lm_head.weight" in sd or "gpt.transformer.wte.weight" in sd
     res = mine.load_state_dict(sd)                                          # strict
@@ -617,6 +620,35 @@ def test_bench_spawns_its_own_ranks(n):
         bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"],
                              capture_output=True, text=True, timeout=120, env=dict(os.environ, RANK="0", WORLD_SIZE="1"))
         assert bad.returncode != 0 and "WORLD_SIZE=1" in (bad.stderr + bad.stdout)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32 / float64): the
+    same arrays from one rank and from two (the dry run's fake decode), and above the size limit the same seeded sample
+    of rows of every array, with the row indices beside them"""
+    import bench
+    got = {}
+    for n in (1, 2):
+        d = tmp_path / ("dump%d" % n)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-run", "--captions", "300",
+                              "--steps", "2", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got[n] = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+    assert sorted(got[1]) == ["ids.npy", "lengths.npy", "scores.npy"]
+    assert got[1]["ids.npy"].shape == (300, 67) and got[1]["lengths.npy"].shape == (300,)
+    for f, a in got[1].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, got[2][f]), f
+    ids = torch.arange(1000 * 4, dtype=torch.int64).reshape(1000, 4)
+    big = {"ids": ids, "wide": ids[:, :1] + (1 << 30), "scores": torch.linspace(0, 1, 1000)}
+    shapes = bench.dump_outputs(str(tmp_path / "s1"), big, limit=8000)
+    bench.dump_outputs(str(tmp_path / "s2"), big, limit=8000)
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    k = shapes["rows"][0]
+    assert 0 < k < 1000 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "s1" / (f + ".npy")) - 128 for f in shapes) <= 8000
+    w = np.load(tmp_path / "s1" / "wide.npy")
+    assert w.dtype == np.float64 and np.array_equal(w[:, 0], rows * 4 + (1 << 30))          # beyond float32: float64
+    assert np.array_equal(np.load(tmp_path / "s1" / "ids.npy"), ids.numpy()[rows.astype(np.int64)].astype(np.float32))
 
 
 def test_bench_watchdog_names_the_phase_a_rank_is_stuck_in():

@@ -16,14 +16,14 @@ OUT=$R/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd "$R"
-timeout 400 python bench.py --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
-timeout 300 python bench.py --captions 625 --steps 20 --warmup 5 --cpu-seconds 0 > "$OUT/${TAG}_bench_625.json" 2> "$OUT/${TAG}_bench_625.err"
+timeout 400 python bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+timeout 300 python bench.py --full --captions 625 --steps 20 --warmup 5 --cpu-seconds 0 > "$OUT/${TAG}_bench_625.json" 2> "$OUT/${TAG}_bench_625.err"
 # what one decode step of the 625-caption shard is made of: per-(kernel, grid) table of a traced pass
-[ "${SHORT:-0}" = 1 ] || timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/${TAG}_kt625" -- python bench.py --cpu-seconds 0 --no-checks --no-smi --captions 625 --steps 1 --warmup 1 \
+[ "${SHORT:-0}" = 1 ] || timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/${TAG}_kt625" -- python bench.py --full --cpu-seconds 0 --no-checks --no-smi --captions 625 --steps 1 --warmup 1 \
     > "$OUT/${TAG}_kt625.json" 2> "$OUT/${TAG}_kt625.err"
 [ "${SHORT:-0}" = 1 ] || python tools/trace_summary.py "$OUT/${TAG}_kt625" "$OUT/${TAG}_625_kernels.txt" --title "bench.py --captions 625 --steps 1 --warmup 1 under rocprofv3 --kernel-trace (two passes of 67 steps + mapper + prefill)"
 find "$OUT/${TAG}_kt625" -name "*.csv" -delete
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_kt" -- python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi \
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_kt" -- python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi \
     > "$OUT/${TAG}_bench_under_rocprof.json" 2> "$OUT/${TAG}_kt.err"
 find "$OUT/${TAG}_kt" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_bench_kernel_stats.csv" \;
 find "$OUT/${TAG}_kt" -name "*kernel_trace.csv" -delete
@@ -33,11 +33,11 @@ if [ "${SHORT:-0}" = 1 ]; then
     exit 0
 fi
 for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --pmc $c --output-format csv -d "$OUT/${TAG}_pmc_$c" -- python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi --steps 1 --warmup 0 \
+    timeout 300 rocprofv3 --pmc $c --output-format csv -d "$OUT/${TAG}_pmc_$c" -- python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi --steps 1 --warmup 0 \
         > "$OUT/${TAG}_pmc_$c.log" 2>&1
 done
 python tools/pmc_summary.py "$OUT" "$OUT/${TAG}_pmc_traffic.json" \
-    "python bench.py --cpu-seconds 0 --no-checks --steps 1 --warmup 0 (default workload: 5000 captions, beam 5, T=67)" f16x2 5000 "${TAG}"
+    "python bench.py --full --cpu-seconds 0 --no-checks --steps 1 --warmup 0 (default workload: 5000 captions, beam 5, T=67)" f16x2 5000 "${TAG}"
 find "$OUT" -name "*counter_collection.csv" -delete
 export CAPDEC_HOOK_PACKA=1 CAPDEC_HOOK_CACHE=1
 for h in 0 2 10 12; do for data in random zeros; do      # (12 = the 256 x 256 ping-pong tile: measurement build only since round 5)

@@ -135,6 +135,41 @@ def gen_mappers(refs):
     print("mappers.npz", {k: getattr(v, "shape", v) for k, v in out.items()})
 
 
+def gen_checkpoint_keys(refs):
+    """What a checkpoint the reference writes (torch.save(model.state_dict()), train.py:359-371) holds: every key with its
+    shape and dtype, and the keys that share storage with another (the tied lm_head), for the two model classes the
+    reference saves -- train.py's ClipCaptionModel (MLP mapper, ``prefix_size``) and gpt2_prefix.py's (TransformerMapper,
+    ``prefix_dim``) -- on a 2-layer GPT-2 of vocabulary 1531 and 128 positions.  Names and shapes only: the checkpoint test
+    fills them with seeded values, writes and reads them back the way the reference does."""
+    from transformers import GPT2Config, GPT2LMHeadModel
+    ref_gpt2_prefix, ref_train = refs[0], refs[3]
+    dims = synth.GPT2Dims(n_layer=2, vocab=1531, n_pos=128)
+    cfg = GPT2Config(n_layer=dims.n_layer, n_head=dims.n_head, n_embd=dims.n_embd, vocab_size=dims.vocab, n_positions=dims.n_pos)
+    GPT2LMHeadModel.from_pretrained = staticmethod(lambda name, *a, **k: GPT2LMHeadModel(cfg))
+    torch.manual_seed(3)
+    models = {"train_mlp": ref_train.ClipCaptionModel(10, clip_length=10, prefix_size=512, num_layers=8,
+                                                      mapping_type=ref_train.MappingType.MLP),
+              "eval_transformer": ref_gpt2_prefix.ClipCaptionModel(10, clip_length=10, prefix_dim=640, num_layers=3,
+                                                                   mapping_type=ref_gpt2_prefix.MappingType.TransformerEncoder)}
+    out = {}
+    for variant, model in models.items():
+        sd = model.state_dict()
+        first, tied = {}, []
+        for k, v in sd.items():
+            ptr = v.untyped_storage().data_ptr()
+            if ptr in first:
+                tied.append([k, first[ptr]])
+            else:
+                first[ptr] = k
+        out[f"keys_{variant}"] = np.array(list(sd.keys()))
+        out[f"dtypes_{variant}"] = np.array([str(v.dtype).replace("torch.", "") for v in sd.values()])
+        out[f"ndim_{variant}"] = np.array([v.dim() for v in sd.values()], np.int64)
+        out[f"shapes_{variant}"] = np.array([s for v in sd.values() for s in v.shape], np.int64)
+        out[f"tied_{variant}"] = np.array(tied, dtype=str).reshape(-1, 2)
+        print("reference_checkpoints", variant, len(sd), "keys, tied", tied)
+    np.savez_compressed(os.path.join(OUT, "reference_checkpoints.npz"), **out)
+
+
 def gen_noise(refs):
     _, _, _, ref_train = refs
     out = {}
@@ -764,6 +799,7 @@ def main():
     refs = None if args.only and set(args.only) <= {"preprocess", "clip_resnet", "clip_tiny", "clip_b32"} else import_reference()
     jobs = {
         "mappers": lambda: gen_mappers(refs),
+        "reference_checkpoints": lambda: gen_checkpoint_keys(refs),
         "noise": lambda: gen_noise(refs),
         "logits_tiny": lambda: gen_gpt2_logits(refs, synth.GPT2_TINY, "tiny"),
         "logits_small": lambda: gen_gpt2_logits(refs, synth.GPT2_SMALL, "small"),

@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
 CAPS=${2:-5000}
-B="python bench.py --cpu-seconds 0 --no-checks --steps 3 --warmup 1 --captions $CAPS"
+B="python bench.py --full --cpu-seconds 0 --no-checks --steps 3 --warmup 1 --captions $CAPS"
 for kv in "X=0" $1; do
     echo "== $kv"
     env $kv $B 2>/dev/null | python -c "

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd "$R"
-B="python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks"
+B="python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks"
 timeout 300 $B --steps 3 --warmup 1 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 timeout 200 $B --captions 625 --steps 10 --warmup 2 > "$OUT/${TAG}_bench_625.json" 2> "$OUT/${TAG}_bench_625.err"
 timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/${TAG}_kt625" -- $B --no-smi --captions 625 --steps 1 --warmup 1 \

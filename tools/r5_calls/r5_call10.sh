@@ -31,9 +31,9 @@ k=d.get('kernels',{})
 print(d['value'], d['ms_per_step'], {n:(round(v.get('avg_ms',0)*1000,1), v.get('tflops')) for n,v in k.items() if 'gemm_x1' in n or 'attn_dec' in n})"; }
 for w in 0 1 2; do
     echo "-- greedy_mlp bf16 CAPDEC_X1_WIDE=$w"
-    CAPDEC_X1_WIDE=$w timeout 200 python bench.py --workload greedy_mlp --gemm-mode bf16 --steps 6 --warmup 2 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_greedy_bf16_x1w_$w.json" | summ
+    CAPDEC_X1_WIDE=$w timeout 200 python bench.py --full --workload greedy_mlp --gemm-mode bf16 --steps 6 --warmup 2 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_greedy_bf16_x1w_$w.json" | summ
 done
 for w in 0 1; do
     echo "-- beam bf16 CAPDEC_X1_WIDE=$w"
-    CAPDEC_X1_WIDE=$w timeout 300 python bench.py --gemm-mode bf16 --steps 3 --warmup 1 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_beam_bf16_x1w_$w.json" | summ
+    CAPDEC_X1_WIDE=$w timeout 300 python bench.py --full --gemm-mode bf16 --steps 3 --warmup 1 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_beam_bf16_x1w_$w.json" | summ
 done

@@ -10,4 +10,4 @@ timeout 600 python -m pytest tests/test_hip_parity.py -q -m gpu -x -k "train_ste
 echo "== forced geometries, three at a time"
 timeout 900 python -m pytest tests/test_hip_parity.py -q -m gpu -x -k "test_wide_single_accumulator" --durations=3 2>&1 | tail -15 | tee "$OUT/r5_forced_geo.txt"
 echo "== train bench (default = f16x2 backward)"
-timeout 120 python bench.py --workload train_step --steps 10 --warmup 2 --cpu-seconds 0 2>/dev/null | tee "$OUT/r5_train_bench_call2.json" | cut -c1-900
+timeout 120 python bench.py --full --workload train_step --steps 10 --warmup 2 --cpu-seconds 0 2>/dev/null | tee "$OUT/r5_train_bench_call2.json" | cut -c1-900

@@ -10,7 +10,7 @@ tail -12 "$OUT/parity_counts.txt"
 echo "== A/B: greedy bf16 (configs[1]) and beam bf16, planner modes"
 for m in 0 1 2; do
     echo "-- greedy_mlp bf16 CAPDEC_PP_X1=$m"
-    CAPDEC_PP_X1=$m timeout 200 python bench.py --workload greedy_mlp --gemm-mode bf16 --steps 6 --warmup 2 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_greedy_bf16_ppx1_$m.json" | python -c "
+    CAPDEC_PP_X1=$m timeout 200 python bench.py --full --workload greedy_mlp --gemm-mode bf16 --steps 6 --warmup 2 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_greedy_bf16_ppx1_$m.json" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d.get('kernels',{})
@@ -18,7 +18,7 @@ print(d['value'], d['ms_per_step'], {n:(round(v.get('avg_ms',0)*1000,1), v.get('
 done
 for m in 0 2 3; do
     echo "-- beam_transformer bf16 CAPDEC_PP_X1=$m"
-    CAPDEC_PP_X1=$m timeout 300 python bench.py --gemm-mode bf16 --steps 3 --warmup 1 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_beam_bf16_ppx1_$m.json" | python -c "
+    CAPDEC_PP_X1=$m timeout 300 python bench.py --full --gemm-mode bf16 --steps 3 --warmup 1 --cpu-seconds 0 --no-checks 2>/dev/null | tee "$OUT/r5_beam_bf16_ppx1_$m.json" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d.get('kernels',{})

@@ -17,7 +17,7 @@ CAPDEC_TRAIN_F16X2=1 timeout 120 python -m pytest tests/test_hip_parity.py -q -m
 echo "== 2b. train-step bench A/B"
 for kv in X=0 CAPDEC_TRAIN_F16X2=1; do
     echo "-- $kv"
-    env $kv timeout 100 python bench.py --workload train_step --steps 10 --warmup 2 --cpu-seconds 0 2>/dev/null | tee "$OUT/r5_train_bench_${kv%%=*}.json" | cut -c1-700
+    env $kv timeout 100 python bench.py --full --workload train_step --steps 10 --warmup 2 --cpu-seconds 0 2>/dev/null | tee "$OUT/r5_train_bench_${kv%%=*}.json" | cut -c1-700
 done
 echo "== 3. per-kernel table"
 bash tools/train_profile.sh r5 2>&1 | tail -45

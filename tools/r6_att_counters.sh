@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd "$R"
-CMD="python bench.py --workload text_embed --captions 8000 --gemm-mode f16 --steps 1 --warmup 0 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi"
+CMD="python bench.py --full --workload text_embed --captions 8000 --gemm-mode f16 --steps 1 --warmup 0 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi"
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
     --output-format csv -d "$OUT/r6_sq_att_a" -- $CMD > "$OUT/r6_sq_att_a.log" 2>&1
 timeout 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM_RD SQ_INSTS_SALU \

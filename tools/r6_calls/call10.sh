@@ -11,6 +11,6 @@ SECONDS=0; timeout 1300 python -m pytest tests/ -x -q -m gpu --durations=25 > "$
 echo "suite wall seconds: $SECONDS" | tee -a "$OUT/${TAG}_pytest_gpu.txt"; tail -5 "$OUT/${TAG}_pytest_gpu.txt" | cut -c1-160
 cp "$OUT/parity_counts.txt" "$OUT/${TAG}_parity_counts.txt" 2>/dev/null
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a "$OUT/${TAG}_pytest_gpu.txt"
-B="timeout 400 python bench.py --cpu-captions 0 --no-checks --cpu-seconds 0"
+B="timeout 400 python bench.py --full --cpu-captions 0 --no-checks --cpu-seconds 0"
 $B --steps 5 --warmup 2 > "$OUT/tmp5000.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/tmp5000.json'));k=r['kernels'];print('5000 (5 steps):',r['value'],r['ms_per_step'],'select',k['select']['avg_ms'],'attn',k['attn_decode']['avg_ms'])"
 $B --captions 625 --steps 20 --warmup 5 > "$OUT/tmp625.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/tmp625.json'));k=r['kernels'];print('625:',r['value'],r['ms_per_step'],'select',k['select']['avg_ms'])"

@@ -11,7 +11,7 @@ SECONDS=0; timeout 1300 python -m pytest tests/ -x -q -m gpu --durations=25 > "$
 echo "suite wall seconds: $SECONDS" | tee -a "$OUT/${TAG}_pytest_gpu.txt"; tail -4 "$OUT/${TAG}_pytest_gpu.txt" | cut -c1-160
 cp "$OUT/parity_counts.txt" "$OUT/${TAG}_parity_counts.txt" 2>/dev/null
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a "$OUT/${TAG}_pytest_gpu.txt"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 python - "$OUT/${TAG}_bench.json" <<'PY'
 import json, sys
 r = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -21,12 +21,12 @@ print("T12", r["entry_length_12"]["value"]); print("cpu", r["cpu_baseline"]["val
 for k, v in (r.get("other_configs") or {}).items(): print(k, v.get("value"), (v.get("roofline") or {}).get("frac"), v.get("error"))
 k = r["kernels"]; print({n: (v["avg_ms"], v.get("tflops")) for n, v in k.items() if n in ("gemm_f16x2p", "gemm_f16x2p_lmhead_topk", "attn_decode")})
 PY
-B="timeout 400 python bench.py --cpu-captions 0 --no-checks"
+B="timeout 400 python bench.py --full --cpu-captions 0 --no-checks"
 $B --cpu-seconds 0 --captions 625 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_625.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/${TAG}_bench_625.json'));print('625:',r['value'],r['ms_per_step'])"
 $B --cpu-seconds 12 --workload text_embed --captions 20000 --gemm-mode f16 --steps 5 --warmup 2 > "$OUT/${TAG}_text_f16.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/${TAG}_text_f16.json'));print('text f16:',r['value'],r['ms_per_step'],r['roofline']['frac'],r['roofline']['share_of_tower'],r['cpu_baseline']['value'],{k:v['avg_ms'] for k,v in r['clip_tower_kernels'].items()})"
 $B --cpu-seconds 0 --workload text_embed --captions 20000 --gemm-mode bf16 --steps 3 --warmup 1 > "$OUT/${TAG}_text_bf16.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/${TAG}_text_bf16.json'));print('text bf16:',r['value'],r['ms_per_step'])"
 $B --cpu-seconds 0 --workload image_beam --captions 2014 --gemm-mode f16 --steps 3 --warmup 1 > "$OUT/${TAG}_image_vit_f16.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/${TAG}_image_vit_f16.json'));print('image vit, f16 tower + f16 decode mode:',r['value'],r['ms_per_step'])"
-rm -rf "$OUT/ktt"; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ktt" -- python bench.py --workload text_embed --captions 20000 --gemm-mode f16 --steps 2 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
+rm -rf "$OUT/ktt"; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ktt" -- python bench.py --full --workload text_embed --captions 20000 --gemm-mode f16 --steps 2 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
 find "$OUT/ktt" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_clip_text_f16_kernel_stats.csv" \;
 python tools/trace_summary.py "$OUT/ktt" "$OUT/${TAG}_clip_text_f16_kernels.txt" --title "bench.py --workload text_embed --captions 20000 --gemm-mode f16 --steps 2 --warmup 1 under rocprofv3 --kernel-trace (final tree: one fp16 plane per attention operand)"; rm -rf "$OUT/ktt"
 head -6 "$OUT/${TAG}_clip_text_f16_kernels.txt" | cut -c1-50,95-200

@@ -9,12 +9,12 @@ export TMPDIR=/tmp
 rm -f "$OUT/parity_counts.txt"
 timeout 900 python -m pytest tests/ -x -q -m gpu -k "clip or logits or long_context or text_to_prefix or config4 or make_preds_from or gpt2_small_geometry or mapper or bf16_mode_logits" --durations=8 2>&1 | tail -16 | cut -c1-180
 cat "$OUT/parity_counts.txt" 2>/dev/null | tail -3
-B="timeout 300 python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks"
+B="timeout 300 python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks"
 for m in f16 f16x2; do
   $B --workload text_embed --captions 20000 --gemm-mode $m --steps 3 --warmup 1 > "$OUT/r6b_text_$m.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6b_text_$m.json'));print('text $m:',r['value'],r['ms_per_step'],{k:(v['avg_ms'],v['ms_est']) for k,v in r['clip_tower_kernels'].items()})"
 done
 $B --workload image_beam --captions 2014 --steps 2 --warmup 1 > "$OUT/r6b_image_f16x2.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6b_image_f16x2.json'));print('image:',r['value'],r['ms_per_step'],{k:(v['avg_ms'],v['ms_est']) for k,v in r['clip_tower_kernels'].items()})"
-rm -rf "$OUT/tracetext"; timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tracetext" -- python bench.py --workload text_embed --captions 20000 --gemm-mode f16 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
+rm -rf "$OUT/tracetext"; timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tracetext" -- python bench.py --full --workload text_embed --captions 20000 --gemm-mode f16 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
 python tools/trace_summary.py "$OUT/tracetext" "$OUT/r6_clip_text_f16_kernels.txt" --title "bench.py --workload text_embed --captions 20000 --gemm-mode f16 under rocprofv3 --kernel-trace (lane-per-query attention)"; head -12 "$OUT/r6_clip_text_f16_kernels.txt" | cut -c1-50,95-200
 rm -rf "$OUT/tracetext"
 # knob A/Bs, same box
@@ -26,7 +26,7 @@ echo "--- greedy bf16 5000: default vs CAPDEC_X1_SPLITK=0"
 for e in "X=1" "CAPDEC_X1_SPLITK=0" "X=1" "CAPDEC_X1_SPLITK=0"; do
   env $e $B --workload greedy_mlp --gemm-mode bf16 --steps 10 --warmup 3 --no-smi > "$OUT/tmp.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/tmp.json'));k=r['kernels'];print('$e',r['value'],r['ms_per_step'],'gemm',k['gemm_x1']['ms_est'],'ln',k['layernorm']['ms_est'])"
 done
-timeout 600 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 > "$OUT/r6b_bench.json" 2> "$OUT/r6b_bench.err"; python - <<PY
+timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > "$OUT/r6b_bench.json" 2> "$OUT/r6b_bench.err"; python - <<PY
 import json
 r=json.loads([l for l in open("$OUT/r6b_bench.json") if l.startswith("{")][-1])
 print(r["value"], r["ms_per_step"])

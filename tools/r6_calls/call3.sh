@@ -9,15 +9,15 @@ export TMPDIR=/tmp
 rm -f "$OUT/parity_counts.txt"
 timeout 900 python -m pytest tests/ -x -q -m gpu -k "p40 or clip or logits or long_context or text_to_prefix or config4 or make_preds_from or gpt2_small_geometry or mapper or bf16_mode_logits" --durations=8 2>&1 | tail -16 | cut -c1-180
 cat "$OUT/parity_counts.txt" 2>/dev/null | tail -3
-B="timeout 300 python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks"
+B="timeout 300 python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks"
 for m in f16 f16x2; do
   $B --workload text_embed --captions 20000 --gemm-mode $m --steps 3 --warmup 1 > "$OUT/r6c_text_$m.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6c_text_$m.json'));print('text $m:',r['value'],r['ms_per_step'],{k:(v['avg_ms'],v['ms_est']) for k,v in r['clip_tower_kernels'].items()})"
 done
 $B --workload image_beam --captions 2014 --steps 2 --warmup 1 > "$OUT/r6c_image_f16x2.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6c_image_f16x2.json'));print('image:',r['value'],r['ms_per_step'],{k:(v['avg_ms'],v['ms_est']) for k,v in r['clip_tower_kernels'].items()})"
-rm -rf "$OUT/tracetext"; timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tracetext" -- python bench.py --workload text_embed --captions 20000 --gemm-mode f16 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
+rm -rf "$OUT/tracetext"; timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tracetext" -- python bench.py --full --workload text_embed --captions 20000 --gemm-mode f16 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
 python tools/trace_summary.py "$OUT/tracetext" "$OUT/r6_clip_text_f16_kernels.txt" --title "bench.py --workload text_embed --captions 20000 --gemm-mode f16 under rocprofv3 --kernel-trace (matrix-core prefill attention)"; head -12 "$OUT/r6_clip_text_f16_kernels.txt" | cut -c1-50,95-200
 rm -rf "$OUT/tracetext"
-timeout 600 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 > "$OUT/r6c_bench.json" 2> "$OUT/r6c_bench.err"; python - <<PY
+timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > "$OUT/r6c_bench.json" 2> "$OUT/r6c_bench.err"; python - <<PY
 import json
 r=json.loads([l for l in open("$OUT/r6c_bench.json") if l.startswith("{")][-1])
 print(r["value"], r["ms_per_step"])
@@ -32,5 +32,5 @@ import json
 r=json.loads([l for l in open("$OUT/r6c_bench.json") if l.startswith("{")][-1])
 sp=r["stop_profile"]; print("launched", sp.get("rows_launched_per_step")); print("alive   ", sp.get("rows_alive_per_step"))
 PY
-timeout 300 python bench.py --workload text_embed --captions 20000 --gemm-mode f16 --steps 3 --warmup 1 --cpu-seconds 10 --no-checks > "$OUT/r6c_text_f16_full.json" 2>/dev/null; tail -c 1800 "$OUT/r6c_text_f16_full.json"; echo
-timeout 400 python bench.py --workload image_beam --captions 2014 --steps 2 --warmup 1 --cpu-seconds 10 --no-checks > "$OUT/r6c_image_full.json" 2>/dev/null; tail -c 1500 "$OUT/r6c_image_full.json"; echo
+timeout 300 python bench.py --full --workload text_embed --captions 20000 --gemm-mode f16 --steps 3 --warmup 1 --cpu-seconds 10 --no-checks > "$OUT/r6c_text_f16_full.json" 2>/dev/null; tail -c 1800 "$OUT/r6c_text_f16_full.json"; echo
+timeout 400 python bench.py --full --workload image_beam --captions 2014 --steps 2 --warmup 1 --cpu-seconds 10 --no-checks > "$OUT/r6c_image_full.json" 2>/dev/null; tail -c 1500 "$OUT/r6c_image_full.json"; echo

@@ -9,15 +9,15 @@ OUT=$R/gpurun_out; mkdir -p "$OUT"; cd "$R"
 export TMPDIR=/tmp
 rm -f "$OUT/parity_counts.txt"
 timeout 900 python -m pytest tests/ -x -q -m gpu -k "p40 or clip or long_context or config4 or make_preds_from or compact or midsize or text_to_prefix" --durations=6 2>&1 | tail -12 | cut -c1-180
-B="timeout 300 python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks"
+B="timeout 300 python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks"
 for m in f16 f16x2; do
   $B --workload text_embed --captions 20000 --gemm-mode $m --steps 3 --warmup 1 > "$OUT/r6d_text_$m.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6d_text_$m.json'));print('text $m:',r['value'],r['ms_per_step'],{k:(v['avg_ms'],v['ms_est']) for k,v in r['clip_tower_kernels'].items()})"
 done
 $B --workload image_beam --captions 2014 --steps 2 --warmup 1 > "$OUT/r6d_image_f16x2.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6d_image_f16x2.json'));print('image:',r['value'],r['ms_per_step'],{k:(v['avg_ms'],v['ms_est']) for k,v in r['clip_tower_kernels'].items()})"
-rm -rf "$OUT/tracetext"; timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tracetext" -- python bench.py --workload text_embed --captions 20000 --gemm-mode f16 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
+rm -rf "$OUT/tracetext"; timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tracetext" -- python bench.py --full --workload text_embed --captions 20000 --gemm-mode f16 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
 python tools/trace_summary.py "$OUT/tracetext" "$OUT/r6_clip_text_f16_kernels.txt" --title "bench.py --workload text_embed --captions 20000 --gemm-mode f16 under rocprofv3 --kernel-trace (matrix-core prefill attention, loads up front)"; head -8 "$OUT/r6_clip_text_f16_kernels.txt" | cut -c1-50,95-200
 rm -rf "$OUT/tracetext"
-timeout 600 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 > "$OUT/r6d_bench.json" 2> "$OUT/r6d_bench.err"; python - <<PY
+timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > "$OUT/r6d_bench.json" 2> "$OUT/r6d_bench.err"; python - <<PY
 import json
 r=json.loads([l for l in open("$OUT/r6d_bench.json") if l.startswith("{")][-1])
 print(r["value"], r["ms_per_step"], r["oracle_check"]["ok"], r["ids_check"]["ok"])
@@ -31,7 +31,7 @@ echo "--- item 1a: 625 captions, the N = 768 projections"
 for tag in default pp0 pp0_unsplit; do
   case $tag in default) E="X=1";; pp0) E="CAPDEC_PP=0";; pp0_unsplit) E="CAPDEC_PP=0 CAPDEC_SPLITK_MID=0";; esac
   env $E $B --captions 625 --steps 10 --warmup 3 --no-smi > "$OUT/tmp.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/tmp.json'));k=r['kernels'];print('$tag',r['value'],r['ms_per_step'],'gemm',k['gemm_f16x2p']['ms_est'],'ln',k['layernorm']['ms_est'])"
-  rm -rf "$OUT/trace1a"; env $E timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace1a" -- python bench.py --captions 625 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
+  rm -rf "$OUT/trace1a"; env $E timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace1a" -- python bench.py --full --captions 625 --steps 1 --warmup 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --no-smi > /dev/null 2>&1
   python tools/trace_summary.py "$OUT/trace1a" "$OUT/r6_625_kernels_$tag.txt" --title "bench.py --captions 625 --steps 1 --warmup 1 under rocprofv3 --kernel-trace, $E"; head -9 "$OUT/r6_625_kernels_$tag.txt" | cut -c1-60,95-200
   rm -rf "$OUT/trace1a"
 done

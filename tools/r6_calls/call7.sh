@@ -6,12 +6,12 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"; cd "$R"
 export TMPDIR=/tmp
 timeout 600 python -m pytest tests/ -x -q -m gpu -k "stop or compact or midsize or large_launch" 2>&1 | tail -3 | cut -c1-160
-B="timeout 400 python bench.py --cpu-captions 0 --no-checks --cpu-seconds 0"
+B="timeout 400 python bench.py --full --cpu-captions 0 --no-checks --cpu-seconds 0"
 for i in 1 2; do
   $B --captions 625 --steps 20 --warmup 5 > "$OUT/r6_bench_625.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/r6_bench_625.json'));print('625:',r['value'],r['ms_per_step'])"
   $B --steps 5 --warmup 2 > "$OUT/tmp5000.json" 2>/dev/null; python -c "import json;r=json.load(open('$OUT/tmp5000.json'));print('5000 (5 steps):',r['value'],r['ms_per_step'])"
 done
-timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/r6_bench.json" 2> "$OUT/r6_bench.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/r6_bench.json" 2> "$OUT/r6_bench.err"
 python - "$OUT/r6_bench.json" <<'PY'
 import json, sys
 r = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

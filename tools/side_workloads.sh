@@ -6,7 +6,7 @@ TAG=${1:-r3}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"
 cd "$R"
-B="timeout 300 python bench.py --cpu-seconds 0 --cpu-captions 0 --no-checks --steps 2 --warmup 1"
+B="timeout 300 python bench.py --full --cpu-seconds 0 --cpu-captions 0 --no-checks --steps 2 --warmup 1"
 $B --entry-length 12 > "$OUT/${TAG}_side_T12.json" 2>/dev/null
 $B --workload greedy_mlp > "$OUT/${TAG}_side_greedy_f16x2.json" 2>/dev/null
 $B --workload greedy_mlp --gemm-mode bf16 > "$OUT/${TAG}_side_greedy_bf16.json" 2>/dev/null
@@ -16,10 +16,10 @@ $B --workload text_embed --captions 20000 > "$OUT/${TAG}_side_text_f16x2.json" 2
 $B --workload text_embed --captions 20000 --gemm-mode f16 > "$OUT/${TAG}_side_text_f16.json" 2>/dev/null
 $B --workload image_beam --captions 2014 > "$OUT/${TAG}_side_image_f16x2.json" 2>/dev/null
 $B --workload image_beam --clip rn50x4 --captions 2014 > "$OUT/${TAG}_side_image_rn50x4.json" 2>/dev/null
-timeout 120 python bench.py --workload train_step --steps 10 --warmup 2 --cpu-seconds 5 > "$OUT/${TAG}_side_train_step.json" 2>/dev/null
-timeout 120 python bench.py --workload train_step --train-scope full --steps 10 --warmup 2 --cpu-seconds 5 > "$OUT/${TAG}_side_train_step_full.json" 2>/dev/null
+timeout 120 python bench.py --full --workload train_step --steps 10 --warmup 2 --cpu-seconds 5 > "$OUT/${TAG}_side_train_step.json" 2>/dev/null
+timeout 120 python bench.py --full --workload train_step --train-scope full --steps 10 --warmup 2 --cpu-seconds 5 > "$OUT/${TAG}_side_train_step_full.json" 2>/dev/null
 CAPDEC_FORCE_DIST=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 \
-   bench.py --gpus 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --steps 2 --warmup 1 > "$OUT/${TAG}_side_dist1.json" 2>/dev/null
+   bench.py --full --gpus 1 --cpu-seconds 0 --cpu-captions 0 --no-checks --steps 2 --warmup 1 > "$OUT/${TAG}_side_dist1.json" 2>/dev/null
 python - "$OUT" "$TAG" <<'PY'
 import json, glob, sys, os
 out, tag = sys.argv[1], sys.argv[2]

@@ -11,8 +11,8 @@ OUT=$R/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd "$R"
-timeout 120 python bench.py --workload train_step --steps 10 --warmup 2 --cpu-seconds 5 > "$OUT/${TAG}_train_step_bench.json" 2> "$OUT/${TAG}_train_step_bench.err"
-timeout 150 rocprofv3 --kernel-trace --output-format csv -d "$OUT/${TAG}_kt_train" -- python bench.py --workload train_step --steps 3 --warmup 1 --cpu-seconds 0 \
+timeout 120 python bench.py --full --workload train_step --steps 10 --warmup 2 --cpu-seconds 5 > "$OUT/${TAG}_train_step_bench.json" 2> "$OUT/${TAG}_train_step_bench.err"
+timeout 150 rocprofv3 --kernel-trace --output-format csv -d "$OUT/${TAG}_kt_train" -- python bench.py --full --workload train_step --steps 3 --warmup 1 --cpu-seconds 0 \
     > "$OUT/${TAG}_kt_train.json" 2> "$OUT/${TAG}_kt_train.err"
 python tools/trace_summary.py "$OUT/${TAG}_kt_train" "$OUT/${TAG}_train_kernels.txt" --title "bench.py --workload train_step --steps 3 --warmup 1 under rocprofv3 --kernel-trace (4 steps + weight transposes of the first)"
 find "$OUT/${TAG}_kt_train" -name "*.csv" -delete
