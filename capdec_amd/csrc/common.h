@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/capdec.h"
@@ -111,39 +112,60 @@ struct QkvScatter {
     bool bf16 = false;                      // bf16 mode: the cache holds bf16 -- K / V are rounded (RNE) as they are written
 };
 
-// gemm_f32.hip
+// The epilogue and launch options of one GEMM.  Families: f32 (native fp32), bf16x3 (fp32 A), bf16x3p / f16x2p / x1
+// (packed A; f16x2p includes the wide-tile and ping-pong geometries its planner picks: gemm_h2w.hip, gemm_pp.hip) and the
+// implicit 3x3 convolution.  gemm_dispatch.hip fills the shared fields (gemm_epilogue).
 struct GemmEpilogue {
-    const float *bias = nullptr;   // [N]
-    const float *resid = nullptr;  // [M, ldr] added after the activation
+    const float *bias = nullptr;   // [N]                                       (all)
+    const float *resid = nullptr;  // [M, ldr] added after the activation       (all)
     int ldr = 0;
-    int act = CAPDEC_ACT_NONE;
-    void *splitk_ws = nullptr;     // bf16x3p only: workspace for split-K partial tiles (gemm_splitk_ws_bytes); without it
-    size_t splitk_ws_bytes = 0;    // under-filled grids run unsplit
-    void *packed_out = nullptr;    // bf16x3p only: write act(acc + bias) as the packed split-bf16 A operand (K = N)
-                                   // of the next GEMM instead of fp32 C
+    int act = CAPDEC_ACT_NONE;     //                                           (all)
+    void *splitk_ws = nullptr;     // bf16x3p / f16x2p / x1: workspace for split-K partial tiles (gemm_splitk_ws_bytes);
+    size_t splitk_ws_bytes = 0;    // without it under-filled grids run unsplit
+    void *packed_out = nullptr;    // bf16x3p / f16x2p / x1 / conv: write act(acc + bias) as the packed A operand (K = N, the
+                                   // launch's format) of the next GEMM instead of fp32 C
     const Tuning *tune = nullptr;  // the context's environment knobs (config.h); nullptr = every default
-    const QkvScatter *qkv_scatter = nullptr;   // f16x2p, unsplit grids only (see QkvScatter)
-    bool invariant = false;        // batch-invariant mode: the unsplit 128 x 128 kernel whatever M is (no planner, no split-K)
+    const QkvScatter *qkv_scatter = nullptr;   // f16x2p / x1, unsplit grids only (see QkvScatter)
+    bool invariant = false;        // f16x2p only -- batch-invariant mode: the unsplit 128 x 128 kernel whatever M is (no
+                                   // planner, no split-K)
     bool wide_ok = false;          // f16x2p only: the B operand is a weight with max |w| < 16, so its high plane can be scaled
                                    // by 2^11 in fp16 registers (the single-accumulator kernels of gemm_h2w.hip)
     const void *resid_packed = nullptr;   // f16x2p / x1 with packed_out only: residual [M, N] stored as a packed operand of
                                           // the output's format (added after the activation; no split-K then)
-    // Optional LayerNorm of the RESULT rows, fused into the split-K reduce pass (only when the launch splits K, C has
-    // N = ldc columns and N <= 1024): ln_out receives LayerNorm(C row) as a packed operand (format of the launch);
-    // *ln_done is set to 1 when the fusion happened, left untouched otherwise (the caller then runs its own LayerNorm)
+    // bf16x3p / f16x2p / x1: optional LayerNorm of the RESULT rows, fused into the split-K reduce pass (only when the launch
+    // splits K, C has N = ldc columns and N <= 1024): ln_out receives LayerNorm(C row) as a packed operand (format of the
+    // launch); *ln_done is set to 1 when the fusion happened, left untouched otherwise (the caller then runs its own LayerNorm)
     const float *ln_w = nullptr, *ln_b = nullptr;
     float ln_eps = 1e-5f;
     void *ln_out = nullptr;
     int *ln_done = nullptr;
 };
+// Outputs of the fused lm_head launchers (*_topk, *_topk_dev): per (row, 128-column tile) the max, sum exp(x - max) and the
+// k best (value, column) pairs -- [rows, tiles] and [rows, tiles, k]
+struct TopkOut {
+    float *tile_max, *tile_sum, *cand_val;
+    int *cand_idx;
+};
+// f(std::integral_constant<int, K>()) for the runtime k in 1..TOPK_MAX: one instantiation of a top-k kernel per k
+template <int K = 1, class F>
+inline int with_topk_k(int k, const char *what, F &&f) {
+    if constexpr (K <= TOPK_MAX) {
+        if (k != K) return with_topk_k<K + 1>(k, what, f);
+        f(std::integral_constant<int, K>());
+        return 0;
+    }
+    CAPDEC_CHECK(false, std::string(what) + ": k must be in 1..8");
+    return 1;
+}
 inline const Tuning &tuning_of(const GemmEpilogue &e) { return e.tune ? *e.tune : default_tuning(); }
+
+// gemm_f32.hip
 int launch_gemm_f32(hipStream_t st, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc,
                     int M, int N, int K, const GemmEpilogue &epi);
 // lm_head: logits tile never leaves the CU; per (row, 128-column tile) emits max, sum exp(x - max)
 // and the top-k (value, column) pairs.
 int launch_gemm_f32_topk(hipStream_t st, const float *A, int lda, const float *Bt, int ldb, int M, int N, int K,
-                         int k, float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx,
-                         const Tuning *tune = nullptr);
+                         int k, float inv_temp, const TopkOut &o, const Tuning *tune = nullptr);
 inline int gemm_tiles_n(int N) { return (N + GEMM_BN - 1) / GEMM_BN; }
 
 // gemm_bf16x3.hip: the same two GEMMs on the bf16 matrix cores with operands split into three bf16
@@ -154,13 +176,13 @@ int launch_pack_planes(hipStream_t st, const float *w, int N, int K, void *out);
 int launch_gemm_bf16x3(hipStream_t st, const float *A, int lda, const void *Bpacked, float *C, int ldc, int M, int N,
                        int K, const GemmEpilogue &epi);
 int launch_gemm_bf16x3_topk(hipStream_t st, const float *A, int lda, const void *Bpacked, int M, int N, int K, int k,
-                            float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx);
+                            float inv_temp, const TopkOut &o);
 // packed-A variants: A already split / tile-major (written by launch_layernorm_packed, launch_pack_planes): both
 // operands move by LDS-DMA
 int launch_gemm_bf16x3p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
                         const GemmEpilogue &epi);
 int launch_gemm_bf16x3p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                             float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx);
+                             float inv_temp, const TopkOut &o);
 // split-K of the packed-A kernel for under-filled grids: number of K slices (1 = none) and the workspace it needs
 int gemm_splitk_slices(int M, int N, int K, const Tuning &t = default_tuning());
 size_t gemm_splitk_ws_bytes(int M, int N, int K, const Tuning &t = default_tuning());
@@ -176,7 +198,7 @@ int launch_pack_planes_h2_t(hipStream_t st, const float *src, int ld, int rows, 
 int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
                        const GemmEpilogue &epi);
 int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                            float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx);
+                            float inv_temp, const TopkOut &o);
 // round-3 wide-tile kernels with ONE accumulator set (gemm_h2w.hip); scale = 2^(t - 11), t = pack-time pre-scale
 // exponent of the weights; `which`: 2 = 256x128 (two blocks per CU), 3 = 256x256 (8 waves), 6 = 256x256 (4 waves), 8 = 128x192
 int h2w_plan(int M, int N, int K);
@@ -184,8 +206,7 @@ int launch_absmax_bits(hipStream_t st, const float *w, size_t n, unsigned *d_out
 int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
                     int K, const GemmEpilogue &epi, float scale);
 int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                         float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx,
-                         const Tuning *tune = nullptr);
+                         float inv_temp, const TopkOut &o, const Tuning *tune = nullptr);
 // round-4 ping-pong kernels (gemm_pp.hip): ONE 8-wavefront block per CU, the two wavefronts of a SIMD alternate between a
 // load phase and a matrix phase; `which`: 10 = 256x128 (two accumulator sets), 11 = 256x128, 12 = 256x256, 13 = 128x256 (one set)
 int launch_gemm_pp(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
@@ -195,16 +216,16 @@ int pp_plan(int M, int N, int K, bool wide_ok, bool can_split, int mode = 2);
 size_t pp_splitk_ws_bytes(int which, int M, int N, int K);
 // exact second pass of the fused lm_head (decode.hip): k = 5 lists for the *m_dev rows of a compacted packed A operand
 int launch_gemm_h2w_topk_dev(hipStream_t st, const void *Apacked, const void *Bpacked, const int *m_dev, int N, int K,
-                             float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx);
+                             float inv_temp, const TopkOut &o);
 int launch_gemm_x1_topk_dev(hipStream_t st, const void *Apacked, const void *Bpacked, const int *m_dev, int N, int K,
-                            float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx, int fmt);
+                            float inv_temp, const TopkOut &o, int fmt);
 // generic packer for any PackFmt (gemm_f16x2.hip); the one-plane formats use it
 int launch_pack_planes_fmt(hipStream_t st, const float *w, int ldw, int N, int K, void *out, int fmt);
 // round-2 one-plane kernels on the f16x2 main loop (gemm_f16x2.hip): 128x128 tile, two blocks per CU, 32-deep stages
 int launch_gemm_x1(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
                    const GemmEpilogue &epi, int fmt);
 int launch_gemm_x1_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                        float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx, int fmt);
+                        float inv_temp, const TopkOut &o, int fmt);
 // LayerNorm whose output goes straight into the packed split-bf16 A format of the next GEMM (d % 16 == 0)
 int launch_layernorm_packed(hipStream_t st, const float *x, int ldx, const float *w, const float *b, float eps,
                             void *packed, int rows, int d, int fmt = 0);

@@ -2,7 +2,8 @@
 // containers, the per-family profiler and the host-side pieces each unit exports to the others.
 //   capi_context.hip  context lifetime, streams, modes, memory, timers, profiler, decode statistics, the environment knobs
 //   weights.hip       capdec_load_* (uploads; Conv1D transposes; BatchNorm folding)
-//   gemm_dispatch.hip the GEMM planner: operand planes cache, which kernel / split for a projection, capdec_gemm_f32
+//   gemm_dispatch.hip the GEMM planner: operand planes cache, which kernel / split for a projection and for the fused
+//                     lm_head, capdec_gemm_f32
 //   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam decode loop, mapper
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
 //   clip.hip          CLIP ViT-B/32 towers, the ModifiedResNet tower, image preprocessing
@@ -227,6 +228,17 @@ inline bool mode_single(const capdec_ctx *c) { return c->gemm_mode == GEMM_BF16 
 int pack_any(capdec_ctx *c, const float *W, int N, int K, int fmt, void *out);
 int planes_of(capdec_ctx *c, const float *W, int N, int K, bool cache, const void **out, int fmt_override = -1,
               bool *wide_ok = nullptr);
+// profiler family of a packed-operand GEMM in format fmt (PK_*: bf16x3.h)
+int gemm_family(int fmt);
+// Fills the GemmEpilogue fields every launch shares; call it once e.wide_ok is known.
+//   tune       the context's knobs
+//   invariant  apply the batch-invariant rule: the unsplit 128 x 128 kernel whatever M is (callers pass c->batch_invariant;
+//              the test hook passes false)
+//   split      the caller allows split-K: the workspace is attached when the planner wants one (never batch-invariant)
+int gemm_epilogue(capdec_ctx *c, GemmEpilogue &e, int M, int N, int K, bool split, bool invariant);
+// C = epilogue(A . Bt^T) on the native fp32 MFMA kernel (the f32 mode, other K; the train step under CAPDEC_TRAIN_F16X2=0)
+int gemm_native(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N, int K,
+                GemmEpilogue e = GemmEpilogue());
 // C = act(A . Bt^T + bias) + resid with fp32 A in HBM (mapper, patch embedding, projections)
 int gemm(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N, int K,
          const float *bias, int act, const float *resid = nullptr, int ldr = 0, bool weight = true);
@@ -241,6 +253,16 @@ int gemm_packed(capdec_ctx *c, const void *Apk, const float *W, float *C, int ld
 int ln_gemm_packed(capdec_ctx *c, const float *h, int ldh, const float *lnw, const float *lnb, float eps, const float *W,
                    float *C, int ldc, int M, int N, int K, const float *bias, int act, void *packed_out = nullptr,
                    bool ln_ready = false, const QkvScatter *qkv_scatter = nullptr);
+
+// The fused lm_head: LayerNorm of the M rows of h, then LN(h) . W^T (W [N, K]) fused with the per-(row, 128-column tile)
+// top-k of the logits * inv_temp into o.  k3_ok: a k = 5 selection may keep three candidates per tile where the kernel
+// allows it (the wide two-plane tile; the one-plane kernel from 2048 rows); *k3 reports whether it did -- the rows the
+// merge then flags need gemm_topk_dev.  The packed modes leave LN(h) in c->xpk.
+int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const float *lnb, float eps, const float *W,
+                 int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3);
+// ... its exact second pass: k = 5 lists for the *m_dev rows of the packed operand Apk (in the format of the mode)
+int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_dev, int N, int K, float inv_temp,
+                  const TopkOut &o);
 
 // ---- decode.hip: the block stack (GPT-2 and the CLIP towers run on it)
 struct StepShape {

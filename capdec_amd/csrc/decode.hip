@@ -112,7 +112,6 @@ static int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv) {
 static int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp) {
     const Gpt2 &g = c->gpt;
     const int d = g.d, nt = gemm_tiles_n(g.vocab);
-    CAPDEC_TRY(c->xl.ensure((size_t)R * d * 4));
     CAPDEC_TRY(c->tmax.ensure((size_t)R * nt * 4));
     CAPDEC_TRY(c->tsum.ensure((size_t)R * nt * 4));
     CAPDEC_TRY(c->cval.ensure((size_t)R * nt * k * 4));
@@ -120,59 +119,14 @@ static int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k,
     CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
     CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
     CAPDEC_TRY(c->topi.ensure((size_t)R * k * 4));
-    bool k3 = false;                 // the fused kernel kept 3 candidates per tile of a k = 5 selection (below)
-    const void *wte_planes = nullptr;
-    if (use_packed_a(c, d)) {
-        CAPDEC_TRY(c->xpk.ensure(x3_packed_bytes_host(R, d)));
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm_packed(c->stream, h0, ldh, g.lnfw, g.lnfb, g.eps, c->xpk.p, R, d, pack_fmt(c))); }
-        const void *pl = nullptr;
-        bool wide_ok = false;
-        CAPDEC_TRY(planes_of(c, g.wte, g.vocab, d, true, &pl, -1, &wide_ok));
-        if (c->gemm_mode == GEMM_F16X2) {
-            ProfScope ps(c, F_LMHEAD_H2, 2.0 * R * (double)g.vocab * d);
-            // 256 x 128 tiles with one accumulator set once the grid is many rounds deep (each wte panel is then fetched
-            // by half as many row tiles); small row counts keep the 128-row tile (more blocks, the same partial lists)
-            const bool lm_wide = c->tune.lmhead_wide;
-            const int h2w = c->tune.h2w;
-            if (wide_ok && !c->batch_invariant && ((lm_wide && h2w >= 1 && R >= 2048) || h2w >= 2)) {   // (CAPDEC_H2W >= 2: forced, tests)
-                // Beam search (k = 5): keep THREE candidates per (row, 128-column tile) -- two selection rounds fewer in
-                // every tile's epilogue.  The merge then knows exactly which rows that can have been too few for (some
-                // tile's third candidate is still strictly better than the row's fifth: with 393 tiles a rare event) and
-                // those rows alone go through the k = 5 kernel again, compacted; the result is the k = 5 result.
-                k3 = c->tune.lmhead_k3 && k == 5 && !c->k3_off;
-                CAPDEC_TRY(launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, R, g.vocab, d, k3 ? 3 : k, inv_temp, c->tmax.as<float>(),
-                                                c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>(), &c->tune));
-                wte_planes = pl;
-            } else
-            CAPDEC_TRY(launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, R, g.vocab, d, k, inv_temp, c->tmax.as<float>(),
-                                               c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()));
-        } else if (mode_single(c)) {
-            ProfScope ps(c, F_LMHEAD_BF16, 2.0 * R * (double)g.vocab * d);
-            k3 = c->tune.lmhead_k3 && k == 5 && R >= 2048 && !c->batch_invariant && !c->k3_off;   // (as in the two-plane mode above)
-            wte_planes = pl;
-            CAPDEC_TRY(launch_gemm_x1_topk(c->stream, c->xpk.p, pl, R, g.vocab, d, k3 ? 3 : k, inv_temp, c->tmax.as<float>(),
-                                           c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>(), pack_fmt(c)));
-        } else {
-            ProfScope ps(c, F_LMHEAD_X3, 2.0 * R * (double)g.vocab * d);
-            CAPDEC_TRY(launch_gemm_bf16x3p_topk(c->stream, c->xpk.p, pl, R, g.vocab, d, k, inv_temp,
-                                                c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(),
-                                                c->cidx.as<int>()));
-        }
-    } else if (c->gemm_mode != GEMM_F32) {
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, h0, ldh, g.lnfw, g.lnfb, g.eps, c->xl.as<float>(), d, R, d)); }
-        const void *pl = nullptr;
-        CAPDEC_TRY(planes_of(c, g.wte, g.vocab, d, true, &pl));
-        ProfScope ps(c, F_LMHEAD_X3, 2.0 * R * (double)g.vocab * d);
-        CAPDEC_TRY(launch_gemm_bf16x3_topk(c->stream, c->xl.as<float>(), d, pl, R, g.vocab, d, k, inv_temp,
-                                           c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(),
-                                           c->cidx.as<int>()));
-    } else {
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, h0, ldh, g.lnfw, g.lnfb, g.eps, c->xl.as<float>(), d, R, d)); }
-        ProfScope ps(c, F_LMHEAD, 2.0 * R * (double)g.vocab * d);
-        CAPDEC_TRY(launch_gemm_f32_topk(c->stream, c->xl.as<float>(), d, g.wte, d, R, g.vocab, d, k, inv_temp,
-                                        c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(),
-                                        c->cidx.as<int>(), &c->tune));
-    }
+    const TopkOut o{c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()};
+    // Beam search (k = 5) may keep THREE candidates per (row, 128-column tile) -- two selection rounds fewer in every tile's
+    // epilogue.  The merge then knows exactly which rows that can have been too few for (some tile's third candidate is
+    // still strictly better than the row's fifth: with 393 tiles a rare event) and those rows alone go through the k = 5
+    // kernel again, compacted; the result is the k = 5 result.
+    bool k3 = false;
+    CAPDEC_TRY(ln_gemm_topk(c, h0, ldh, g.lnfw, g.lnfb, g.eps, g.wte, R, g.vocab, d, k, inv_temp, o,
+                            c->tune.lmhead_k3 && k == 5 && !c->k3_off, &k3));
     if (k3) {
         CAPDEC_TRY(c->lmflag.ensure(((size_t)R + 2) * 4));
         CAPDEC_TRY(c->xpk2.ensure(x3_packed_bytes_host(R, d)));
@@ -180,33 +134,23 @@ static int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k,
         {
             ProfScope ps(c, F_SELECT);
             CAPDEC_HIP(hipMemsetAsync(cnt, 0, sizeof(int), c->stream));
-            CAPDEC_TRY(launch_topk_merge_k3(c->stream, c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(),
-                                            c->cidx.as<int>(), R, nt, c->lse.as<float>(), c->topv.as<float>(),
-                                            c->topi.as<int>(), rows, cnt, total));
+            CAPDEC_TRY(launch_topk_merge_k3(c->stream, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, R, nt,
+                                            c->lse.as<float>(), c->topv.as<float>(), c->topi.as<int>(), rows, cnt, total));
         }
-        // the second pass: gather, k = 5 kernel over the device-side row count, merge (the partial lists of the first pass
-        // are dead once its merge has run: their buffers are reused)
+        // the second pass: gather (the packed LayerNorm output sits in c->xpk), k = 5 kernel over the device-side row count,
+        // merge (the partial lists of the first pass are dead once its merge has run: their buffers are reused)
         ProfScope ps(c, F_LMHEAD_2ND);
         CAPDEC_TRY(launch_gather_packed_rows(c->stream, c->xpk.p, d, rows, cnt, R, c->xpk2.p, pack_fmt(c)));
-        if (mode_single(c))
-            CAPDEC_TRY(launch_gemm_x1_topk_dev(c->stream, c->xpk2.p, wte_planes, cnt, g.vocab, d, inv_temp, c->tmax.as<float>(),
-                                               c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>(), pack_fmt(c)));
-        else
-            CAPDEC_TRY(launch_gemm_h2w_topk_dev(c->stream, c->xpk2.p, wte_planes, cnt, g.vocab, d, inv_temp, c->tmax.as<float>(),
-                                                c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()));
-        CAPDEC_TRY(launch_topk_merge_rows(c->stream, c->cval.as<float>(), c->cidx.as<int>(), cnt, rows, R, nt,
-                                          c->topv.as<float>(), c->topi.as<int>()));
+        CAPDEC_TRY(gemm_topk_dev(c, c->xpk2.p, g.wte, cnt, g.vocab, d, inv_temp, o));
+        CAPDEC_TRY(launch_topk_merge_rows(c->stream, o.cand_val, o.cand_idx, cnt, rows, R, nt, c->topv.as<float>(),
+                                          c->topi.as<int>()));
         c->lmflag_live = true;
         c->k3_rows += R;
         return 0;
     }
-    {
-        ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_topk_merge(c->stream, c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(),
-                                     c->cidx.as<int>(), R, nt, k, c->lse.as<float>(), c->topv.as<float>(),
-                                     c->topi.as<int>()));
-    }
-    return 0;
+    ProfScope ps(c, F_SELECT);
+    return launch_topk_merge(c->stream, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, R, nt, k, c->lse.as<float>(),
+                             c->topv.as<float>(), c->topi.as<int>());
 }
 
 // geometry only (the CLIP towers attend straight from the qkv activations and never touch a cache)

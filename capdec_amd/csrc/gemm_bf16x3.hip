@@ -621,25 +621,14 @@ int launch_gemm_bf16x3p(hipStream_t st, const void *Apacked, const void *Bpacked
 }
 
 int launch_gemm_bf16x3p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                             float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx) {
+                             float inv_temp, const TopkOut &o) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_bf16x3p_topk: K must be a multiple of 64");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid(tiles_m * tiles_n), block(256);
-#define LAUNCH_TOPKP(KS)                                                                                          \
-    hipLaunchKernelGGL(gemm_bf16x3p_topk_kernel<KS>, grid, block, 0, st, (const __bf16 *)Apacked,                  \
-                       (const __bf16 *)Bpacked, M, N, K, inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n)
-    switch (k) {
-        case 1: LAUNCH_TOPKP(1); break;
-        case 2: LAUNCH_TOPKP(2); break;
-        case 3: LAUNCH_TOPKP(3); break;
-        case 4: LAUNCH_TOPKP(4); break;
-        case 5: LAUNCH_TOPKP(5); break;
-        case 6: LAUNCH_TOPKP(6); break;
-        case 7: LAUNCH_TOPKP(7); break;
-        case 8: LAUNCH_TOPKP(8); break;
-        default: CAPDEC_CHECK(false, "gemm_topk: k must be in 1..8");
-    }
-#undef LAUNCH_TOPKP
+    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
+        hipLaunchKernelGGL(gemm_bf16x3p_topk_kernel<KS>, grid, block, 0, st, (const __bf16 *)Apacked, (const __bf16 *)Bpacked,
+                           M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_m, tiles_n);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -673,32 +662,21 @@ int launch_gemm_bf16x3(hipStream_t st, const float *A, int lda, const void *Bpac
 }
 
 int launch_gemm_bf16x3_topk(hipStream_t st, const float *A, int lda, const void *Bpacked, int M, int N, int K, int k,
-                            float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx) {
+                            float inv_temp, const TopkOut &o) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0, "gemm_topk: empty problem");
     CAPDEC_CHECK(K % 64 == 0 && lda % 4 == 0, "gemm_bf16x3_topk: K must be a multiple of 64");
     const int tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     const bool small = x3_use_small_tile(M, tiles_n, default_tuning());
     const int bm = small ? 64 : 128, tiles_m = (M + bm - 1) / bm;
     dim3 grid(tiles_m * tiles_n), block(256);
-#define LAUNCH_TOPK(KS)                                                                                               \
-    if (small)                                                                                                        \
-        hipLaunchKernelGGL((gemm_bf16x3_topk_kernel<KS, 1>), grid, block, 0, st, A, lda, (const __bf16 *)Bpacked, M, N, K, \
-                           inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n);                       \
-    else                                                                                                              \
-        hipLaunchKernelGGL((gemm_bf16x3_topk_kernel<KS, 2>), grid, block, 0, st, A, lda, (const __bf16 *)Bpacked, M, N, K, \
-                           inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n)
-    switch (k) {
-        case 1: LAUNCH_TOPK(1); break;
-        case 2: LAUNCH_TOPK(2); break;
-        case 3: LAUNCH_TOPK(3); break;
-        case 4: LAUNCH_TOPK(4); break;
-        case 5: LAUNCH_TOPK(5); break;
-        case 6: LAUNCH_TOPK(6); break;
-        case 7: LAUNCH_TOPK(7); break;
-        case 8: LAUNCH_TOPK(8); break;
-        default: CAPDEC_CHECK(false, "gemm_topk: k must be in 1..8");
-    }
-#undef LAUNCH_TOPK
+    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
+        if (small)
+            hipLaunchKernelGGL((gemm_bf16x3_topk_kernel<KS, 1>), grid, block, 0, st, A, lda, (const __bf16 *)Bpacked, M, N, K,
+                               inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_m, tiles_n);
+        else
+            hipLaunchKernelGGL((gemm_bf16x3_topk_kernel<KS, 2>), grid, block, 0, st, A, lda, (const __bf16 *)Bpacked, M, N, K,
+                               inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_m, tiles_n);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

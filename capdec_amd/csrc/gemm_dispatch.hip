@@ -1,7 +1,8 @@
 // The GEMM planner behind every projection of the path: the cache of packed weight planes, which kernel family and
-// operand format a launch takes in the context's precision mode, the LayerNorm -> GEMM and packed-chain forms of the block
-// stack, and capdec_gemm_f32 (the test / micro-benchmark hook onto the same launchers).  Tile geometry and split-K are
-// chosen one level down (launch_gemm_f16x2p / pp_plan / h2w_plan) from the shape and the context's Tuning.
+// operand format a launch takes in the context's precision mode, the shared epilogue fields and split-K workspace, the
+// LayerNorm -> GEMM and packed-chain forms of the block stack, the fused lm_head (LayerNorm -> GEMM -> per-tile top-k), and
+// capdec_gemm_f32 (the test / micro-benchmark hook onto the same launchers).  Tile geometry and split-K slices are chosen one
+// level down (launch_gemm_f16x2p / pp_plan / h2w_plan) from the shape and the context's Tuning.
 #include "context.h"
 
 namespace capdec {
@@ -27,10 +28,6 @@ int pack_fmt(const capdec_ctx *c) {
         case GEMM_F16: return PK_F16X1;
         default: return PK_BF16X3;
     }
-}
-static int gemm_single(capdec_ctx *c, const void *A, const void *B, float *C, int ldc, int M, int N, int K,
-                       const GemmEpilogue &e) {
-    return launch_gemm_x1(c->stream, A, B, C, ldc, M, N, K, e, pack_fmt(c));
 }
 int pack_any(capdec_ctx *c, const float *W, int N, int K, int fmt, void *out) {
     if (fmt == PK_F16X2) return launch_pack_planes_h2(c->stream, W, K, N, K, out);
@@ -84,6 +81,38 @@ int planes_of(capdec_ctx *c, const float *W, int N, int K, bool cache, const voi
     return 0;
 }
 
+int gemm_family(int fmt) { return fmt == PK_F16X2 ? F_GEMM_H2P : fmt == PK_BF16X3 ? F_GEMM_X3P : F_GEMM_BF16P; }
+
+int gemm_epilogue(capdec_ctx *c, GemmEpilogue &e, int M, int N, int K, bool split, bool invariant) {
+    e.tune = &c->tune;
+    if (invariant) { e.wide_ok = false; e.invariant = true; }      // (the geometry planners look at M)
+    const size_t wsb = split && !c->batch_invariant ? gemm_splitk_ws_bytes(M, N, K, c->tune) : 0;
+    if (wsb) {
+        CAPDEC_TRY(c->splitk.ensure(wsb));
+        e.splitk_ws = c->splitk.p;
+        e.splitk_ws_bytes = c->splitk.cap;
+    }
+    return 0;
+}
+
+// C = epilogue(Apk . Bpk^T) with both operands packed in format fmt: two fp16 planes -> f16x2p (whose planner picks among
+// the 128 x 128, wide and ping-pong tiles), three bf16 planes -> bf16x3p, one 16-bit plane -> x1.  flops: what the profiler
+// books for the launch
+static int launch_packed(capdec_ctx *c, int fmt, const void *Apk, const void *Bpk, float *C, int ldc, int M, int N, int K,
+                         const GemmEpilogue &e, double flops) {
+    ProfScope ps(c, gemm_family(fmt), flops);
+    if (fmt == PK_F16X2) return launch_gemm_f16x2p(c->stream, Apk, Bpk, C, ldc, M, N, K, e);
+    if (fmt == PK_BF16X3) return launch_gemm_bf16x3p(c->stream, Apk, Bpk, C, ldc, M, N, K, e);
+    return launch_gemm_x1(c->stream, Apk, Bpk, C, ldc, M, N, K, e, fmt);
+}
+
+int gemm_native(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N, int K,
+                GemmEpilogue e) {
+    e.tune = &c->tune;
+    ProfScope ps(c, F_GEMM, 2.0 * M * (double)N * K);
+    return launch_gemm_f32(c->stream, A, lda, Bt, ldb, C, ldc, M, N, K, e);
+}
+
 int gemm(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N,
                 int K, const float *bias, int act, const float *resid, int ldr, bool weight) {
     GemmEpilogue e;
@@ -98,17 +127,10 @@ int gemm(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float
         // whose 16-bit operands are confined to the GPT-2 / CLIP block stacks and the lm_head
         const void *pl = nullptr;
         CAPDEC_TRY(planes_of(c, Bt, N, K, weight, &pl, PK_F16X2, &e.wide_ok));
-        if (c->batch_invariant) { e.wide_ok = false; e.invariant = true; }      // (the geometry planners look at M)
         CAPDEC_TRY(c->a_tmp.ensure(x3_packed_bytes(M, K, PK_F16X2)));
         { ProfScope ps(c, F_PACK); CAPDEC_TRY(launch_pack_planes_h2(c->stream, A, lda, M, K, c->a_tmp.p)); }
-        const size_t wsb = c->batch_invariant ? 0 : gemm_splitk_ws_bytes(M, N, K, c->tune);
-        if (wsb) {
-            CAPDEC_TRY(c->splitk.ensure(wsb));
-            e.splitk_ws = c->splitk.p;
-            e.splitk_ws_bytes = c->splitk.cap;
-        }
-        ProfScope ps(c, F_GEMM_H2P, 2.0 * M * (double)N * K);
-        return launch_gemm_f16x2p(c->stream, c->a_tmp.p, pl, C, ldc, M, N, K, e);
+        CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, /*split=*/true, c->batch_invariant));
+        return launch_packed(c, PK_F16X2, c->a_tmp.p, pl, C, ldc, M, N, K, e, 2.0 * M * (double)N * K);
     }
     // (bf16 mode: GEMMs whose A operand is fp32 in HBM -- mapper, patch embedding -- keep the split kernel)
     if (c->gemm_mode != GEMM_F32 && ldb == K && K % 64 == 0) {   // other K: native fp32 MFMA
@@ -117,8 +139,7 @@ int gemm(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float
         ProfScope ps(c, F_GEMM_X3, 2.0 * M * (double)N * K);
         return launch_gemm_bf16x3(c->stream, A, lda, pl, C, ldc, M, N, K, e);
     }
-    ProfScope ps(c, F_GEMM, 2.0 * M * (double)N * K);
-    return launch_gemm_f32(c->stream, A, lda, Bt, ldb, C, ldc, M, N, K, e);
+    return gemm_native(c, A, lda, Bt, ldb, C, ldc, M, N, K, e);
 }
 
 // C [N1, N2] = Xa^T Xb for fp32 Xa [rows, N1], Xb [rows, N2] (row-major, row strides lda / ldb): the weight-gradient product of the train
@@ -134,20 +155,12 @@ int gemm_tn(capdec_ctx *c, const float *Xa, int lda, const float *Xb, int ldb, i
         CAPDEC_TRY(launch_pack_planes_h2_t(c->stream, Xb, ldb, rows, N2, Kp, c->x3_tmp.p));
     }
     GemmEpilogue e;
-    e.tune = &c->tune;
-    if (c->batch_invariant) e.invariant = true;
-    const size_t wsb = c->batch_invariant ? 0 : gemm_splitk_ws_bytes(N1, N2, Kp, c->tune);
-    if (wsb) {
-        CAPDEC_TRY(c->splitk.ensure(wsb));
-        e.splitk_ws = c->splitk.p;
-        e.splitk_ws_bytes = c->splitk.cap;
-    }
-    ProfScope ps(c, F_GEMM_H2P, 2.0 * N1 * (double)N2 * rows);
-    return launch_gemm_f16x2p(c->stream, c->a_tmp.p, c->x3_tmp.p, C, ldc, N1, N2, Kp, e);
+    CAPDEC_TRY(gemm_epilogue(c, e, N1, N2, Kp, /*split=*/true, c->batch_invariant));
+    return launch_packed(c, PK_F16X2, c->a_tmp.p, c->x3_tmp.p, C, ldc, N1, N2, Kp, e, 2.0 * N1 * (double)N2 * rows);
 }
 
-// LayerNorm -> GEMM with the normalised rows handed over in packed split-bf16 form (never fp32 in HBM).
-// Returns 1 in *done when the packed path ran; otherwise the caller runs the fp32-activation path.
+// LayerNorm -> GEMM with the normalised rows handed over as the packed A operand of the mode (never fp32 in HBM)?
+// Otherwise the caller runs the fp32-activation path.
 bool use_packed_a(capdec_ctx *c, int K) {
     return (mode_single(c) || c->gemm_mode == GEMM_F16X2 || (c->gemm_mode == GEMM_BF16X3 && c->pack_a)) && K % 64 == 0;
 }
@@ -162,10 +175,8 @@ int gemm_packed(capdec_ctx *c, const void *Apk, const float *W, float *C, int ld
                        const QkvScatter *qkv_scatter) {
     const void *pl = nullptr;
     GemmEpilogue e;
-    e.tune = &c->tune;
     e.qkv_scatter = qkv_scatter;
     CAPDEC_TRY(planes_of(c, W, N, K, true, &pl, -1, &e.wide_ok));
-    if (c->batch_invariant) { e.wide_ok = false; e.invariant = true; }          // (the geometry planners look at M)
     e.bias = bias;
     e.act = act;
     e.resid = resid;
@@ -176,25 +187,10 @@ int gemm_packed(capdec_ctx *c, const void *Apk, const float *W, float *C, int ld
         CAPDEC_TRY(c->xpk.ensure(x3_packed_bytes_host(M, N)));
         e.ln_w = next_ln->w; e.ln_b = next_ln->b; e.ln_eps = next_ln->eps; e.ln_out = c->xpk.p; e.ln_done = next_ln->done;
     }
-    if (c->gemm_mode != GEMM_F32) {
-        const bool x1_split = c->tune.x1_splitk;
-        const size_t wsb = ((mode_single(c) && !x1_split) || c->batch_invariant || qkv_scatter) ? 0 : gemm_splitk_ws_bytes(M, N, K, c->tune);
-        if (wsb) {
-            CAPDEC_TRY(c->splitk.ensure(wsb));
-            e.splitk_ws = c->splitk.p;
-            e.splitk_ws_bytes = c->splitk.cap;
-        }
-    }
-    if (mode_single(c)) {   // one 16-bit plane per operand (bf16 / fp16), one MFMA per product
-        ProfScope ps(c, F_GEMM_BF16P, 2.0 * M * (double)N * K);
-        return gemm_single(c, Apk, pl, C, ldc, M, N, K, e);
-    }
-    if (c->gemm_mode == GEMM_F16X2) {   // two fp16 planes, three MFMAs per product (fp32-accurate)
-        ProfScope ps(c, F_GEMM_H2P, 2.0 * M * (double)N * K);
-        return launch_gemm_f16x2p(c->stream, Apk, pl, C, ldc, M, N, K, e);
-    }
-    ProfScope ps(c, F_GEMM_X3P, 2.0 * M * (double)N * K);
-    return launch_gemm_bf16x3p(c->stream, Apk, pl, C, ldc, M, N, K, e);
+    // (no split-K under the qkv scatter; the one-plane kernels split only under CAPDEC_X1_SPLITK)
+    const bool split = c->gemm_mode != GEMM_F32 && !qkv_scatter && (!mode_single(c) || c->tune.x1_splitk);
+    CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, split, c->batch_invariant));
+    return launch_packed(c, pack_fmt(c), Apk, pl, C, ldc, M, N, K, e, 2.0 * M * (double)N * K);
 }
 
 // (ln_ready: c->xpk already holds LayerNorm(h) -- written by the fused split-K reduce of the previous GEMM)
@@ -209,6 +205,55 @@ int ln_gemm_packed(capdec_ctx *c, const float *h, int ldh, const float *lnw, con
     return gemm_packed(c, c->xpk.p, W, C, ldc, M, N, K, bias, act, nullptr, 0, packed_out, nullptr, nullptr, qkv_scatter);
 }
 
+int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const float *lnb, float eps, const float *W,
+                 int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3) {
+    const double flops = 2.0 * M * (double)N * K;
+    *k3 = false;
+    if (!use_packed_a(c, K)) {
+        CAPDEC_TRY(c->xl.ensure((size_t)M * K * 4));
+        float *x = c->xl.as<float>();
+        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, h, ldh, lnw, lnb, eps, x, K, M, K)); }
+        if (c->gemm_mode == GEMM_F32) {
+            ProfScope ps(c, F_LMHEAD, flops);
+            return launch_gemm_f32_topk(c->stream, x, K, W, K, M, N, K, k, inv_temp, o, &c->tune);
+        }
+        const void *pl = nullptr;
+        CAPDEC_TRY(planes_of(c, W, N, K, true, &pl));
+        ProfScope ps(c, F_LMHEAD_X3, flops);
+        return launch_gemm_bf16x3_topk(c->stream, x, K, pl, M, N, K, k, inv_temp, o);
+    }
+    CAPDEC_TRY(c->xpk.ensure(x3_packed_bytes_host(M, K)));
+    { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm_packed(c->stream, h, ldh, lnw, lnb, eps, c->xpk.p, M, K, pack_fmt(c))); }
+    const void *pl = nullptr;
+    bool wide_ok = false;
+    CAPDEC_TRY(planes_of(c, W, N, K, true, &pl, -1, &wide_ok));
+    if (c->gemm_mode == GEMM_F16X2) {
+        ProfScope ps(c, F_LMHEAD_H2, flops);
+        // 256 x 128 tiles with one accumulator set once the grid is many rounds deep (each W panel is then fetched by half
+        // as many row tiles); small row counts keep the 128-row tile (more blocks, the same partial lists)
+        const int h2w = c->tune.h2w;
+        if (wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2)) {   // (CAPDEC_H2W >= 2: forced, tests)
+            *k3 = k3_ok;
+            return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o, &c->tune);
+        }
+        return launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o);
+    }
+    if (mode_single(c)) {
+        ProfScope ps(c, F_LMHEAD_BF16, flops);
+        *k3 = k3_ok && M >= 2048 && !c->batch_invariant;      // (as for the wide two-plane tile above)
+        return launch_gemm_x1_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o, pack_fmt(c));
+    }
+    ProfScope ps(c, F_LMHEAD_X3, flops);
+    return launch_gemm_bf16x3p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o);
+}
+
+int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_dev, int N, int K, float inv_temp,
+                  const TopkOut &o) {
+    const void *pl = nullptr;
+    CAPDEC_TRY(planes_of(c, W, N, K, true, &pl));
+    if (mode_single(c)) return launch_gemm_x1_topk_dev(c->stream, Apk, pl, m_dev, N, K, inv_temp, o, pack_fmt(c));
+    return launch_gemm_h2w_topk_dev(c->stream, Apk, pl, m_dev, N, K, inv_temp, o);
+}
 
 }  // namespace capdec
 
@@ -223,40 +268,24 @@ int capdec_gemm_f32(capdec_ctx *c, const float *a, int lda, const float *bt, int
     const bool cache = c->tune.hook_cache;   // benchmarking: treat Bt as a resident weight
     const bool packa = c->tune.hook_packa;   // tests / benchmarking: pre-packed A (the LayerNorm -> GEMM path)
     if ((packa || mode_single(c)) && c->gemm_mode != GEMM_F32 && lda == K && ldb == K && K % 64 == 0) {
+        const int fmt = pack_fmt(c);
         const void *pa = nullptr, *pb = nullptr;
         if (cache) {
             CAPDEC_TRY(planes_of(c, a, M, K, true, &pa));
         } else {   // tests: always re-pack A (the plane cache is keyed by address, torch recycles addresses)
             CAPDEC_TRY(c->xpk.ensure(x3_packed_bytes_host(M, K)));
-            CAPDEC_TRY(pack_any(c, a, M, K, pack_fmt(c), c->xpk.p));
+            CAPDEC_TRY(pack_any(c, a, M, K, fmt, c->xpk.p));
             pa = c->xpk.p;
         }
         GemmEpilogue e;
-        e.tune = &c->tune;
-    e.tune = &c->tune;
+        e.bias = bias; e.act = act; e.resid = resid; e.ldr = ldr;
         CAPDEC_TRY(planes_of(c, bt, N, K, cache, &pb, -1, &e.wide_ok));
         // (an uncached B keeps the two-accumulator kernels: measuring max |b| costs a reduction and a stream synchronisation
         //  per call -- paid only when a geometry is FORCED, CAPDEC_H2W >= 2: how the parity tests reach the wide tiles)
-        if (!cache && pack_fmt(c) == PK_F16X2 && c->tune.h2w >= 2) CAPDEC_TRY(weight_wide_ok(c, bt, (size_t)N * K, &e.wide_ok));
-        e.bias = bias; e.act = act; e.resid = resid; e.ldr = ldr;
-        if ((c->gemm_mode == GEMM_F16X2 || c->gemm_mode == GEMM_BF16X3) && !c->batch_invariant) {
-            const size_t wsb = gemm_splitk_ws_bytes(M, N, K, c->tune);
-            if (wsb) {
-                CAPDEC_TRY(c->splitk.ensure(wsb));
-                e.splitk_ws = c->splitk.p;
-                e.splitk_ws_bytes = c->splitk.cap;
-                }
-        }
-        if (c->gemm_mode == GEMM_F16X2) {
-            ProfScope ps(c, F_GEMM_H2P, 2.0 * M * (double)N * K);
-            return launch_gemm_f16x2p(c->stream, pa, pb, cc, ldc, M, N, K, e);
-        }
-        if (mode_single(c)) {
-            ProfScope ps(c, F_GEMM_BF16P, 2.0 * M * (double)N * K);
-            return gemm_single(c, pa, pb, cc, ldc, M, N, K, e);
-        }
-        ProfScope ps(c, F_GEMM_X3P, 2.0 * M * (double)N * K);
-        return launch_gemm_bf16x3p(c->stream, pa, pb, cc, ldc, M, N, K, e);
+        if (!cache && fmt == PK_F16X2 && c->tune.h2w >= 2) CAPDEC_TRY(weight_wide_ok(c, bt, (size_t)N * K, &e.wide_ok));
+        // (the hook leaves the geometry planners on in the batch-invariant mode and never splits the one-plane kernels)
+        CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, /*split=*/!mode_single(c), /*invariant=*/false));
+        return launch_packed(c, fmt, pa, pb, cc, ldc, M, N, K, e, 2.0 * M * (double)N * K);
     }
     return gemm(c, a, lda, bt, ldb, cc, ldc, M, N, K, bias, act, resid, ldr, /*weight=*/cache);
 }

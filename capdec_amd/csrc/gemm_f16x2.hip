@@ -489,25 +489,15 @@ int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked,
 }
 
 int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                            float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx) {
+                            float inv_temp, const TopkOut &o) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_f16x2p_topk: K must be a multiple of 64");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid(tiles_m * tiles_n), block(256);
-#define LAUNCH_TOPKH(KS)                                                                                          \
-    hipLaunchKernelGGL(gemm_f16x2p_topk_kernel<KS>, grid, block, 0, st, (const _Float16 *)Apacked,                 \
-                       (const _Float16 *)Bpacked, M, N, K, inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n)
-    switch (k) {
-        case 1: LAUNCH_TOPKH(1); break;
-        case 2: LAUNCH_TOPKH(2); break;
-        case 3: LAUNCH_TOPKH(3); break;
-        case 4: LAUNCH_TOPKH(4); break;
-        case 5: LAUNCH_TOPKH(5); break;
-        case 6: LAUNCH_TOPKH(6); break;
-        case 7: LAUNCH_TOPKH(7); break;
-        case 8: LAUNCH_TOPKH(8); break;
-        default: CAPDEC_CHECK(false, "gemm_topk: k must be in 1..8");
-    }
-#undef LAUNCH_TOPKH
+    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
+        hipLaunchKernelGGL(gemm_f16x2p_topk_kernel<KS>, grid, block, 0, st, (const _Float16 *)Apacked,
+                           (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
+                           tiles_m, tiles_n);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -577,16 +567,16 @@ __global__ __launch_bounds__(256, 2) void gemm_x1_topk_dev_kernel(const _Float16
 }
 
 int launch_gemm_x1_topk_dev(hipStream_t st, const void *Apacked, const void *Bpacked, const int *m_dev, int N, int K,
-                            float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx, int fmt) {
+                            float inv_temp, const TopkOut &o, int fmt) {
     CAPDEC_CHECK(m_dev && N > 0 && K > 0 && K % 64 == 0, "gemm_x1_topk_dev: bad argument");
     CAPDEC_CHECK(fmt == PK_F16X1 || fmt == PK_BF16X1, "gemm_x1_topk_dev: one-plane operand formats only");
     const int tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     if (fmt == PK_F16X1)
         hipLaunchKernelGGL((gemm_x1_topk_dev_kernel<1>), dim3(512), dim3(256), 0, st, (const _Float16 *)Apacked,
-                           (const _Float16 *)Bpacked, m_dev, N, K, inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_n);
+                           (const _Float16 *)Bpacked, m_dev, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_n);
     else
         hipLaunchKernelGGL((gemm_x1_topk_dev_kernel<2>), dim3(512), dim3(256), 0, st, (const _Float16 *)Apacked,
-                           (const _Float16 *)Bpacked, m_dev, N, K, inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_n);
+                           (const _Float16 *)Bpacked, m_dev, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_n);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -666,30 +656,21 @@ int launch_gemm_x1(hipStream_t st, const void *Apacked, const void *Bpacked, flo
 }
 
 int launch_gemm_x1_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                        float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx, int fmt) {
+                        float inv_temp, const TopkOut &o, int fmt) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_x1_topk: K must be a multiple of 64");
     CAPDEC_CHECK(fmt == PK_F16X1 || fmt == PK_BF16X1, "gemm_x1_topk: one-plane operand formats only");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid(tiles_m * tiles_n), block(256);
-#define LAUNCH_TOPKX(KS)                                                                                              \
-    if (fmt == PK_F16X1)                                                                                              \
-        hipLaunchKernelGGL((gemm_x1_topk_kernel<KS, 1>), grid, block, 0, st, (const _Float16 *)Apacked,                \
-                           (const _Float16 *)Bpacked, M, N, K, inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n); \
-    else                                                                                                              \
-        hipLaunchKernelGGL((gemm_x1_topk_kernel<KS, 2>), grid, block, 0, st, (const _Float16 *)Apacked,                \
-                           (const _Float16 *)Bpacked, M, N, K, inv_temp, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n)
-    switch (k) {
-        case 1: LAUNCH_TOPKX(1); break;
-        case 2: LAUNCH_TOPKX(2); break;
-        case 3: LAUNCH_TOPKX(3); break;
-        case 4: LAUNCH_TOPKX(4); break;
-        case 5: LAUNCH_TOPKX(5); break;
-        case 6: LAUNCH_TOPKX(6); break;
-        case 7: LAUNCH_TOPKX(7); break;
-        case 8: LAUNCH_TOPKX(8); break;
-        default: CAPDEC_CHECK(false, "gemm_topk: k must be in 1..8");
-    }
-#undef LAUNCH_TOPKX
+    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
+        if (fmt == PK_F16X1)
+            hipLaunchKernelGGL((gemm_x1_topk_kernel<KS, 1>), grid, block, 0, st, (const _Float16 *)Apacked,
+                               (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
+                               tiles_m, tiles_n);
+        else
+            hipLaunchKernelGGL((gemm_x1_topk_kernel<KS, 2>), grid, block, 0, st, (const _Float16 *)Apacked,
+                               (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
+                               tiles_m, tiles_n);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

@@ -188,33 +188,21 @@ int launch_gemm_f32(hipStream_t st, const float *A, int lda, const float *Bt, in
 }
 
 int launch_gemm_f32_topk(hipStream_t st, const float *A, int lda, const float *Bt, int ldb, int M, int N, int K,
-                         int k, float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx,
-                         const Tuning *tune) {
+                         int k, float inv_temp, const TopkOut &o, const Tuning *tune) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0, "gemm_topk: empty problem");
     CAPDEC_CHECK(K % GEMM_BK == 0, "gemm_topk: K must be a multiple of 32");
     CAPDEC_CHECK(lda % 4 == 0 && ldb % 4 == 0, "gemm_topk: lda/ldb must be multiples of 4");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid(tiles_m * tiles_n), block(256);
     const int bk = (tune ? *tune : default_tuning()).f32_lmhead_bk;
-#define LAUNCH_TOPK(KS)                                                                                          \
-    if (bk == 16)                                                                                                \
-        hipLaunchKernelGGL((gemm_f32_topk_kernel<KS, 16, 3>), grid, block, 0, st, A, lda, Bt, ldb, M, N, K, inv_temp, \
-                           tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n);                            \
-    else                                                                                                         \
-        hipLaunchKernelGGL((gemm_f32_topk_kernel<KS, 32, 2>), grid, block, 0, st, A, lda, Bt, ldb, M, N, K, inv_temp, \
-                           tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n)
-    switch (k) {
-        case 1: LAUNCH_TOPK(1); break;
-        case 2: LAUNCH_TOPK(2); break;
-        case 3: LAUNCH_TOPK(3); break;
-        case 4: LAUNCH_TOPK(4); break;
-        case 5: LAUNCH_TOPK(5); break;
-        case 6: LAUNCH_TOPK(6); break;
-        case 7: LAUNCH_TOPK(7); break;
-        case 8: LAUNCH_TOPK(8); break;
-        default: CAPDEC_CHECK(false, "gemm_topk: k must be in 1..8");
-    }
-#undef LAUNCH_TOPK
+    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
+        if (bk == 16)
+            hipLaunchKernelGGL((gemm_f32_topk_kernel<KS, 16, 3>), grid, block, 0, st, A, lda, Bt, ldb, M, N, K, inv_temp,
+                               o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_m, tiles_n);
+        else
+            hipLaunchKernelGGL((gemm_f32_topk_kernel<KS, 32, 2>), grid, block, 0, st, A, lda, Bt, ldb, M, N, K, inv_temp,
+                               o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, tiles_m, tiles_n);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

@@ -374,8 +374,7 @@ int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *
 
 // fused lm_head on the 256 x 128 tile: same partial lists per (row, 128-column tile) as launch_gemm_f16x2p_topk
 int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                         float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx,
-                         const Tuning *tune) {
+                         float inv_temp, const TopkOut &o, const Tuning *tune) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_h2w_topk: K must be a multiple of 64");
     using G = W256x128;
     const int tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
@@ -387,34 +386,24 @@ int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacke
 #else
     (void)tune;
 #endif
-#define LAUNCH_TOPKW(KS)                                                                                           \
-    hipLaunchKernelGGL((gemm_h2w_topk_kernel<G, KS>), grid, block, 0, st, (const _Float16 *)Apacked,                \
-                       (const _Float16 *)Bpacked, M, N, K, scale, tile_max, tile_sum, cand_val, cand_idx, tiles_m, tiles_n)
-    switch (k) {
-        case 1: LAUNCH_TOPKW(1); break;
-        case 2: LAUNCH_TOPKW(2); break;
-        case 3: LAUNCH_TOPKW(3); break;
-        case 4: LAUNCH_TOPKW(4); break;
-        case 5: LAUNCH_TOPKW(5); break;
-        case 6: LAUNCH_TOPKW(6); break;
-        case 7: LAUNCH_TOPKW(7); break;
-        case 8: LAUNCH_TOPKW(8); break;
-        default: CAPDEC_CHECK(false, "gemm_topk: k must be in 1..8");
-    }
-#undef LAUNCH_TOPKW
+    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
+        hipLaunchKernelGGL((gemm_h2w_topk_kernel<G, KS>), grid, block, 0, st, (const _Float16 *)Apacked,
+                           (const _Float16 *)Bpacked, M, N, K, scale, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
+                           tiles_m, tiles_n);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
 
 // k = 5 on *m_dev rows (m_cap = the capacity the output lists were sized for)
 int launch_gemm_h2w_topk_dev(hipStream_t st, const void *Apacked, const void *Bpacked, const int *m_dev, int N, int K,
-                             float inv_temp, float *tile_max, float *tile_sum, float *cand_val, int *cand_idx) {
+                             float inv_temp, const TopkOut &o) {
     CAPDEC_CHECK(m_dev && N > 0 && K > 0 && K % 64 == 0, "gemm_h2w_topk_dev: bad argument");
     using G = W256x128;
     const int tiles_n = (N + G::BN - 1) / G::BN;
     hipLaunchKernelGGL((gemm_h2w_topk_dev_kernel<G, 5>), dim3(512), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
-                       (const _Float16 *)Bpacked, m_dev, N, K, inv_temp / H2_LO_SCALE, tile_max, tile_sum, cand_val, cand_idx,
-                       tiles_n);
+                       (const _Float16 *)Bpacked, m_dev, N, K, inv_temp / H2_LO_SCALE, o.tile_max, o.tile_sum, o.cand_val,
+                       o.cand_idx, tiles_n);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

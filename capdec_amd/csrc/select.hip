@@ -209,21 +209,10 @@ int launch_topk_merge(hipStream_t st, const float *tile_max, const float *tile_s
                       const int *cand_idx, int rows, int ntiles, int k, float *lse, float *top_val, int *top_idx) {
     if (rows <= 0) return 0;
     dim3 grid((rows + 3) / 4), block(256);
-#define LAUNCH_MERGE(KS)                                                                                       \
-    hipLaunchKernelGGL(topk_merge_kernel<KS>, grid, block, 0, st, tile_max, tile_sum, cand_val, cand_idx, rows, \
-                       ntiles, lse, top_val, top_idx)
-    switch (k) {
-        case 1: LAUNCH_MERGE(1); break;
-        case 2: LAUNCH_MERGE(2); break;
-        case 3: LAUNCH_MERGE(3); break;
-        case 4: LAUNCH_MERGE(4); break;
-        case 5: LAUNCH_MERGE(5); break;
-        case 6: LAUNCH_MERGE(6); break;
-        case 7: LAUNCH_MERGE(7); break;
-        case 8: LAUNCH_MERGE(8); break;
-        default: CAPDEC_CHECK(false, "topk_merge: k must be in 1..8");
-    }
-#undef LAUNCH_MERGE
+    CAPDEC_TRY(with_topk_k(k, "topk_merge", [&](auto KS) {
+        hipLaunchKernelGGL(topk_merge_kernel<KS>, grid, block, 0, st, tile_max, tile_sum, cand_val, cand_idx, rows, ntiles,
+                           lse, top_val, top_idx);
+    }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

@@ -529,10 +529,7 @@ int gemm_fp32(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, 
                      bool static_weight) {
     if (c->tune.train_f16x2 && K % 64 == 0 && ldb == K && lda % 4 == 0)
         return gemm(c, A, lda, Bt, ldb, C, ldc, M, N, K, nullptr, CAPDEC_ACT_NONE, nullptr, 0, static_weight);
-    GemmEpilogue e;
-    e.tune = &c->tune;
-    ProfScope ps(c, F_GEMM, 2.0 * M * (double)N * K);
-    return launch_gemm_f32(c->stream, A, lda, Bt, ldb, C, ldc, M, N, K, e);
+    return gemm_native(c, A, lda, Bt, ldb, C, ldc, M, N, K);
 }
 
 int ln_bwd(capdec_ctx *c, const float *x, const float *w, const float *dy, const float *add, float *dx, int rows,
