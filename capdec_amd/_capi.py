@@ -44,6 +44,14 @@ class TMapperWeights(C.Structure):
                 ("layers", C.POINTER(TMapperLayer))]
 
 
+class EDMapperWeights(C.Structure):
+    _fields_ = [("prefix_dim", C.c_int), ("prefix_length", C.c_int), ("clip_length", C.c_int),
+                ("num_layers", C.c_int), ("num_heads", C.c_int), ("d", C.c_int), ("enc_dim", C.c_int),
+                ("enc_mlp_hidden", C.c_int), ("dec_mlp_hidden", C.c_int),
+                ("linear_w", c_float_p), ("linear_b", c_float_p), ("prefix_const", c_float_p),
+                ("enc_layers", C.POINTER(TMapperLayer)), ("dec_layers", C.POINTER(TMapperLayer))]
+
+
 class ClipBlock(C.Structure):
     _fields_ = [(n, c_float_p) for n in (
         "ln_1_w", "ln_1_b", "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "ln_2_w", "ln_2_b",
@@ -79,7 +87,7 @@ class ClipResNetWeights(C.Structure):
 
 #: every symbol include/capdec.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
-ABI_VERSION = 5          # include/capdec.h: CAPDEC_ABI_VERSION
+ABI_VERSION = 6          # include/capdec.h: CAPDEC_ABI_VERSION
 SIGNATURES = {
     "capdec_abi_version": (C.c_int, []),
     "capdec_build_id": (C.c_char_p, []),
@@ -112,6 +120,7 @@ SIGNATURES = {
     "capdec_load_gpt2": (C.c_int, [_VP, C.POINTER(Gpt2Weights)]),
     "capdec_load_mapper_mlp": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "capdec_load_mapper_transformer": (C.c_int, [_VP, C.POINTER(TMapperWeights)]),
+    "capdec_load_mapper_encdec": (C.c_int, [_VP, C.POINTER(EDMapperWeights)]),
     "capdec_load_clip_text": (C.c_int, [_VP, C.POINTER(ClipTextWeights)]),
     "capdec_load_clip_vision": (C.c_int, [_VP, C.POINTER(ClipVisionWeights)]),
     "capdec_load_clip_resnet": (C.c_int, [_VP, C.POINTER(ClipResNetWeights)]),

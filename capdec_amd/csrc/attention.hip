@@ -877,6 +877,137 @@ int launch_attn_mapper(hipStream_t st, const float *q, int ldq, const float *k, 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Attention with separate query and key / value rows (the encoder-decoder mapper, reference transformer_mapper.py:22-51
+// called as attn(norm1(x), y)): q [n, nq, ldq] (caption stride q_cap, 0 = every caption shares one q), k / v
+// [n, nkv, ldkv] from pointers of their own, out [n, nq, heads * hd]; bidirectional, fp32 throughout.  A (caption, head)
+// UNIT keeps K and V in LDS in attn_mapper_kernel's layout ([nkv][hd + 1]) and its query rows beside them, so a block
+// waits for global memory once.  The sizes are small (10 x 10 at the headline shape) and the launch is bound by that
+// wait, not by arithmetic: a block of 256 threads serves `group` = 1, 2 or 4 consecutive units with 4 / group wavefronts
+// each, chosen by the launcher so that enough blocks share a CU ("Encoder-decoder mapper").  A wavefront
+// serves query rows: for q.k the 64 lanes are (key, part) pairs -- TJ = the power of two >= min(nkv, 64) keys times
+// 64 / TJ slices of the head dimension, summed by xor-shuffles -- so 10 keys occupy 40 lanes, not 10; for p.v lanes run
+// over channels.
+__global__ __launch_bounds__(256) void attn_cross_kernel(const float *__restrict__ q, int ldq, size_t q_cap,
+                                                         const float *__restrict__ k, const float *__restrict__ v,
+                                                         int ldkv, float *__restrict__ out, int total, int nq, int nkv,
+                                                         int heads, int hd, float scale, int group, int tj, int vec) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int ld = hd + 1;
+    const int tpu = 256 / group, wpu = tpu >> 6;           // threads / wavefronts per unit
+    const int ul = threadIdx.x / tpu, tu = threadIdx.x - ul * tpu;
+    const int unit = blockIdx.x * group + ul;
+    const bool live = unit < total;
+    float *Ks = sm + (size_t)ul * (2 * nkv * ld + nq * hd + wpu * nkv);   // [nkv][ld]
+    float *Vs = Ks + nkv * ld;                                            // [nkv][ld]
+    float *Qs = Vs + nkv * ld;                                            // [nq][hd]
+    const int cap = unit / heads, head = unit - cap * heads;
+    const int lane = tu & 63, wave = tu >> 6;
+    float *pw = Qs + nq * hd + wave * nkv;                                // [nkv]  this wavefront's scores
+    if (live) {
+        const float *kb = k + (size_t)cap * nkv * ldkv + head * hd, *vb = v + (size_t)cap * nkv * ldkv + head * hd;
+        const float *qb = q + (size_t)cap * q_cap + head * hd;
+        if (vec) {      // 16-byte loads: hd, ldq, ldkv multiples of 4 and the bases aligned (the launcher checked)
+            const int hv = hd >> 2;
+            for (int i = tu; i < nkv * hv; i += tpu) {
+                const int j = i / hv, c = (i - j * hv) << 2;
+                const float4 a = *reinterpret_cast<const float4 *>(kb + (size_t)j * ldkv + c);
+                const float4 b = *reinterpret_cast<const float4 *>(vb + (size_t)j * ldkv + c);
+                float *kd = Ks + j * ld + c, *vd = Vs + j * ld + c;
+                kd[0] = a.x; kd[1] = a.y; kd[2] = a.z; kd[3] = a.w;
+                vd[0] = b.x; vd[1] = b.y; vd[2] = b.z; vd[3] = b.w;
+            }
+            for (int i = tu; i < nq * hv; i += tpu) {
+                const int r = i / hv, c = (i - r * hv) << 2;
+                const float4 a = *reinterpret_cast<const float4 *>(qb + (size_t)r * ldq + c);
+                float *qd = Qs + r * hd + c;        // (scalar stores: a unit's rows need not start on 16 bytes of LDS)
+                qd[0] = a.x; qd[1] = a.y; qd[2] = a.z; qd[3] = a.w;
+            }
+        } else {
+            for (int i = tu; i < nkv * hd; i += tpu) {
+                const int j = i / hd, c = i - j * hd;
+                Ks[j * ld + c] = kb[(size_t)j * ldkv + c];
+                Vs[j * ld + c] = vb[(size_t)j * ldkv + c];
+            }
+            for (int i = tu; i < nq * hd; i += tpu) {
+                const int r = i / hd, c = i - r * hd;
+                Qs[r * hd + c] = qb[(size_t)r * ldq + c];
+            }
+        }
+    }
+    __syncthreads();        // the only block-wide barrier: every thread reaches it, units past the end leave after it
+    if (!live) return;
+    const int d = heads * hd;
+    const int parts = 64 / tj, jl = lane & (tj - 1), part = lane / tj;
+    const int hc = (hd + parts - 1) / parts, c0 = part * hc, c1 = min(hd, c0 + hc);
+    for (int i = wave; i < nq; i += wpu) {
+        const float *qw = Qs + i * hd;
+        float mx = -INFINITY;
+        for (int j0 = 0; j0 < nkv; j0 += tj) {
+            const int j = j0 + jl;
+            float s = 0.f;
+            if (j < nkv)
+                for (int c = c0; c < c1; ++c) s += qw[c] * Ks[j * ld + c];
+            for (int o = tj; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+            s *= scale;
+            if (j < nkv) {
+                if (part == 0) pw[j] = s;
+                mx = fmaxf(mx, s);
+            }
+        }
+        mx = wave_max(mx);
+        __builtin_amdgcn_wave_barrier();
+        float sum = 0.f;
+        for (int j = lane; j < nkv; j += 64) {
+            const float e = expf(pw[j] - mx);
+            pw[j] = e;
+            sum += e;
+        }
+        sum = wave_sum(sum);
+        __builtin_amdgcn_wave_barrier();
+        const float inv = 1.0f / sum;
+        float *orow = out + ((size_t)cap * nq + i) * d + head * hd;
+        for (int c = lane; c < hd; c += 64) {
+            float a = 0.f;
+            for (int j = 0; j < nkv; ++j) a += pw[j] * Vs[j * ld + c];
+            orow[c] = a * inv;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// LDS of one block: K, V and the query rows of `group` units, a score row for each of the block's four wavefronts
+size_t attn_cross_lds_bytes(int nq, int nkv, int hd, int group) {
+    return ((size_t)group * (2 * (size_t)nkv * (hd + 1) + (size_t)nq * hd) + 4 * (size_t)nkv) * sizeof(float);
+}
+
+int launch_attn_cross(hipStream_t st, const float *q, int ldq, size_t q_cap_stride, const float *k, const float *v,
+                      int ldkv, float *out, int n, int nq, int nkv, int heads, int hd, int group) {
+    CAPDEC_CHECK(nq >= 1 && nkv >= 1 && heads >= 1 && hd >= 1 && ldq >= heads * hd && ldkv >= heads * hd,
+                 "cross attention: bad geometry");
+    CAPDEC_CHECK(group == 0 || group == 1 || group == 2 || group == 4, "cross attention: group must be 0 (auto), 1, 2 or 4");
+    CAPDEC_CHECK(attn_cross_lds_bytes(nq, nkv, hd, 1) <= 160 * 1024, "cross attention: too many rows for LDS");
+    if (n <= 0) return 0;
+    // units per block: measured in DESIGN.md (ATTN_CROSS_GROUP_LDS: two units while six such blocks fit a CU's 160 KB)
+    if (group == 0) group = attn_cross_lds_bytes(nq, nkv, hd, 2) <= ATTN_CROSS_GROUP_LDS ? 2 : 1;
+    const size_t lds = attn_cross_lds_bytes(nq, nkv, hd, group);
+    CAPDEC_CHECK(lds <= 160 * 1024, "cross attention: too many rows for LDS");
+    if (lds > 64 * 1024)
+        CAPDEC_HIP(hipFuncSetAttribute((const void *)attn_cross_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds));
+    int tj = 1;
+    while (tj < nkv && tj < 64) tj <<= 1;
+    const int vec = hd % 4 == 0 && ldkv % 4 == 0 && ldq % 4 == 0 && q_cap_stride % 4 == 0 &&
+                    ((uintptr_t)k | (uintptr_t)v | (uintptr_t)q) % 16 == 0;
+    const long long total = (long long)n * heads;
+    CAPDEC_CHECK(total <= 0x7fffffff, "cross attention: too many (caption, head) units");
+    hipLaunchKernelGGL(attn_cross_kernel, dim3((unsigned)((total + group - 1) / group)), dim3(256), lds, st, q, ldq,
+                       q_cap_stride, k, v, ldkv, out, (int)total, nq, nkv, heads, hd, (float)pow((double)hd, -0.5), group,
+                       tj, vec);
+    CAPDEC_HIP(hipGetLastError());
+    return 0;
+}
+
 CAPDEC_SAT_ACCESSOR(sat_count_attention)
 
 }  // namespace capdec

@@ -310,6 +310,13 @@ int launch_attn_decode(hipStream_t st, const float *qkv, const KvCache &c, int l
 // TransformerMapper self-attention (no mask): q / k / v rows of n*seq tokens (row strides ldq, ldkv), head-major
 int launch_attn_mapper(hipStream_t st, const float *q, int ldq, const float *k, const float *v, int ldkv, float *out,
                        int n, int seq, int heads, int hd);
+// Encoder-decoder mapper: nq query rows per caption attend to nkv key / value rows from pointers of their own (row
+// strides ldq / ldkv; q_cap_stride = elements between two captions' query blocks, 0 = one block shared by all), out
+// [n, nq, heads * hd].  group = (caption, head) units per block: 1, 2, 4, or 0 = chosen from the LDS need.
+constexpr size_t ATTN_CROSS_GROUP_LDS = 26 * 1024;
+size_t attn_cross_lds_bytes(int nq, int nkv, int hd, int group);
+int launch_attn_cross(hipStream_t st, const float *q, int ldq, size_t q_cap_stride, const float *k, const float *v,
+                      int ldkv, float *out, int n, int nq, int nkv, int heads, int hd, int group = 0);
 
 // select.hip
 int launch_topk_merge(hipStream_t st, const float *tile_max, const float *tile_sum, const float *cand_val,

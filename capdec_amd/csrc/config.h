@@ -61,6 +61,7 @@ struct Tuning {
     int att_na = 0;               // CAPDEC_ATT_NA=2 | 4
     int pp_abl = 0;               // CAPDEC_PP_ABL 1..8 (gemm_pp.hip)
     std::string pp_stamps;        // CAPDEC_PP_STAMPS=<file>: per-block phase stamps of the ping-pong GEMM
+    int ed_attn_group = 0;        // CAPDEC_ED_ATTN_GROUP=1 | 2 | 4: (caption, head) units per block of the encoder-decoder mapper's attention
     int lmhead_k1 = 0;            // CAPDEC_LMHEAD_K1=1: the k = 1 lm_head epilogue whatever k is (WRONG results)
 };
 

@@ -58,9 +58,12 @@ struct Gpt2 {
 };
 struct TMapLayer {
     float *n1w, *n1b, *wqkv, *wproj, *bproj, *n2w, *n2b, *wfc1, *bfc1, *wfc2, *bfc2;
+    // encoder-decoder mapper, decoder layers only: wqkv holds to_queries [d, d] alone; the keys / values of a self layer
+    // come from another input than its queries (wkv [2d, d]); a cross layer's rows sit in Mapper::wkv_cross (wkv = nullptr)
+    float *wkv = nullptr;
 };
 struct Mapper {
-    int kind = 0;   // 0 none, 1 mlp, 2 transformer
+    int kind = 0;   // 0 none, 1 mlp, 2 transformer, 3 transformer encoder-decoder (inference only)
     int D = 0, P = 0, d = 768;
     // mlp
     int hidden = 0;
@@ -69,6 +72,11 @@ struct Mapper {
     int clip_len = 0, n_layers = 0, heads = 8, mlp_hidden = 0;
     float *lin_w = nullptr, *lin_b = nullptr, *prefix_const = nullptr;
     std::vector<TMapLayer> layers;
+    // encoder-decoder: `layers` is the ref_encoder (n_layers at width enc_dim, hidden enc_hidden), `dec` the prefix_decoder
+    // (2 * n_layers at width d, hidden mlp_hidden; even = cross, odd = self); lin_w is [clip_len * enc_dim, D]
+    int enc_dim = 0, enc_hidden = 0;
+    std::vector<TMapLayer> dec;
+    float *wkv_cross = nullptr;     // [n_layers * 2d, enc_dim]: the cross layers' to_keys_values stacked (one GEMM serves all)
     std::vector<void *> owned;
 };
 
@@ -167,6 +175,7 @@ struct capdec_ctx {
     DBuf lmflag, xpk2;     // fused lm_head with 3 candidates per tile: [count, total, rows...] of the rows whose top 5 need
                            // the exact second pass; their compacted packed A operand (decode.hip: lm_head_select)
     DBuf m_hid, m_lin, m_seq, m_x, m_qkv, m_att, m_ff;
+    DBuf m_kvc;            // encoder-decoder mapper: keys / values of the cross layers, [n * clip_len, n_layers * 2d]
     DBuf t_idx, t_patch, t_pout, p_desc, p_inter, splitk, absmax;
     int *alive_host = nullptr;   // pinned: [captions still generating, second-pass rows so far]
     // caption-shard communicator (RCCL), see capdec_comm_init

@@ -193,6 +193,7 @@ extern "C" {
 
 int capdec_train_get(capdec_ctx *c, int kind, int which, float *d_out, size_t n) {
     CAPDEC_CHECK(c && d_out, "train_get: null argument");
+    CAPDEC_CHECK(c->map.kind != 3, "train_get: the encoder-decoder mapper is inference-only");
     CAPDEC_CHECK(c->gpt.loaded && (c->map.kind == 1 || c->map.kind == 2), "train_get: needs GPT-2 weights and a mapper");
     CAPDEC_CHECK(kind == 0 || kind == 1, "train_get: kind must be 0 (parameter) or 1 (gradient)");
     CAPDEC_HIP(hipSetDevice(c->device));

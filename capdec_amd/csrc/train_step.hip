@@ -208,6 +208,7 @@ static int train_step(capdec_ctx *c, const float *prefix, const int *tokens, int
                       float eps, float weight_decay, int apply_update, float *loss_host) {
     const Gpt2 &g = c->gpt;
     Mapper &m = c->map;
+    CAPDEC_CHECK(m.kind != 3, "train_step: the encoder-decoder mapper is inference-only");
     CAPDEC_CHECK(g.loaded && (m.kind == 1 || m.kind == 2), "train_step: needs GPT-2 weights and a mapper");
     CAPDEC_CHECK(g.d == 768 && g.d / g.n_head == 64 && m.d == g.d, "train_step: d = 768, head_dim = 64");
     const int d = g.d, P = m.P, S = P + L, R = B * S, Rl = B * L, O = P * d, D = m.D;

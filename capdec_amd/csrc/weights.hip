@@ -205,6 +205,89 @@ int capdec_load_mapper_transformer(capdec_ctx *c, const capdec_tmapper_weights *
     return 0;
 }
 
+// one layer of the encoder-decoder mapper at width `w` (hidden `hid`): fused = [to_queries ; to_keys_values] as one
+// [3w, w] projection (encoder: both read norm1(x)); otherwise to_queries alone, and to_keys_values [2w, ref] goes to
+// *kv_dst (the stacked cross matrix) or, with kv_dst == nullptr, to a matrix of the layer's own
+static int upload_ed_layer(Mapper &m, const capdec_tmapper_layer &s, TMapLayer &t, int w, int hid, int ref, bool fused,
+                           float *kv_dst) {
+    CAPDEC_CHECK(s.norm1_w && s.norm1_b && s.to_queries_w && s.to_keys_values_w && s.project_w && s.project_b &&
+                 s.norm2_w && s.norm2_b && s.fc1_w && s.fc1_b && s.fc2_w && s.fc2_b, "load_mapper_encdec: null layer weight");
+    CAPDEC_TRY(upload(m.owned, s.norm1_w, w, &t.n1w));
+    CAPDEC_TRY(upload(m.owned, s.norm1_b, w, &t.n1b));
+    if (fused) {
+        void *p = nullptr;
+        CAPDEC_HIP(hipMalloc(&p, (size_t)3 * w * w * 4));
+        m.owned.push_back(p);
+        t.wqkv = (float *)p;
+        CAPDEC_HIP(hipMemcpy(t.wqkv, s.to_queries_w, (size_t)w * w * 4, hipMemcpyHostToDevice));
+        CAPDEC_HIP(hipMemcpy(t.wqkv + (size_t)w * w, s.to_keys_values_w, (size_t)2 * w * w * 4, hipMemcpyHostToDevice));
+    } else {
+        CAPDEC_TRY(upload(m.owned, s.to_queries_w, (size_t)w * w, &t.wqkv));
+        if (kv_dst) CAPDEC_HIP(hipMemcpy(kv_dst, s.to_keys_values_w, (size_t)2 * w * ref * 4, hipMemcpyHostToDevice));
+        else CAPDEC_TRY(upload(m.owned, s.to_keys_values_w, (size_t)2 * w * ref, &t.wkv));
+    }
+    CAPDEC_TRY(upload(m.owned, s.project_w, (size_t)w * w, &t.wproj));
+    CAPDEC_TRY(upload(m.owned, s.project_b, w, &t.bproj));
+    CAPDEC_TRY(upload(m.owned, s.norm2_w, w, &t.n2w));
+    CAPDEC_TRY(upload(m.owned, s.norm2_b, w, &t.n2b));
+    CAPDEC_TRY(upload(m.owned, s.fc1_w, (size_t)hid * w, &t.wfc1));
+    CAPDEC_TRY(upload(m.owned, s.fc1_b, hid, &t.bfc1));
+    CAPDEC_TRY(upload(m.owned, s.fc2_w, (size_t)w * hid, &t.wfc2));
+    CAPDEC_TRY(upload(m.owned, s.fc2_b, w, &t.bfc2));
+    return 0;
+}
+
+int capdec_load_mapper_encdec(capdec_ctx *c, const capdec_edmapper_weights *w) {
+    CAPDEC_CHECK(c && w, "null argument");
+    CAPDEC_CHECK(w->prefix_dim >= 32 && w->prefix_dim % 32 == 0, "load_mapper_encdec: prefix_dim must be a multiple of 32");
+    CAPDEC_CHECK(w->d >= 32 && w->d % 32 == 0, "load_mapper_encdec: d must be a multiple of 32");
+    CAPDEC_CHECK(w->enc_dim >= 32 && w->enc_dim % 32 == 0, "load_mapper_encdec: enc_dim must be a multiple of 32");
+    CAPDEC_CHECK(w->enc_mlp_hidden >= 32 && w->enc_mlp_hidden % 32 == 0, "load_mapper_encdec: enc_mlp_hidden must be a multiple of 32");
+    CAPDEC_CHECK(w->dec_mlp_hidden >= 32 && w->dec_mlp_hidden % 32 == 0, "load_mapper_encdec: dec_mlp_hidden must be a multiple of 32");
+    CAPDEC_CHECK(w->num_heads >= 1 && w->d % w->num_heads == 0 && w->enc_dim % w->num_heads == 0,
+                 "load_mapper_encdec: num_heads must divide d and enc_dim");
+    CAPDEC_CHECK(w->clip_length >= 1, "load_mapper_encdec: clip_length must be at least 1");
+    CAPDEC_CHECK(w->prefix_length >= 1, "load_mapper_encdec: prefix_length must be at least 1");
+    CAPDEC_CHECK(w->num_layers >= 1, "load_mapper_encdec: num_layers must be at least 1");
+    CAPDEC_CHECK(w->linear_w && w->linear_b && w->prefix_const && w->enc_layers && w->dec_layers,
+                 "load_mapper_encdec: null weight (linear_w, linear_b, prefix_const, enc_layers, dec_layers)");
+    // the three attention launches of this geometry must fit the LDS (encoder: C x C rows at enc_dim; cross: P x C and
+    // self: P x P at d): refused here, before anything of the loaded mapper is given up
+    {
+        const int C = w->clip_length, P = w->prefix_length, H = w->num_heads;
+        CAPDEC_CHECK(attn_cross_lds_bytes(C, C, w->enc_dim / H, 1) <= 160 * 1024 && attn_cross_lds_bytes(P, C, w->d / H, 1) <= 160 * 1024,
+                     "load_mapper_encdec: clip_length too large (keys, values and queries of one head must fit 160 KB of LDS)");
+        CAPDEC_CHECK(attn_cross_lds_bytes(P, P, w->d / H, 1) <= 160 * 1024,
+                     "load_mapper_encdec: prefix_length too large (keys, values and queries of one head must fit 160 KB of LDS)");
+    }
+    CAPDEC_HIP(hipSetDevice(c->device));
+    Mapper &m = c->map;
+    free_all(m.owned);
+    drop_planes(c);
+    train_release(c);
+    m = Mapper();
+    m.D = w->prefix_dim; m.P = w->prefix_length; m.clip_len = w->clip_length; m.n_layers = w->num_layers;
+    m.heads = w->num_heads; m.d = w->d; m.mlp_hidden = w->dec_mlp_hidden; m.enc_dim = w->enc_dim; m.enc_hidden = w->enc_mlp_hidden;
+    const int d = m.d, E = m.enc_dim, L = m.n_layers;
+    CAPDEC_TRY(upload(m.owned, w->linear_w, (size_t)m.clip_len * E * m.D, &m.lin_w));
+    CAPDEC_TRY(upload(m.owned, w->linear_b, (size_t)m.clip_len * E, &m.lin_b));
+    CAPDEC_TRY(upload(m.owned, w->prefix_const, (size_t)m.P * d, &m.prefix_const));
+    void *p = nullptr;
+    CAPDEC_HIP(hipMalloc(&p, (size_t)L * 2 * d * E * 4));
+    m.owned.push_back(p);
+    m.wkv_cross = (float *)p;
+    m.layers.resize(L);
+    for (int l = 0; l < L; ++l) CAPDEC_TRY(upload_ed_layer(m, w->enc_layers[l], m.layers[l], E, m.enc_hidden, E, true, nullptr));
+    m.dec.resize(2 * L);
+    for (int l = 0; l < 2 * L; ++l) {
+        const bool cross = l % 2 == 0;
+        CAPDEC_TRY(upload_ed_layer(m, w->dec_layers[l], m.dec[l], d, m.mlp_hidden, cross ? E : d, false,
+                                   cross ? m.wkv_cross + (size_t)(l / 2) * 2 * d * E : nullptr));
+    }
+    m.kind = 3;
+    return 0;
+}
+
 int capdec_load_clip_text(capdec_ctx *c, const capdec_clip_text_weights *w) {
     CAPDEC_CHECK(c && w, "null argument");
     CAPDEC_CHECK(w->width % 32 == 0 && w->heads >= 1 && w->width / w->heads == 64 && w->width % w->heads == 0,

@@ -149,6 +149,54 @@ class Engine:
         self._chk(self.lib.capdec_load_mapper_transformer(self._h, C.byref(w)), "capdec_load_mapper_transformer")
         self.mapper = dict(kind="transformer", D=lw.shape[1], P=P, d=d, clip_length=clip_len, num_layers=n_layers)
 
+    def load_mapper_encdec(self, sd: Dict[str, torch.Tensor], prefix: str = "clip_project.", num_heads: int = 8):
+        """TransformerEncoderDecoder (MappingType.TransformerDecoder): geometry from the tensors -- the encoder's width
+        from ref_encoder's first norm (512 in the reference), its depth L from the keys; the decoder has 2 L layers."""
+        lw, lb = _f32(sd[prefix + "linear.weight"]), _f32(sd[prefix + "linear.bias"])
+        pc = _f32(sd[prefix + "prefix_const"])
+        P, d = pc.shape
+        n_layers = 0
+        while f"{prefix}ref_encoder.layers.{n_layers}.norm1.weight" in sd:
+            n_layers += 1
+        if n_layers == 0 or f"{prefix}prefix_decoder.layers.{2 * n_layers - 1}.norm1.weight" not in sd or \
+                f"{prefix}prefix_decoder.layers.{2 * n_layers}.norm1.weight" in sd:
+            raise CapdecError(f"encoder-decoder mapper: {n_layers} ref_encoder layers need {2 * n_layers} prefix_decoder layers")
+        enc = _f32(sd[f"{prefix}ref_encoder.layers.0.norm1.weight"]).shape[0]
+        clip_len = lw.shape[0] // enc
+        keep = [lw, lb, pc]
+        names = [("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("to_queries_w", "attn.to_queries.weight"),
+                 ("to_keys_values_w", "attn.to_keys_values.weight"), ("project_w", "attn.project.weight"),
+                 ("project_b", "attn.project.bias"), ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"),
+                 ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"),
+                 ("fc2_b", "mlp.fc2.bias")]
+
+        def stack(which: str, count: int, width: int):
+            layers = (_capi.TMapperLayer * count)()
+            hid = _f32(sd[f"{prefix}{which}.layers.0.mlp.fc1.weight"]).shape[0]
+            for i in range(count):
+                ref = width if which == "ref_encoder" or i % 2 == 1 else enc
+                shapes = {"norm1_w": (width,), "norm1_b": (width,), "to_queries_w": (width, width),
+                          "to_keys_values_w": (2 * width, ref), "project_w": (width, width), "project_b": (width,),
+                          "norm2_w": (width,), "norm2_b": (width,), "fc1_w": (hid, width), "fc1_b": (hid,),
+                          "fc2_w": (width, hid), "fc2_b": (width,)}
+                for field, key in names:
+                    a = _f32(sd[f"{prefix}{which}.layers.{i}.{key}"])
+                    if tuple(a.shape) != shapes[field]:
+                        raise CapdecError(f"encoder-decoder mapper: {which}.layers.{i}.{key} is {tuple(a.shape)}, expected {shapes[field]}")
+                    keep.append(a)
+                    setattr(layers[i], field, _fp(a))
+            return layers, hid
+
+        if lw.shape[0] != clip_len * enc or tuple(lb.shape) != (clip_len * enc,):
+            raise CapdecError(f"encoder-decoder mapper: linear.weight rows {lw.shape[0]} are not a multiple of the encoder width {enc}")
+        enc_layers, enc_hid = stack("ref_encoder", n_layers, enc)
+        dec_layers, dec_hid = stack("prefix_decoder", 2 * n_layers, d)
+        w = _capi.EDMapperWeights(lw.shape[1], P, clip_len, n_layers, num_heads, d, enc, enc_hid, dec_hid, _fp(lw), _fp(lb),
+                                  _fp(pc), enc_layers, dec_layers)
+        self._chk(self.lib.capdec_load_mapper_encdec(self._h, C.byref(w)), "capdec_load_mapper_encdec")
+        self.mapper = dict(kind="transformer_decoder", D=lw.shape[1], P=P, d=d, clip_length=clip_len, num_layers=n_layers,
+                           enc_dim=enc)
+
     # ------------------------------------------------------------------ prefix stage
     def normalize_prefix(self, x: torch.Tensor, normalize: bool = True, offset: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = self._dev(x)

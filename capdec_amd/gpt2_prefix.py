@@ -6,6 +6,8 @@ Same names, constructor arguments and attribute surface (``.clip_project``, ``.g
 ``.parameters``), but the arithmetic runs in libcapdec_hip.so on an MI355X.  ``forward`` is the
 forward pass of the reference's train step (:145-155; train.py:251-260) -- logits and loss, inference
 only: backward and the optimiser are outside this path.
+All three mapping types run: ``MappingType.TransformerDecoder`` builds ``transformer_mapper.TransformerEncoderDecoder``
+(:169-171), for inference (``capdec_amd.train.train_step`` refuses it).
 """
 from __future__ import annotations
 
@@ -182,8 +184,10 @@ class ClipCaptionModel(_HipModule):
         elif mapping_type == MappingType.MLP:
             self.clip_project = MLP((prefix_dim, (self.gpt_embedding_size * prefix_length) // 2,
                                      self.gpt_embedding_size * prefix_length), _owner=self)
-        else:
-            raise CapdecError("MappingType.TransformerDecoder (TransformerEncoderDecoder) is outside the hot path")
+        else:       # MappingType.TransformerDecoder (reference gpt2_prefix.py:169-171); inference only
+            self.clip_project = transformer_mapper.TransformerEncoderDecoder(prefix_dim, self.gpt_embedding_size,
+                                                                             prefix_length, clip_length, num_layers,
+                                                                             _owner=self)
 
     def get_dummy_token(self, batch_size: int, device) -> torch.Tensor:
         return torch.zeros(batch_size, self.prefix_length, dtype=torch.int64, device=device)
@@ -204,6 +208,8 @@ class ClipCaptionModel(_HipModule):
 
     def _mapper_shapes(self):
         """ordered {name: shape} of the mapper's trainable tensors, in the device's slot order"""
+        if self.mapping_type == MappingType.TransformerDecoder:
+            raise CapdecError("train_step: the encoder-decoder mapper is inference-only")
         mlp = self.mapping_type == MappingType.MLP
         names = Engine.train_tensor_names("mlp" if mlp else "transformer", self.num_layers)
         sd = self.clip_project._sd

@@ -41,6 +41,10 @@ GPT2_SMALL = GPT2Dims()
 GPT2_TINY = GPT2Dims(n_layer=2, vocab=1531, n_pos=128)
 
 
+#: width of TransformerEncoderDecoder's ref_encoder, hard-coded in the reference (transformer_mapper.py:142-144)
+ENCDEC_ENC_DIM = 512
+
+
 def _randn(gen, *shape, std=1.0, mean=0.0):
     return torch.randn(*shape, generator=gen, dtype=torch.float32) * std + mean
 
@@ -114,6 +118,42 @@ def hot_transformer_mapper_state_dict(seed: int, prefix_dim: int, prefix_length:
     return sd
 
 
+def hot_encdec_mapper_state_dict(seed: int, prefix_dim: int, prefix_length: int, clip_length: int,
+                                 num_layers: int = 4, d: int = 768,
+                                 prefix: str = "clip_project.") -> "OrderedDict[str, torch.Tensor]":
+    """TransformerEncoderDecoder (reference transformer_mapper.py:130-145): linear D -> clip_len*512, ``num_layers``
+    encoder layers at width 512, ``2 * num_layers`` decoder layers at width d (even: cross, to_keys_values [2d, 512];
+    odd: self, [2d, d]), prefix_const [P, d].  The rules of ``hot_transformer_mapper_state_dict`` except the matrices'
+    std, sqrt(0.5 / fan_in): the odd decoder layers take keys from the un-normalised residual stream, so with
+    sqrt(2 / fan_in) the softmax logits grow with depth until fp32 itself is 0.03 (L 4) to 0.7 (L 8) away from float64."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    enc = ENCDEC_ENC_DIM
+
+    def layer(l: str, w: int, ref: int):
+        sd[l + "norm1.weight"] = _randn(g, w, std=0.1, mean=1.0)
+        sd[l + "norm1.bias"] = _randn(g, w, std=0.1)
+        sd[l + "attn.to_queries.weight"] = _randn(g, w, w, std=math.sqrt(0.5 / w))
+        sd[l + "attn.to_keys_values.weight"] = _randn(g, 2 * w, ref, std=math.sqrt(0.5 / ref))
+        sd[l + "attn.project.weight"] = _randn(g, w, w, std=math.sqrt(0.5 / w))
+        sd[l + "attn.project.bias"] = _randn(g, w, std=0.02)
+        sd[l + "norm2.weight"] = _randn(g, w, std=0.1, mean=1.0)
+        sd[l + "norm2.bias"] = _randn(g, w, std=0.1)
+        sd[l + "mlp.fc1.weight"] = _randn(g, 2 * w, w, std=math.sqrt(0.5 / w))
+        sd[l + "mlp.fc1.bias"] = _randn(g, 2 * w, std=0.02)
+        sd[l + "mlp.fc2.weight"] = _randn(g, w, 2 * w, std=math.sqrt(0.5 / (2 * w)))
+        sd[l + "mlp.fc2.bias"] = _randn(g, w, std=0.02)
+
+    for i in range(num_layers):
+        layer(f"{prefix}ref_encoder.layers.{i}.", enc, enc)
+    for i in range(2 * num_layers):
+        layer(f"{prefix}prefix_decoder.layers.{i}.", d, enc if i % 2 == 0 else d)
+    sd[prefix + "linear.weight"] = _randn(g, clip_length * enc, prefix_dim, std=math.sqrt(0.5 / prefix_dim))
+    sd[prefix + "linear.bias"] = _randn(g, clip_length * enc, std=0.02)
+    sd[prefix + "prefix_const"] = _randn(g, prefix_length, d, std=1.0)
+    return sd
+
+
 def hot_state_dict(seed: int = 42, mapping_type: str = "mlp", prefix_dim: int = 512, prefix_length: int = 10,
                    clip_length: int = 10, num_layers: int = 8,
                    dims: GPT2Dims = GPT2_SMALL) -> "OrderedDict[str, torch.Tensor]":
@@ -124,6 +164,8 @@ def hot_state_dict(seed: int = 42, mapping_type: str = "mlp", prefix_dim: int = 
     elif mapping_type in ("transformer", "transformer_encoder"):
         sd = hot_transformer_mapper_state_dict(seed + 1, prefix_dim, prefix_length, clip_length, num_layers,
                                                dims.n_embd)
+    elif mapping_type == "transformer_decoder":
+        sd = hot_encdec_mapper_state_dict(seed + 1, prefix_dim, prefix_length, clip_length, num_layers, dims.n_embd)
     else:
         raise ValueError(f"unsupported mapping_type {mapping_type!r}")
     sd.update(hot_gpt2_state_dict(seed, dims))

@@ -127,6 +127,8 @@ def train_step(model: ClipCaptionModel, optimizer: AdamW, tokens: torch.Tensor, 
     from a Philox stream seeded from torch's global seed -- or from ``dropout_masks`` (uint8, 1 = keep: every site of the
     step concatenated in call order, include/capdec.h), the hook the parity test uses.  ``wait=False`` enqueues the step
     and returns None (``model.engine.train_loss()`` reads losses later)."""
+    if model.mapping_type == MappingType.TransformerDecoder:
+        raise CapdecError("train_step: the encoder-decoder mapper is inference-only")
     full = not isinstance(model, ClipCaptionPrefix)      # a plain ClipCaptionModel trains GPT-2 too (reference train.py:306-308)
     if model._train_gpt != full:
         model._pull_mapper()

@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define CAPDEC_ABI_VERSION 5   /* 5: capdec_set_compact, capdec_decode_step_rows (the workload in which captions stop);
+#define CAPDEC_ABI_VERSION 6   /* 6: capdec_load_mapper_encdec (MappingType.TransformerDecoder, inference only);
+                                  5: capdec_set_compact, capdec_decode_step_rows (the workload in which captions stop);
                                   4: train step -- GPT-2's dropouts (capdec_train_set_dropout / _masks), capdec_train_loss, loss == NULL
                                      enqueues without waiting, the scope survives capdec_train_reset;
                                   3: the diverged-beam debug hook left the shipped library (measurement builds only);
@@ -147,6 +148,23 @@ typedef struct capdec_tmapper_weights {
 
 /* TransformerMapper: reference transformer_mapper.py:113-127 (8 heads, pre-LN, ReLU MLP) */
 int capdec_load_mapper_transformer(capdec_ctx *ctx, const capdec_tmapper_weights *h_w);
+
+typedef struct capdec_edmapper_weights capdec_edmapper_weights;
+struct capdec_edmapper_weights {
+    int prefix_dim, prefix_length, clip_length, num_layers, num_heads, d;
+    int enc_dim;                             /* width of the encoder: 512 in the reference, whatever prefix_dim and d are */
+    int enc_mlp_hidden, dec_mlp_hidden;      /* 2 * enc_dim, 2 * d in the reference */
+    const float *linear_w, *linear_b;        /* [clip_length*enc_dim, D], [clip_length*enc_dim] */
+    const float *prefix_const;               /* [P, d] */
+    const capdec_tmapper_layer *enc_layers;  /* [num_layers]: the layer of capdec_tmapper_weights at d = enc_dim, hid = enc_mlp_hidden */
+    const capdec_tmapper_layer *dec_layers;  /* [2*num_layers] at d, hid = dec_mlp_hidden; to_keys_values_w is [2d, enc_dim] in the
+                                                even layers (cross: keys from the encoder's output) and [2d, d] in the odd
+                                                ones (self: keys from the residual stream, which norm1 does NOT touch) */
+};
+
+/* TransformerEncoderDecoder: reference transformer_mapper.py:130-145 (MappingType.TransformerDecoder).  Inference only:
+ * capdec_mapper_forward and everything built on it serve it; capdec_train_step refuses it. */
+int capdec_load_mapper_encdec(capdec_ctx *ctx, const capdec_edmapper_weights *h_w);
 
 /* ---- prefix stage -------------------------------------------------------------------- */
 /* `prefix / prefix.norm(2,-1)` then `+ offset` (reference predictions_runner.py:221-224);

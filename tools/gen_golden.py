@@ -68,7 +68,8 @@ def build_ref_model(gpt2_prefix, dims, mapping_type, prefix_dim, P, clip_length=
     cfg = GPT2Config(n_layer=dims.n_layer, n_head=dims.n_head, n_embd=dims.n_embd, vocab_size=dims.vocab,
                      n_positions=dims.n_pos)
     GPT2LMHeadModel.from_pretrained = staticmethod(lambda name, *a, **k: GPT2LMHeadModel(cfg))
-    mt = {"mlp": gpt2_prefix.MappingType.MLP, "transformer_encoder": gpt2_prefix.MappingType.TransformerEncoder}[mapping_type]
+    mt = {"mlp": gpt2_prefix.MappingType.MLP, "transformer_encoder": gpt2_prefix.MappingType.TransformerEncoder,
+          "transformer_decoder": gpt2_prefix.MappingType.TransformerDecoder}[mapping_type]
     model = gpt2_prefix.ClipCaptionModel(P, clip_length=clip_length, prefix_dim=prefix_dim, num_layers=num_layers,
                                          mapping_type=mt).eval()
     sd = synth.hot_state_dict(seed, mapping_type, prefix_dim, P, clip_length, num_layers, dims)
@@ -133,6 +134,103 @@ def gen_mappers(refs):
         out["x_p5"], out["tm_p5"] = x.numpy(), m(x).numpy()
     np.savez_compressed(os.path.join(OUT, "mappers.npz"), **out)
     print("mappers.npz", {k: getattr(v, "shape", v) for k, v in out.items()})
+
+
+#: (tag, prefix_dim, prefix_length, clip_length, num_layers, captions, weight seed, input seed, atol of the GPU tests)
+ENCDEC_CASES = (("ed_512", 512, 10, 10, 4, 4, 43, 522, 2e-4), ("ed_640", 640, 10, 10, 4, 4, 43, 650, 2e-4),
+                ("ed_p5", 512, 5, 7, 3, 3, 44, 77, 2e-4), ("ed_p40", 512, 40, 40, 1, 2, 45, 78, 3e-4))
+
+
+def gen_mapper_encdec(refs):
+    """TransformerEncoderDecoder (MappingType.TransformerDecoder): the reference class on the hot weights, in fp32 and
+    in float64 (the distance between the two is the reference's own rounding floor).  Also asserts the conditions the
+    tolerances of tests/test_mapper_encdec.py rest on: (i) that floor is at most a tenth of the case's bound, (ii) the
+    variant whose odd decoder layers take keys / values from norm1(x) -- the mistake a fused [q|k|v] projection would
+    make -- is at least 100 bounds away, (iii) the output's rms lies in 1..10 like the TransformerMapper fixtures."""
+    transformer_mapper = refs[2]
+    for tag, D, P, C, L, n, wseed, xseed, atol in ENCDEC_CASES:
+        out = {}
+        x = synth.synthetic_clip_embeddings(n, D, seed=xseed)
+        sd = synth.hot_encdec_mapper_state_dict(wseed, D, P, C, L)
+        m = transformer_mapper.TransformerEncoderDecoder(D, 768, P, C, L).eval()
+        m.load_state_dict({k[len("clip_project."):]: v for k, v in sd.items()})
+        with torch.no_grad():
+            y = m(x)
+            y64 = m.double()(x.double())
+            # the wrong variant, through the reference's own modules: odd layers called as layer(x) (y = None -> norm1(x))
+            dec = m.prefix_decoder
+            ref = m.ref_encoder(m.linear(x.double()).view(n, C, -1))
+            h = m.prefix_const.unsqueeze(0).expand(n, P, 768)
+            for i, layer in enumerate(dec.layers):
+                h = layer(h, ref) if i % 2 == 0 else layer(h)
+        floor = float((y.double() - y64).abs().max())
+        wrong = float((h - y64).abs().max())
+        rms = float(y64.pow(2).mean().sqrt())
+        print(f"  {tag}: rms {rms:.3f} absmax {float(y64.abs().max()):.2f} fp32-vs-f64 {floor:.2e} wrong variant {wrong:.3f} "
+              f"caption 0 vs 1 {float((y64[0] - y64[1]).abs().max()):.2f}")
+        assert floor <= atol / 10, (tag, floor)
+        assert wrong >= 100 * atol, (tag, wrong)
+        assert 1.0 <= rms <= 10.0, (tag, rms)
+        out["x"], out["y"], out["y_f64"] = x.numpy(), y.numpy(), y64.numpy()
+        out["geom"] = np.array([D, P, C, L, wseed], np.int64)
+        out["atol"] = np.float64(atol)
+        out["crc"] = np.uint32(synth.state_dict_checksum(sd))
+        out["floor"], out["wrong"] = np.float64(floor), np.float64(wrong)
+        out["keys"] = np.array(list(m.state_dict().keys()))
+        path = os.path.join(OUT, f"mapper_encdec_{tag[3:]}.npz")     # one file per case: float64 outputs are bulky
+        np.savez_compressed(path, **out)
+        print("  ", os.path.basename(path), os.path.getsize(path), "bytes")
+
+
+def gen_decode_encdec(refs, dims, tag):
+    """gen_decode's shape for MappingType.TransformerDecoder (512-d, P = C = 10, 4 layers): generate2 on 8 captions,
+    generate_beam on 4 at T 12, each with a stop id that never fires and one that occurs mid-sequence."""
+    gpt2_prefix, gpt2_prefix_eval = refs[0], refs[1]
+    n_greedy, n_beam, T = 8, 4, 12
+    model, sd = build_ref_model(gpt2_prefix, dims, "transformer_decoder", 512, 10, num_layers=4)
+    out = {"sd_crc": np.uint32(synth.state_dict_checksum(sd))}
+    x = synth.synthetic_clip_embeddings(n_greedy, 512, seed=3)
+    out["greedy_x"] = x.numpy()
+    ids_free = np.zeros((n_greedy, T), np.int64)
+    with torch.no_grad():
+        pe = model.clip_project(x).reshape(n_greedy, 10, -1)
+        out["greedy_prefix_embed"] = pe.numpy()
+        for r in range(n_greedy):
+            txt = gpt2_prefix_eval.generate2(model, FakeTok(stop=dims.vocab + 5), embed=pe[r:r + 1], entry_length=T)
+            ids_free[r] = [int(t) for t in txt.split()]
+    out["greedy_ids_nostop"] = ids_free
+    # (a stop id that fires at the first step makes the reference's generate2 fail on its own squeeze(): leave those out)
+    vals, counts = np.unique(ids_free[:, 2:], return_counts=True)
+    counts = np.where(np.isin(vals, ids_free[:, :2]), 0, counts)
+    stop = int(vals[np.argmax(counts)])
+    out["greedy_stop_id"] = np.int64(stop)
+    ids, lens = np.zeros((n_greedy, T), np.int64), np.zeros(n_greedy, np.int64)
+    with torch.no_grad():
+        for r in range(n_greedy):
+            t = [int(v) for v in gpt2_prefix_eval.generate2(model, FakeTok(stop=stop), embed=pe[r:r + 1], entry_length=T).split()]
+            ids[r, :len(t)], lens[r] = t, len(t)
+    out[f"greedy_ids_T{T}"], out[f"greedy_lens_T{T}"] = ids, lens
+    x = synth.synthetic_clip_embeddings(n_beam, 512, seed=4)
+    out["beam_x"] = x.numpy()
+    with torch.no_grad():
+        pe = model.clip_project(x).reshape(n_beam, 10, -1)
+        out["beam_prefix_embed"] = pe.numpy()
+        first = [capture_beam(gpt2_prefix_eval, model, FakeTok(stop=dims.vocab + 5), pe[r:r + 1], T) for r in range(n_beam)]
+    vals, counts = np.unique(np.concatenate([f["tokens"][:, 1:].reshape(-1) for f in first]), return_counts=True)
+    stop = int(vals[np.argmax(counts)])
+    out["beam_stop_id"] = np.int64(stop)
+    for name, st in (("nostop", dims.vocab + 5), ("stop", stop)):
+        toks, seql = np.zeros((n_beam, 5, T), np.int64), np.zeros((n_beam, 5), np.float32)
+        scs, order = np.zeros((n_beam, 5), np.float32), np.zeros((n_beam, 5), np.int64)
+        with torch.no_grad():
+            for r in range(n_beam):
+                got = capture_beam(gpt2_prefix_eval, model, FakeTok(stop=st), pe[r:r + 1], T)
+                toks[r] = pad_tokens(got["tokens"], T)
+                seql[r], scs[r], order[r] = got["seq_lengths"], got["scores"], got["order"]
+        out[f"beam_{name}_tokens_T{T}"], out[f"beam_{name}_seqlen_T{T}"] = toks, seql
+        out[f"beam_{name}_scores_T{T}"], out[f"beam_{name}_order_T{T}"] = scs, order
+    np.savez_compressed(os.path.join(OUT, f"decode_encdec_{tag}.npz"), **out)
+    print(f"decode_encdec_{tag}.npz written; greedy stop {out['greedy_stop_id']}, beam stop {out['beam_stop_id']}")
 
 
 def gen_checkpoint_keys(refs):
@@ -799,6 +897,8 @@ def main():
     refs = None if args.only and set(args.only) <= {"preprocess", "clip_resnet", "clip_tiny", "clip_b32"} else import_reference()
     jobs = {
         "mappers": lambda: gen_mappers(refs),
+        "mapper_encdec": lambda: gen_mapper_encdec(refs),
+        "decode_encdec_tiny": lambda: gen_decode_encdec(refs, synth.GPT2_TINY, "tiny"),
         "reference_checkpoints": lambda: gen_checkpoint_keys(refs),
         "noise": lambda: gen_noise(refs),
         "logits_tiny": lambda: gen_gpt2_logits(refs, synth.GPT2_TINY, "tiny"),
