@@ -31,10 +31,18 @@ class Gpt2Weights(C.Structure):
                 ("layers", C.POINTER(Gpt2Layer)), ("ln_f_w", c_float_p), ("ln_f_b", c_float_p)]
 
 
+#: one TransformerLayer (reference transformer_mapper.py:54-73): (field of capdec_tmapper_layer, state-dict key) in
+#: checkpoint order -- the order of the train step's per-layer slots too (csrc/train.h: TLayerSlot)
+TMAPPER_LAYER = (
+    ("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("to_queries_w", "attn.to_queries.weight"),
+    ("to_keys_values_w", "attn.to_keys_values.weight"), ("project_w", "attn.project.weight"),
+    ("project_b", "attn.project.bias"), ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"),
+    ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"), ("fc2_b", "mlp.fc2.bias"))
+TMAPPER_LAYER_KEYS = tuple(key for _, key in TMAPPER_LAYER)
+
+
 class TMapperLayer(C.Structure):
-    _fields_ = [(n, c_float_p) for n in (
-        "norm1_w", "norm1_b", "to_queries_w", "to_keys_values_w", "project_w", "project_b",
-        "norm2_w", "norm2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+    _fields_ = [(field, c_float_p) for field, _ in TMAPPER_LAYER]
 
 
 class TMapperWeights(C.Structure):

@@ -4,7 +4,9 @@
 //   weights.hip       capdec_load_* (uploads; Conv1D transposes; BatchNorm folding)
 //   gemm_dispatch.hip the GEMM planner: operand planes cache, which kernel / split for a projection and for the fused
 //                     lm_head, capdec_gemm_f32
-//   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam decode loop, mapper
+//   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam decode loop
+//   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
+//                     forward share (tlayer_self_front / tlayer_tail)
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
 //   clip.hip          CLIP ViT-B/32 towers, the ModifiedResNet tower, image preprocessing
 //   comm.hip          caption-shard bounds and the RCCL all-gather (librccl dlopen'ed)
@@ -56,11 +58,14 @@ struct Gpt2 {
     std::vector<Gpt2Layer> layers;
     std::vector<void *> owned;
 };
+// One TransformerLayer of the reference (transformer_mapper.py:54-73) at width w: its twelve tensors in checkpoint order
+// (TLayerSlot, train.h).  wq is to_queries [w, w], wkv to_keys_values [2w, ref]; both are always valid.
 struct TMapLayer {
-    float *n1w, *n1b, *wqkv, *wproj, *bproj, *n2w, *n2b, *wfc1, *bfc1, *wfc2, *bfc2;
-    // encoder-decoder mapper, decoder layers only: wqkv holds to_queries [d, d] alone; the keys / values of a self layer
-    // come from another input than its queries (wkv [2d, d]); a cross layer's rows sit in Mapper::wkv_cross (wkv = nullptr)
-    float *wkv = nullptr;
+    float *n1w, *n1b, *wq, *wkv, *wproj, *bproj, *n2w, *n2b, *wfc1, *bfc1, *wfc2, *bfc2;
+    // true: TransformerMapper and ref_encoder layers, whose queries, keys and values all read norm1(x): wkv == wq + w * w, so
+    // wq is also the fused [3w, w] projection [q | k | v].  false: prefix_decoder layers -- wkv is a matrix of the layer's
+    // own (odd = self, keys / values from x itself) or this layer's rows of Mapper::wkv_cross (even = cross)
+    bool fused = false;
 };
 struct Mapper {
     int kind = 0;   // 0 none, 1 mlp, 2 transformer, 3 transformer encoder-decoder (inference only)
@@ -272,6 +277,16 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
 // ... its exact second pass: k = 5 lists for the *m_dev rows of the packed operand Apk (in the format of the mode)
 int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_dev, int N, int K, float inv_temp,
                   const TopkOut &o);
+
+// ---- mapper.hip: the TransformerLayer forward, x -> out on M rows of width w (hidden hid):
+//     a1 = norm1(x); qkv = a1 . [q | k | v]^T                                       tlayer_self_front (fused layers)
+//     att = attention(...)                                                          the caller's launch: it is what differs
+//     mid = x + project(att); a2 = norm2(mid); ff = relu(fc1(a2)); out = mid + fc2(ff)      tlayer_tail (every layer)
+// The buffers may alias (inference: x = mid = out, a1 = a2) or be kept per layer (the train forward saves all of them).
+// weight: the GEMMs may cache the weights' operand planes (false in the train forward: the weights change every step).
+struct TLayerBufs { const float *x; float *a1, *qkv; const float *att; float *mid, *a2, *ff, *out; };
+int tlayer_self_front(capdec_ctx *c, const TMapLayer &w, const TLayerBufs &b, int M, int wd, bool weight);
+int tlayer_tail(capdec_ctx *c, const TMapLayer &w, const TLayerBufs &b, int M, int wd, int hid, bool weight);
 
 // ---- decode.hip: the block stack (GPT-2 and the CLIP towers run on it)
 struct StepShape {

@@ -1,6 +1,6 @@
 // The KV-cached batched decode: the pre-LN block stack (GPT-2, and the CLIP towers that run on the same stack), the fused
-// lm_head + candidate selection, the greedy / beam drivers with finished-caption compaction, the mapping networks and the
-// prefix stage -- host-side orchestration only: every operation is a launcher of common.h enqueued on the context's stream.
+// lm_head + candidate selection, the greedy / beam drivers with finished-caption compaction -- host-side orchestration
+// only: every operation is a launcher of common.h enqueued on the context's stream.  (The mapping networks: mapper.hip.)
 #include "context.h"
 
 namespace capdec {
@@ -384,159 +384,12 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int b
     return 0;
 }
 
-// ---------------------------------------------------------------------------- mapper forward
-// One pre-LN layer's tail, shared by the three layer kinds of the encoder-decoder mapper: x += project(att);
-// x += fc2(relu(fc1(norm2(x)))) on M rows of width w (hidden hid); the last GEMM writes to `dst` (x itself, or the
-// caller's output for the last layer)
-static int ed_layer_tail(capdec_ctx *c, const TMapLayer &w, float *x, const float *att, float *xn, float *ff, int M, int wd,
-                         int hid, float *dst) {
-    CAPDEC_TRY(gemm(c, att, wd, w.wproj, wd, x, wd, M, wd, wd, w.bproj, CAPDEC_ACT_NONE, x, wd));
-    { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, x, wd, w.n2w, w.n2b, 1e-5f, xn, wd, M, wd)); }
-    CAPDEC_TRY(gemm(c, xn, wd, w.wfc1, wd, ff, hid, M, hid, wd, w.bfc1, CAPDEC_ACT_RELU));
-    CAPDEC_TRY(gemm(c, ff, hid, w.wfc2, hid, dst, wd, M, wd, hid, w.bfc2, CAPDEC_ACT_NONE, x, wd));
-    return 0;
-}
-
-// TransformerEncoderDecoder (reference transformer_mapper.py:130-145): ref = ref_encoder(linear(x) as [n, C, E]);
-// out = prefix_decoder(prefix_const for every caption, ref).  Decoder layers alternate: even = cross (keys / values of
-// `ref` as it is), odd = self called as layer(x, x): queries from norm1(x), keys / values from x ITSELF -- so the odd
-// layers cannot use a fused [q|k|v] projection of one input.
-static int encdec_chunk(capdec_ctx *c, const float *x, int n, float *out) {
-    Mapper &m = c->map;
-    const int d = m.d, E = m.enc_dim, C = m.clip_len, P = m.P, L = m.n_layers, H = m.heads;
-    const int Me = n * C, Md = n * P, grp = c->tune.ed_attn_group;
-    // refused before the first launch (the loader checked the same: a context cannot hold such a mapper)
-    CAPDEC_CHECK(attn_cross_lds_bytes(C, C, E / H, 1) <= 160 * 1024 && attn_cross_lds_bytes(P, C, d / H, 1) <= 160 * 1024 &&
-                 attn_cross_lds_bytes(P, P, d / H, 1) <= 160 * 1024, "mapper_forward: one head's keys, values and queries exceed 160 KB of LDS");
-    const size_t ldc = (size_t)L * 2 * d;
-    CAPDEC_TRY(c->m_lin.ensure((size_t)Me * E * 4));
-    CAPDEC_TRY(c->m_seq.ensure((size_t)Md * d * 4));
-    CAPDEC_TRY(c->m_x.ensure(std::max((size_t)Me * E, (size_t)Md * d) * 4));
-    CAPDEC_TRY(c->m_qkv.ensure(std::max((size_t)Me * 3 * E, (size_t)Md * 3 * d) * 4));
-    CAPDEC_TRY(c->m_att.ensure(std::max((size_t)Me * E, (size_t)Md * d) * 4));
-    CAPDEC_TRY(c->m_ff.ensure(std::max((size_t)Me * m.enc_hidden, (size_t)Md * m.mlp_hidden) * 4));
-    CAPDEC_TRY(c->m_kvc.ensure((size_t)Me * ldc * 4));
-    CAPDEC_TRY(c->m_hid.ensure((size_t)2 * P * d * 4));
-    float *ref = c->m_lin.as<float>(), *seq = c->m_seq.as<float>(), *xn = c->m_x.as<float>(), *qkv = c->m_qkv.as<float>(),
-          *att = c->m_att.as<float>(), *ff = c->m_ff.as<float>(), *kvc = c->m_kvc.as<float>(), *q0 = c->m_hid.as<float>();
-    // ---- encoder: the TransformerMapper layer at width E on the C rows of linear(x)
-    CAPDEC_TRY(gemm(c, x, m.D, m.lin_w, m.D, ref, C * E, n, C * E, m.D, m.lin_b, CAPDEC_ACT_NONE));
-    for (int l = 0; l < L; ++l) {
-        const TMapLayer &w = m.layers[l];
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, ref, E, w.n1w, w.n1b, 1e-5f, xn, E, Me, E)); }
-        CAPDEC_TRY(gemm(c, xn, E, w.wqkv, E, qkv, 3 * E, Me, 3 * E, E, nullptr, CAPDEC_ACT_NONE));
-        { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, qkv, 3 * E, (size_t)C * 3 * E, qkv + E, qkv + 2 * E, 3 * E, att, n, C, C, H, E / H, grp)); }
-        CAPDEC_TRY(ed_layer_tail(c, w, ref, att, xn, ff, Me, E, m.enc_hidden, ref));
-    }
-    // ---- decoder
-    // `ref` is the same for every cross layer: their to_keys_values, stacked at load, run as ONE GEMM (N = L * 2d)
-    // (5000 captions, L 4: 23.12 -> 22.75 ms per call against one GEMM per layer, profiles/mapper_encdec_bench.txt)
-    CAPDEC_TRY(gemm(c, ref, E, m.wkv_cross, E, kvc, (int)ldc, Me, (int)ldc, E, nullptr, CAPDEC_ACT_NONE));
-    // the residual stream starts as prefix_const in every caption (the concat kernel with no CLIP rows never reads `lin`)
-    { ProfScope ps(c, F_OTHER); CAPDEC_TRY(launch_tmapper_concat(c->stream, nullptr, m.prefix_const, seq, n, 0, P, d)); }
-    float *q = qkv, *kv = qkv + (size_t)Md * d;
-    for (int l = 0; l < 2 * L; ++l) {
-        const TMapLayer &w = m.dec[l];
-        const bool cross = l % 2 == 0;
-        const float *ql = q;
-        size_t q_cap = (size_t)P * d;
-        if (l == 0) {       // ... so layer 0's norm1 and to_queries are caption-independent: P rows, caption stride 0 (22.99 -> 22.75 ms)
-            { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, m.prefix_const, d, w.n1w, w.n1b, 1e-5f, q0 + (size_t)P * d, d, P, d)); }
-            CAPDEC_TRY(gemm(c, q0 + (size_t)P * d, d, w.wqkv, d, q0, d, P, d, d, nullptr, CAPDEC_ACT_NONE));
-            ql = q0;
-            q_cap = 0;
-        } else {
-            { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, seq, d, w.n1w, w.n1b, 1e-5f, xn, d, Md, d)); }
-            CAPDEC_TRY(gemm(c, xn, d, w.wqkv, d, q, d, Md, d, d, nullptr, CAPDEC_ACT_NONE));
-        }
-        if (cross) {
-            const float *kl = kvc + (size_t)(l / 2) * 2 * d;
-            { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, ql, d, q_cap, kl, kl + d, (int)ldc, att, n, P, C, H, d / H, grp)); }
-        } else {
-            CAPDEC_TRY(gemm(c, seq, d, w.wkv, d, kv, 2 * d, Md, 2 * d, d, nullptr, CAPDEC_ACT_NONE));   // the stream itself, not norm1 of it
-            { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, ql, d, q_cap, kv, kv + d, 2 * d, att, n, P, P, H, d / H, grp)); }
-        }
-        CAPDEC_TRY(ed_layer_tail(c, w, seq, att, xn, ff, Md, d, m.mlp_hidden, l == 2 * L - 1 ? out : seq));
-    }
-    return 0;
-}
-
-static int mapper_chunk(capdec_ctx *c, const float *x, int n, float *out) {
-    Mapper &m = c->map;
-    const int d = m.d;
-    if (m.kind == 3) return encdec_chunk(c, x, n, out);
-    if (m.kind == 1) {
-        CAPDEC_TRY(c->m_hid.ensure((size_t)n * m.hidden * 4));
-        CAPDEC_TRY(gemm(c, x, m.D, m.w1, m.D, c->m_hid.as<float>(), m.hidden, n, m.hidden, m.D, m.b1, CAPDEC_ACT_TANH));
-        CAPDEC_TRY(gemm(c, c->m_hid.as<float>(), m.hidden, m.w2, m.hidden, out, m.P * d, n, m.P * d, m.hidden, m.b2,
-                        CAPDEC_ACT_NONE));
-        return 0;
-    }
-    const int S = m.clip_len + m.P, M = n * S, hd = d / m.heads;
-    CAPDEC_TRY(c->m_lin.ensure((size_t)n * m.clip_len * d * 4));
-    CAPDEC_TRY(c->m_seq.ensure((size_t)M * d * 4));
-    CAPDEC_TRY(c->m_x.ensure((size_t)M * d * 4));
-    CAPDEC_TRY(c->m_qkv.ensure((size_t)M * 3 * d * 4));
-    CAPDEC_TRY(c->m_att.ensure((size_t)M * d * 4));
-    CAPDEC_TRY(c->m_ff.ensure((size_t)M * m.mlp_hidden * 4));
-    float *seq = c->m_seq.as<float>(), *xn = c->m_x.as<float>(), *qkv = c->m_qkv.as<float>(),
-          *att = c->m_att.as<float>(), *ff = c->m_ff.as<float>();
-    CAPDEC_TRY(gemm(c, x, m.D, m.lin_w, m.D, c->m_lin.as<float>(), m.clip_len * d, n, m.clip_len * d, m.D, m.lin_b,
-                    CAPDEC_ACT_NONE));
-    { ProfScope ps(c, F_OTHER); CAPDEC_TRY(launch_tmapper_concat(c->stream, c->m_lin.as<float>(), m.prefix_const, seq, n, m.clip_len, m.P, d)); }
-    for (int l = 0; l < m.n_layers; ++l) {
-        const TMapLayer &w = m.layers[l];
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, seq, d, w.n1w, w.n1b, 1e-5f, xn, d, M, d)); }
-        CAPDEC_TRY(gemm(c, xn, d, w.wqkv, d, qkv, 3 * d, M, 3 * d, d, nullptr, CAPDEC_ACT_NONE));
-        { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_mapper(c->stream, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, n, S, m.heads, hd)); }
-        CAPDEC_TRY(gemm(c, att, d, w.wproj, d, seq, d, M, d, d, w.bproj, CAPDEC_ACT_NONE, seq, d));
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, seq, d, w.n2w, w.n2b, 1e-5f, xn, d, M, d)); }
-        CAPDEC_TRY(gemm(c, xn, d, w.wfc1, d, ff, m.mlp_hidden, M, m.mlp_hidden, d, w.bfc1, CAPDEC_ACT_RELU));
-        CAPDEC_TRY(gemm(c, ff, m.mlp_hidden, w.wfc2, m.mlp_hidden, seq, d, M, d, m.mlp_hidden, w.bfc2, CAPDEC_ACT_NONE,
-                        seq, d));
-    }
-    { ProfScope ps(c, F_OTHER); CAPDEC_TRY(launch_tmapper_take(c->stream, seq, out, n, m.clip_len, m.P, d)); }
-    return 0;
-}
-
 
 }  // namespace capdec
 
 using namespace capdec;
 
 extern "C" {
-
-int capdec_normalize_prefix(capdec_ctx *c, const float *x, int n, int dim, int normalize, const float *offset,
-                            float *out) {
-    CAPDEC_CHECK(c && n >= 0 && dim >= 1 && (n == 0 || (x && out)), "normalize_prefix: bad argument");
-    if (n == 0) return 0;
-    CAPDEC_HIP(hipSetDevice(c->device));
-    ProfScope ps(c, F_OTHER);
-    return launch_normalize_prefix(c->stream, x, n, dim, normalize, offset, out);
-}
-
-int capdec_noise_inject(capdec_ctx *c, const float *x, int n, int dim, float variance, const float *offset,
-                        int uniform, int dont_norm, uint64_t seed, const float *noise, const float *u, float *out) {
-    CAPDEC_CHECK(c && n >= 0 && dim >= 1 && (n == 0 || (x && out)), "noise_inject: bad argument");
-    CAPDEC_CHECK(variance >= 0.f, "noise_inject: negative variance");
-    if (n == 0) return 0;
-    CAPDEC_HIP(hipSetDevice(c->device));
-    ProfScope ps(c, F_OTHER);
-    return launch_noise_inject(c->stream, x, n, dim, variance, offset, uniform, dont_norm, seed, noise, u, out);
-}
-
-int capdec_mapper_forward(capdec_ctx *c, const float *x, int n, float *out) {
-    CAPDEC_CHECK(c && c->map.kind != 0, "mapper_forward: no mapper loaded");
-    CAPDEC_CHECK(n >= 0 && (n == 0 || (x && out)), "mapper_forward: bad argument");
-    CAPDEC_HIP(hipSetDevice(c->device));
-    const Mapper &m = c->map;
-    const int chunk = 8192;
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int nc = std::min(chunk, n - c0);
-        CAPDEC_TRY(mapper_chunk(c, x + (size_t)c0 * m.D, nc, out + (size_t)c0 * m.P * m.d));
-    }
-    return 0;
-}
 
 int capdec_gpt2_logits(capdec_ctx *c, const float *embeds, int n, int L, int all_positions, float *logits) {
     CAPDEC_CHECK(c && c->gpt.loaded, "gpt2_logits: GPT-2 weights not loaded");

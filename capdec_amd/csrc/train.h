@@ -25,7 +25,8 @@
 // Translation units (round 6: one 1500-line file until then):
 //   train_step.hip    the step itself -- GPT-2 forward with saved activations, loss, backward -- with the kernels only it uses
 //                     (GELU, the dropouts, embedding / loss-row maps, cross-entropy); capdec_train_step
-//   train_mapper.hip  both mapping networks: forward with saved activations, backward
+//   train_mapper.hip  both mapping networks: forward with saved activations (the TransformerMapper's layers run the shared
+//                     layer forward of mapper.hip, context.h: tlayer_self_front / tlayer_tail), backward
 //   train_ops.hip     what the two share: LayerNorm / attention backward, the block-form attention, transposes, column sums,
 //                     the dX / dW products
 //   train_optim.hip   the trainable-tensor table, gradient / moment arenas, AdamW, the transposed weight copies, and the
@@ -72,6 +73,11 @@ struct Slot {
     size_t n, off;
     int rows = 0, cols = 0;      // rows > 0: a GPT-2 Conv1D weight, kept [out = rows, in = cols] on the device, [in, out] in checkpoints
 };
+// The TransformerMapper's slots, in checkpoint order (= Engine.train_tensor_names): three tensors, then TL_COUNT per layer
+enum TMapSlot { TM_LIN_W = 0, TM_LIN_B, TM_PREFIX_CONST, TM_LAYER0 };
+enum TLayerSlot { TL_N1W = 0, TL_N1B, TL_WQ, TL_WKV, TL_WPROJ, TL_BPROJ, TL_N2W, TL_N2B, TL_WFC1, TL_BFC1, TL_WFC2, TL_BFC2, TL_COUNT };
+inline int tlayer_slot(int layer, TLayerSlot s) { return TM_LAYER0 + TL_COUNT * layer + s; }
+
 struct TrainState {
     // transposed copies of the frozen GPT-2 weights: the "[N, K]" operand of dX = dY W^T (= the checkpoint's own Conv1D
     // layout [in, out]); wte_t [d][Vp] zero-padded to a multiple of 64 columns

@@ -71,8 +71,8 @@ int mapper_forward_saved(capdec_ctx *c, TrainState &t, const float *x, int B, fl
         float *h = seq + Md * l, *hn = seq + Md * (l + 1), *a1 = t.t_a1.as<float>() + Md * l, *qkv = t.t_qkv.as<float>() + Md * 3 * l,
               *att = t.t_att.as<float>() + Md * l, *mid = t.t_mid.as<float>() + Md * l, *a2 = t.t_a2.as<float>() + Md * l,
               *r = t.t_r.as<float>() + (size_t)M * hid * l;
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(st, h, d, w.n1w, w.n1b, 1e-5f, a1, d, M, d)); }
-        CAPDEC_TRY(gemm(c, a1, d, w.wqkv, d, qkv, 3 * d, M, 3 * d, d, nullptr, CAPDEC_ACT_NONE, nullptr, 0, false));
+        const TLayerBufs b{h, a1, qkv, att, mid, a2, r, hn};
+        CAPDEC_TRY(tlayer_self_front(c, w, b, M, d, false));      // (current weights: never cached planes)
         {
             ProfScope ps(c, F_MAP_ATTN);
             if (hd == 96)       // (block-per-(sample, head) kernel when the head fits the LDS; the inference kernel otherwise)
@@ -80,10 +80,7 @@ int mapper_forward_saved(capdec_ctx *c, TrainState &t, const float *x, int B, fl
             else
                 CAPDEC_TRY(launch_attn_mapper(st, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, B, S, m.heads, hd));
         }
-        CAPDEC_TRY(gemm(c, att, d, w.wproj, d, mid, d, M, d, d, w.bproj, CAPDEC_ACT_NONE, h, d, false));
-        { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(st, mid, d, w.n2w, w.n2b, 1e-5f, a2, d, M, d)); }
-        CAPDEC_TRY(gemm(c, a2, d, w.wfc1, d, r, hid, M, hid, d, w.bfc1, CAPDEC_ACT_RELU, nullptr, 0, false));
-        CAPDEC_TRY(gemm(c, r, hid, w.wfc2, hid, hn, d, M, d, hid, w.bfc2, CAPDEC_ACT_NONE, mid, d, false));
+        CAPDEC_TRY(tlayer_tail(c, w, b, M, d, hid, false));
     }
     ProfScope ps(c, F_OTHER);
     return launch_tmapper_take(st, seq + Md * nl, pe, B, m.clip_len, m.P, d);
@@ -122,29 +119,29 @@ int mapper_backward(capdec_ctx *c, TrainState &t, const float *x, const float *d
     hipLaunchKernelGGL(tmapper_put_kernel, grid1(Md), dim3(256), 0, st, dy, ds, B, m.clip_len, m.P, d);
     for (int l = nl - 1; l >= 0; --l) {
         const TMapLayer &w = m.layers[l];
-        const int s0 = 3 + 12 * l;
+        auto g = [&](TLayerSlot s) { return t.grad(tlayer_slot(l, s)); };
         const float *h = seq + Md * l, *a1 = t.t_a1.as<float>() + Md * l, *qkv = t.t_qkv.as<float>() + Md * 3 * l,
                     *att = t.t_att.as<float>() + Md * l, *mid = t.t_mid.as<float>() + Md * l, *a2 = t.t_a2.as<float>() + Md * l,
                     *r = t.t_r.as<float>() + (size_t)M * hid * l;
         // mlp: out = mid + fc2(relu(fc1(a2)))
-        CAPDEC_TRY(linear_dw(c, t, ds, r, M, d, hid, t.grad(s0 + 10), t.grad(s0 + 11)));
+        CAPDEC_TRY(linear_dw(c, t, ds, r, M, d, hid, g(TL_WFC2), g(TL_BFC2)));
         CAPDEC_TRY(linear_dx(c, t, ds, w.wfc2, dr, M, d, hid));
         hipLaunchKernelGGL(relu_bwd_kernel, grid1((size_t)M * hid), dim3(256), 0, st, r, dr, dr, (size_t)M * hid);
-        CAPDEC_TRY(linear_dw(c, t, dr, a2, M, hid, d, t.grad(s0 + 8), t.grad(s0 + 9)));
+        CAPDEC_TRY(linear_dw(c, t, dr, a2, M, hid, d, g(TL_WFC1), g(TL_BFC1)));
         CAPDEC_TRY(linear_dx(c, t, dr, w.wfc1, da, M, hid, d));
-        CAPDEC_TRY(ln_bwd(c, mid, w.n2w, da, ds, ds2, M, d, 1e-5f, t.grad(s0 + 6), t.grad(s0 + 7)));        // ds2 = d mid
+        CAPDEC_TRY(ln_bwd(c, mid, w.n2w, da, ds, ds2, M, d, 1e-5f, g(TL_N2W), g(TL_N2B)));        // ds2 = d mid
         // attention: mid = h + project(att)
-        CAPDEC_TRY(linear_dw(c, t, ds2, att, M, d, d, t.grad(s0 + 4), t.grad(s0 + 5)));
+        CAPDEC_TRY(linear_dw(c, t, ds2, att, M, d, d, g(TL_WPROJ), g(TL_BPROJ)));
         CAPDEC_TRY(linear_dx(c, t, ds2, w.wproj, datt, M, d, d));
         CAPDEC_TRY(train_attn_bwd(c, t, qkv, datt, dqkv, B, S, m.heads, 96, false, scale, nullptr, 1.f));
-        CAPDEC_TRY(linear_dw(c, t, dqkv, a1, M, 3 * d, d, t.grad(s0 + 2), nullptr));      // [to_queries ; to_keys_values]: no bias
-        CAPDEC_TRY(linear_dx(c, t, dqkv, w.wqkv, da, M, 3 * d, d));
-        CAPDEC_TRY(ln_bwd(c, h, w.n1w, da, ds2, ds, M, d, 1e-5f, t.grad(s0 + 0), t.grad(s0 + 1)));          // ds = d h
+        CAPDEC_TRY(linear_dw(c, t, dqkv, a1, M, 3 * d, d, g(TL_WQ), nullptr));      // [to_queries ; to_keys_values]: no bias
+        CAPDEC_TRY(linear_dx(c, t, dqkv, w.wq, da, M, 3 * d, d));
+        CAPDEC_TRY(ln_bwd(c, h, w.n1w, da, ds2, ds, M, d, 1e-5f, g(TL_N1W), g(TL_N1B)));          // ds = d h
     }
     hipLaunchKernelGGL(tmapper_split_grad_kernel, grid1(std::max((size_t)B * m.clip_len * d, (size_t)m.P * d)), dim3(256), 0, st,
-                       ds, dlin, t.grad(2), B, m.clip_len, m.P, d);
+                       ds, dlin, t.grad(TM_PREFIX_CONST), B, m.clip_len, m.P, d);
     CAPDEC_HIP(hipGetLastError());
-    return linear_dw(c, t, dlin, x, B, m.clip_len * d, D, t.grad(0), t.grad(1));
+    return linear_dw(c, t, dlin, x, B, m.clip_len * d, D, t.grad(TM_LIN_W), t.grad(TM_LIN_B));
 }
 
 }  // namespace capdec

@@ -53,9 +53,8 @@ void train_release(capdec_ctx *c) {
 }
 
 // Slot order (capdec.h: capdec_train_get).  MLP: model.0.weight, model.0.bias, model.2.weight, model.2.bias.
-// TransformerMapper: linear.weight, linear.bias, prefix_const, then per layer norm1.weight, norm1.bias,
-// attn.to_queries.weight, attn.to_keys_values.weight (adjacent halves of the fused [3d, d] projection on the device),
-// attn.project.weight, attn.project.bias, norm2.weight, norm2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias
+// TransformerMapper: TMapSlot, then TLayerSlot per layer (train.h); to_queries and to_keys_values are the adjacent halves of
+// the fused [3d, d] projection on the device, so TL_WQ's gradient is also where the fused matrix's begins
 int build_slots(capdec_ctx *c, TrainState &t) {
     if (!t.slots.empty()) return 0;
     Mapper &m = c->map;
@@ -73,14 +72,19 @@ int build_slots(capdec_ctx *c, TrainState &t) {
         const size_t O = (size_t)m.P * d;
         add(m.w1, (size_t)m.hidden * m.D); add(m.b1, m.hidden); add(m.w2, O * m.hidden); add(m.b2, O);
     } else {
-        add(m.lin_w, (size_t)m.clip_len * d * m.D); add(m.lin_b, (size_t)m.clip_len * d); add(m.prefix_const, (size_t)m.P * d);
+        const size_t hid = m.mlp_hidden;
+        struct { float *p; size_t n; } head[TM_LAYER0], s[TL_COUNT];
+        head[TM_LIN_W] = {m.lin_w, (size_t)m.clip_len * d * m.D};   head[TM_LIN_B] = {m.lin_b, (size_t)m.clip_len * d};
+        head[TM_PREFIX_CONST] = {m.prefix_const, (size_t)m.P * d};
+        for (auto &e : head) add(e.p, e.n);
         for (TMapLayer &l : m.layers) {
-            add(l.n1w, d); add(l.n1b, d);
-            add(l.wqkv, d * d); add(l.wqkv + d * d, 2 * d * d);
-            add(l.wproj, d * d); add(l.bproj, d);
-            add(l.n2w, d); add(l.n2b, d);
-            add(l.wfc1, (size_t)m.mlp_hidden * d); add(l.bfc1, m.mlp_hidden);
-            add(l.wfc2, d * m.mlp_hidden); add(l.bfc2, d);
+            s[TL_N1W] = {l.n1w, d};             s[TL_N1B] = {l.n1b, d};
+            s[TL_WQ] = {l.wq, d * d};           s[TL_WKV] = {l.wkv, 2 * d * d};
+            s[TL_WPROJ] = {l.wproj, d * d};     s[TL_BPROJ] = {l.bproj, d};
+            s[TL_N2W] = {l.n2w, d};             s[TL_N2B] = {l.n2b, d};
+            s[TL_WFC1] = {l.wfc1, hid * d};     s[TL_BFC1] = {l.bfc1, hid};
+            s[TL_WFC2] = {l.wfc2, d * hid};     s[TL_BFC2] = {l.bfc2, d};
+            for (auto &e : s) add(e.p, e.n);
         }
     }
     if (t.train_gpt) {

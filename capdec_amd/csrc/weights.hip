@@ -94,6 +94,42 @@ static int upload_conv_bn(ResNet &r, const capdec_conv_bn &s, bool first, ConvW 
     return 0;
 }
 
+// One TransformerLayer (context.h: TMapLayer) at width `w`, hidden `hid`, for the entry point `who`.  fused: [to_queries ;
+// to_keys_values] go up as one [3w, w] matrix, rows [q | k | v] (TransformerMapper, ref_encoder: all three read norm1(x)).
+// Otherwise to_queries alone, and to_keys_values [2w, ref] goes to kv_dst (the layer's rows of the stacked cross matrix)
+// or, with kv_dst == nullptr, to a matrix of the layer's own.
+static int upload_tlayer(Mapper &m, const char *who, const capdec_tmapper_layer &s, TMapLayer &t, int w, int hid, int ref,
+                         bool fused, float *kv_dst) {
+    CAPDEC_CHECK(s.norm1_w && s.norm1_b && s.to_queries_w && s.to_keys_values_w && s.project_w && s.project_b &&
+                 s.norm2_w && s.norm2_b && s.fc1_w && s.fc1_b && s.fc2_w && s.fc2_b, std::string(who) + ": null layer weight");
+    t.fused = fused;
+    CAPDEC_TRY(upload(m.owned, s.norm1_w, w, &t.n1w));
+    CAPDEC_TRY(upload(m.owned, s.norm1_b, w, &t.n1b));
+    if (fused) {
+        void *p = nullptr;
+        CAPDEC_HIP(hipMalloc(&p, (size_t)3 * w * w * 4));
+        m.owned.push_back(p);
+        t.wq = (float *)p;
+        t.wkv = t.wq + (size_t)w * w;
+        CAPDEC_HIP(hipMemcpy(t.wq, s.to_queries_w, (size_t)w * w * 4, hipMemcpyHostToDevice));
+        CAPDEC_HIP(hipMemcpy(t.wkv, s.to_keys_values_w, (size_t)2 * w * w * 4, hipMemcpyHostToDevice));
+    } else {
+        CAPDEC_TRY(upload(m.owned, s.to_queries_w, (size_t)w * w, &t.wq));
+        if (kv_dst) CAPDEC_HIP(hipMemcpy(kv_dst, s.to_keys_values_w, (size_t)2 * w * ref * 4, hipMemcpyHostToDevice));
+        else CAPDEC_TRY(upload(m.owned, s.to_keys_values_w, (size_t)2 * w * ref, &kv_dst));
+        t.wkv = kv_dst;
+    }
+    CAPDEC_TRY(upload(m.owned, s.project_w, (size_t)w * w, &t.wproj));
+    CAPDEC_TRY(upload(m.owned, s.project_b, w, &t.bproj));
+    CAPDEC_TRY(upload(m.owned, s.norm2_w, w, &t.n2w));
+    CAPDEC_TRY(upload(m.owned, s.norm2_b, w, &t.n2b));
+    CAPDEC_TRY(upload(m.owned, s.fc1_w, (size_t)hid * w, &t.wfc1));
+    CAPDEC_TRY(upload(m.owned, s.fc1_b, hid, &t.bfc1));
+    CAPDEC_TRY(upload(m.owned, s.fc2_w, (size_t)w * hid, &t.wfc2));
+    CAPDEC_TRY(upload(m.owned, s.fc2_b, w, &t.bfc2));
+    return 0;
+}
+
 // out[N, Ho, Wo, cout_p] = act(conv(in) folded-BN (+ resid)); k = 3: im2col + GEMM; returns the output spatial size
 
 }  // namespace capdec
@@ -179,61 +215,9 @@ int capdec_load_mapper_transformer(capdec_ctx *c, const capdec_tmapper_weights *
     CAPDEC_TRY(upload(m.owned, w->linear_b, (size_t)m.clip_len * d, &m.lin_b));
     CAPDEC_TRY(upload(m.owned, w->prefix_const, (size_t)m.P * d, &m.prefix_const));
     m.layers.resize(m.n_layers);
-    for (int l = 0; l < m.n_layers; ++l) {
-        const capdec_tmapper_layer &s = w->layers[l];
-        TMapLayer &t = m.layers[l];
-        CAPDEC_TRY(upload(m.owned, s.norm1_w, d, &t.n1w));
-        CAPDEC_TRY(upload(m.owned, s.norm1_b, d, &t.n1b));
-        // fused projection [3d, d] = [to_queries ; to_keys_values] -> rows [q | k | v]
-        CAPDEC_CHECK(s.to_queries_w && s.to_keys_values_w, "load_mapper_transformer: null weight");
-        void *p = nullptr;
-        CAPDEC_HIP(hipMalloc(&p, (size_t)3 * d * d * 4));
-        m.owned.push_back(p);
-        t.wqkv = (float *)p;
-        CAPDEC_HIP(hipMemcpy(t.wqkv, s.to_queries_w, (size_t)d * d * 4, hipMemcpyHostToDevice));
-        CAPDEC_HIP(hipMemcpy(t.wqkv + (size_t)d * d, s.to_keys_values_w, (size_t)2 * d * d * 4, hipMemcpyHostToDevice));
-        CAPDEC_TRY(upload(m.owned, s.project_w, (size_t)d * d, &t.wproj));
-        CAPDEC_TRY(upload(m.owned, s.project_b, d, &t.bproj));
-        CAPDEC_TRY(upload(m.owned, s.norm2_w, d, &t.n2w));
-        CAPDEC_TRY(upload(m.owned, s.norm2_b, d, &t.n2b));
-        CAPDEC_TRY(upload(m.owned, s.fc1_w, (size_t)m.mlp_hidden * d, &t.wfc1));
-        CAPDEC_TRY(upload(m.owned, s.fc1_b, m.mlp_hidden, &t.bfc1));
-        CAPDEC_TRY(upload(m.owned, s.fc2_w, (size_t)d * m.mlp_hidden, &t.wfc2));
-        CAPDEC_TRY(upload(m.owned, s.fc2_b, d, &t.bfc2));
-    }
+    for (int l = 0; l < m.n_layers; ++l)
+        CAPDEC_TRY(upload_tlayer(m, "load_mapper_transformer", w->layers[l], m.layers[l], d, m.mlp_hidden, d, true, nullptr));
     m.kind = 2;
-    return 0;
-}
-
-// one layer of the encoder-decoder mapper at width `w` (hidden `hid`): fused = [to_queries ; to_keys_values] as one
-// [3w, w] projection (encoder: both read norm1(x)); otherwise to_queries alone, and to_keys_values [2w, ref] goes to
-// *kv_dst (the stacked cross matrix) or, with kv_dst == nullptr, to a matrix of the layer's own
-static int upload_ed_layer(Mapper &m, const capdec_tmapper_layer &s, TMapLayer &t, int w, int hid, int ref, bool fused,
-                           float *kv_dst) {
-    CAPDEC_CHECK(s.norm1_w && s.norm1_b && s.to_queries_w && s.to_keys_values_w && s.project_w && s.project_b &&
-                 s.norm2_w && s.norm2_b && s.fc1_w && s.fc1_b && s.fc2_w && s.fc2_b, "load_mapper_encdec: null layer weight");
-    CAPDEC_TRY(upload(m.owned, s.norm1_w, w, &t.n1w));
-    CAPDEC_TRY(upload(m.owned, s.norm1_b, w, &t.n1b));
-    if (fused) {
-        void *p = nullptr;
-        CAPDEC_HIP(hipMalloc(&p, (size_t)3 * w * w * 4));
-        m.owned.push_back(p);
-        t.wqkv = (float *)p;
-        CAPDEC_HIP(hipMemcpy(t.wqkv, s.to_queries_w, (size_t)w * w * 4, hipMemcpyHostToDevice));
-        CAPDEC_HIP(hipMemcpy(t.wqkv + (size_t)w * w, s.to_keys_values_w, (size_t)2 * w * w * 4, hipMemcpyHostToDevice));
-    } else {
-        CAPDEC_TRY(upload(m.owned, s.to_queries_w, (size_t)w * w, &t.wqkv));
-        if (kv_dst) CAPDEC_HIP(hipMemcpy(kv_dst, s.to_keys_values_w, (size_t)2 * w * ref * 4, hipMemcpyHostToDevice));
-        else CAPDEC_TRY(upload(m.owned, s.to_keys_values_w, (size_t)2 * w * ref, &t.wkv));
-    }
-    CAPDEC_TRY(upload(m.owned, s.project_w, (size_t)w * w, &t.wproj));
-    CAPDEC_TRY(upload(m.owned, s.project_b, w, &t.bproj));
-    CAPDEC_TRY(upload(m.owned, s.norm2_w, w, &t.n2w));
-    CAPDEC_TRY(upload(m.owned, s.norm2_b, w, &t.n2b));
-    CAPDEC_TRY(upload(m.owned, s.fc1_w, (size_t)hid * w, &t.wfc1));
-    CAPDEC_TRY(upload(m.owned, s.fc1_b, hid, &t.bfc1));
-    CAPDEC_TRY(upload(m.owned, s.fc2_w, (size_t)w * hid, &t.wfc2));
-    CAPDEC_TRY(upload(m.owned, s.fc2_b, w, &t.bfc2));
     return 0;
 }
 
@@ -277,12 +261,12 @@ int capdec_load_mapper_encdec(capdec_ctx *c, const capdec_edmapper_weights *w) {
     m.owned.push_back(p);
     m.wkv_cross = (float *)p;
     m.layers.resize(L);
-    for (int l = 0; l < L; ++l) CAPDEC_TRY(upload_ed_layer(m, w->enc_layers[l], m.layers[l], E, m.enc_hidden, E, true, nullptr));
+    for (int l = 0; l < L; ++l) CAPDEC_TRY(upload_tlayer(m, "load_mapper_encdec", w->enc_layers[l], m.layers[l], E, m.enc_hidden, E, true, nullptr));
     m.dec.resize(2 * L);
     for (int l = 0; l < 2 * L; ++l) {
         const bool cross = l % 2 == 0;
-        CAPDEC_TRY(upload_ed_layer(m, w->dec_layers[l], m.dec[l], d, m.mlp_hidden, cross ? E : d, false,
-                                   cross ? m.wkv_cross + (size_t)(l / 2) * 2 * d * E : nullptr));
+        CAPDEC_TRY(upload_tlayer(m, "load_mapper_encdec", w->dec_layers[l], m.dec[l], d, m.mlp_hidden, cross ? E : d, false,
+                                 cross ? m.wkv_cross + (size_t)(l / 2) * 2 * d * E : nullptr));
     }
     m.kind = 3;
     return 0;

@@ -124,27 +124,33 @@ class Engine:
               "capdec_load_mapper_mlp")
         self.mapper = dict(kind="mlp", D=D, P=P, d=d)
 
+    @staticmethod
+    def _tmapper_layers(sd: Dict[str, torch.Tensor], stem: str, count: int, keep: list, shapes=None):
+        """a ``TMapperLayer`` array from the tensors ``{stem}{i}.{key}``; the host copies go to ``keep`` (they must outlive
+        the load call).  ``shapes(i)``: field -> the shape layer i's tensor must have (unchecked when None)"""
+        layers = (_capi.TMapperLayer * count)()
+        for i in range(count):
+            want = shapes(i) if shapes else None
+            for field, key in _capi.TMAPPER_LAYER:
+                a = _f32(sd[f"{stem}{i}.{key}"])
+                if want and tuple(a.shape) != want[field]:
+                    raise CapdecError(f"mapper: {stem}{i}.{key} is {tuple(a.shape)}, expected {want[field]}")
+                keep.append(a)
+                setattr(layers[i], field, _fp(a))
+        return layers
+
     def load_mapper_transformer(self, sd: Dict[str, torch.Tensor], prefix: str = "clip_project.", num_heads: int = 8):
         lw, lb = _f32(sd[prefix + "linear.weight"]), _f32(sd[prefix + "linear.bias"])
         pc = _f32(sd[prefix + "prefix_const"])
         P, d = pc.shape
         clip_len = lw.shape[0] // d
+        stem = prefix + "transformer.layers."
         n_layers = 0
-        while f"{prefix}transformer.layers.{n_layers}.norm1.weight" in sd:
+        while f"{stem}{n_layers}.norm1.weight" in sd:
             n_layers += 1
         keep = [lw, lb, pc]
-        layers = (_capi.TMapperLayer * n_layers)()
-        names = [("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("to_queries_w", "attn.to_queries.weight"),
-                 ("to_keys_values_w", "attn.to_keys_values.weight"), ("project_w", "attn.project.weight"),
-                 ("project_b", "attn.project.bias"), ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"),
-                 ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"),
-                 ("fc2_b", "mlp.fc2.bias")]
-        for i in range(n_layers):
-            for field, key in names:
-                a = _f32(sd[f"{prefix}transformer.layers.{i}.{key}"])
-                keep.append(a)
-                setattr(layers[i], field, _fp(a))
-        hid = _f32(sd[f"{prefix}transformer.layers.0.mlp.fc1.weight"]).shape[0]
+        layers = self._tmapper_layers(sd, stem, n_layers, keep)
+        hid = sd[f"{stem}0.mlp.fc1.weight"].shape[0]
         w = _capi.TMapperWeights(lw.shape[1], P, clip_len, n_layers, num_heads, d, hid, _fp(lw), _fp(lb), _fp(pc), layers)
         self._chk(self.lib.capdec_load_mapper_transformer(self._h, C.byref(w)), "capdec_load_mapper_transformer")
         self.mapper = dict(kind="transformer", D=lw.shape[1], P=P, d=d, clip_length=clip_len, num_layers=n_layers)
@@ -161,31 +167,20 @@ class Engine:
         if n_layers == 0 or f"{prefix}prefix_decoder.layers.{2 * n_layers - 1}.norm1.weight" not in sd or \
                 f"{prefix}prefix_decoder.layers.{2 * n_layers}.norm1.weight" in sd:
             raise CapdecError(f"encoder-decoder mapper: {n_layers} ref_encoder layers need {2 * n_layers} prefix_decoder layers")
-        enc = _f32(sd[f"{prefix}ref_encoder.layers.0.norm1.weight"]).shape[0]
+        enc = sd[f"{prefix}ref_encoder.layers.0.norm1.weight"].shape[0]
         clip_len = lw.shape[0] // enc
         keep = [lw, lb, pc]
-        names = [("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("to_queries_w", "attn.to_queries.weight"),
-                 ("to_keys_values_w", "attn.to_keys_values.weight"), ("project_w", "attn.project.weight"),
-                 ("project_b", "attn.project.bias"), ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"),
-                 ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"),
-                 ("fc2_b", "mlp.fc2.bias")]
 
         def stack(which: str, count: int, width: int):
-            layers = (_capi.TMapperLayer * count)()
-            hid = _f32(sd[f"{prefix}{which}.layers.0.mlp.fc1.weight"]).shape[0]
-            for i in range(count):
+            hid = sd[f"{prefix}{which}.layers.0.mlp.fc1.weight"].shape[0]
+
+            def shapes(i: int):      # keys / values of an even (cross) decoder layer come from the encoder's rows
                 ref = width if which == "ref_encoder" or i % 2 == 1 else enc
-                shapes = {"norm1_w": (width,), "norm1_b": (width,), "to_queries_w": (width, width),
-                          "to_keys_values_w": (2 * width, ref), "project_w": (width, width), "project_b": (width,),
-                          "norm2_w": (width,), "norm2_b": (width,), "fc1_w": (hid, width), "fc1_b": (hid,),
-                          "fc2_w": (width, hid), "fc2_b": (width,)}
-                for field, key in names:
-                    a = _f32(sd[f"{prefix}{which}.layers.{i}.{key}"])
-                    if tuple(a.shape) != shapes[field]:
-                        raise CapdecError(f"encoder-decoder mapper: {which}.layers.{i}.{key} is {tuple(a.shape)}, expected {shapes[field]}")
-                    keep.append(a)
-                    setattr(layers[i], field, _fp(a))
-            return layers, hid
+                return {"norm1_w": (width,), "norm1_b": (width,), "to_queries_w": (width, width),
+                        "to_keys_values_w": (2 * width, ref), "project_w": (width, width), "project_b": (width,),
+                        "norm2_w": (width,), "norm2_b": (width,), "fc1_w": (hid, width), "fc1_b": (hid,),
+                        "fc2_w": (width, hid), "fc2_b": (width,)}
+            return self._tmapper_layers(sd, f"{prefix}{which}.layers.", count, keep, shapes), hid
 
         if lw.shape[0] != clip_len * enc or tuple(lb.shape) != (clip_len * enc,):
             raise CapdecError(f"encoder-decoder mapper: linear.weight rows {lw.shape[0]} are not a multiple of the encoder width {enc}")
@@ -543,10 +538,7 @@ class Engine:
             return ["model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias"]
         names = ["linear.weight", "linear.bias", "prefix_const"]
         for i in range(num_layers):
-            names += [f"transformer.layers.{i}.{n}" for n in (
-                "norm1.weight", "norm1.bias", "attn.to_queries.weight", "attn.to_keys_values.weight", "attn.project.weight",
-                "attn.project.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight",
-                "mlp.fc2.bias")]
+            names += [f"transformer.layers.{i}.{key}" for key in _capi.TMAPPER_LAYER_KEYS]
         return names
 
     def train_step(self, prefix: torch.Tensor, tokens: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-6,
