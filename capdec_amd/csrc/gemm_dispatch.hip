@@ -283,8 +283,11 @@ int capdec_gemm_f32(capdec_ctx *c, const float *a, int lda, const float *bt, int
         // (an uncached B keeps the two-accumulator kernels: measuring max |b| costs a reduction and a stream synchronisation
         //  per call -- paid only when a geometry is FORCED, CAPDEC_H2W >= 2: how the parity tests reach the wide tiles)
         if (!cache && fmt == PK_F16X2 && c->tune.h2w >= 2) CAPDEC_TRY(weight_wide_ok(c, bt, (size_t)N * K, &e.wide_ok));
-        // (the hook leaves the geometry planners on in the batch-invariant mode and never splits the one-plane kernels)
-        CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, /*split=*/!mode_single(c), /*invariant=*/false));
+        // (the hook leaves the geometry planners on in the batch-invariant mode.  Split-K of the one-plane kernels: under
+        //  CAPDEC_HOOK_PACKA the decision of gemm_packed -- CAPDEC_X1_SPLITK -- so that the tests reach gemm_x1_splitk_kernel;
+        //  without the flag, the tools/ micro-benchmarks, never)
+        const bool split = !mode_single(c) || (packa && c->tune.x1_splitk);
+        CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, split, /*invariant=*/false));
         return launch_packed(c, fmt, pa, pb, cc, ldc, M, N, K, e, 2.0 * M * (double)N * K);
     }
     return gemm(c, a, lda, bt, ldb, cc, ldc, M, N, K, bias, act, resid, ldr, /*weight=*/cache);

@@ -644,17 +644,44 @@ class Engine:
         self._chk(self.lib.capdec_set_debug_diverge(self._h, int(bool(on))), "set_debug_diverge")
 
     # ------------------------------------------------------------------ hooks
-    def gemm(self, a: torch.Tensor, bt: torch.Tensor, bias=None, resid=None, act: int = 0) -> torch.Tensor:
-        a, bt = self._dev(a), self._dev(bt)
+    def _rows(self, t: torch.Tensor, what: str) -> torch.Tensor:
+        """a 2-D fp32 operand on the device as it is when its rows are contiguous (a column slice of a wider tensor keeps
+        its row stride: the product call sites pass lda = T * C, ldc = Vp); anything else is copied to a dense tensor"""
+        if (t.device == self.device and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and
+                t.stride(0) >= t.shape[1]):
+            return t
+        if what == "out":
+            raise CapdecError("gemm: out= must be a 2-D fp32 tensor on the engine's device with contiguous rows")
+        return self._dev(t)
+
+    def gemm(self, a: torch.Tensor, bt: torch.Tensor, bias=None, resid=None, act: int = 0, out=None) -> torch.Tensor:
+        """out = act(a . bt^T + bias) + resid.  ``a`` [M, K] and ``resid`` [M, N] may be row-strided views (their real row
+        strides are passed as lda / ldr); ``out=`` is an [M, N] view with row stride ldc >= N, written in place and
+        returned; ``resid is out`` accumulates onto the output as the block stack does (h += ...)."""
+        a, bt = self._rows(a, "a"), self._dev(bt)
+        if a.stride(0) % 4 or a.data_ptr() % 16:      # (the kernels read 16-byte pieces of a row)
+            a = a.clone(memory_format=torch.contiguous_format)
         M, K = a.shape
         N = bt.shape[0]
-        out = torch.empty(M, N, device=self.device, dtype=torch.float32)
+        if bt.shape[1] != K:
+            raise CapdecError(f"gemm: a is [{M}, {K}] but bt is {list(bt.shape)}")
+        if out is None:
+            out = torch.empty(M, N, device=self.device, dtype=torch.float32)
+        else:
+            out = self._rows(out, "out")
+            if tuple(out.shape) != (M, N):
+                raise CapdecError(f"gemm: out= must be [{M}, {N}], got {list(out.shape)}")
         b = self._dev(bias) if bias is not None else None
-        r = self._dev(resid) if resid is not None else None
+        r = None
+        if resid is not None:
+            r = out if resid is out else self._rows(resid, "resid")
+            if tuple(r.shape) != (M, N):
+                raise CapdecError(f"gemm: resid must be [{M}, {N}], got {list(r.shape)}")
         self._sync_stream()
-        self._chk(self.lib.capdec_gemm_f32(self._h, a.data_ptr(), K, bt.data_ptr(), K, out.data_ptr(), N, M, N, K,
-                                       b.data_ptr() if b is not None else None,
-                                       r.data_ptr() if r is not None else None, N, act), "capdec_gemm_f32")
+        self._chk(self.lib.capdec_gemm_f32(self._h, a.data_ptr(), a.stride(0), bt.data_ptr(), K, out.data_ptr(), out.stride(0),
+                                       M, N, K, b.data_ptr() if b is not None else None,
+                                       r.data_ptr() if r is not None else None, r.stride(0) if r is not None else N, act),
+                  "capdec_gemm_f32")
         return out
 
     def set_gemm_mode(self, mode: str):

@@ -12,6 +12,21 @@ import glob
 import sys
 
 
+def read_kernel_trace(src):
+    """every launch of the *kernel_trace.csv files below ``src`` in start order: (start ns, end ns, kernel name without its
+    argument list, grid in THREADS as "XxYxZ", workgroup size as "XxYxZ").  Shared with tests/test_hip_gemm_plans.py."""
+    rows = []
+    for p in glob.glob(f"{src}/**/*kernel_trace.csv", recursive=True):
+        for r in csv.DictReader(open(p, newline="")):
+            s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
+            name = r["Kernel_Name"].split("(")[0].strip()
+            grid = r.get("Grid_Size") or "x".join(r.get(k, "1") for k in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z"))
+            wg = r.get("Workgroup_Size") or "x".join(r.get(k, "1") for k in ("Workgroup_Size_X", "Workgroup_Size_Y", "Workgroup_Size_Z"))
+            rows.append((s, e, name, grid, wg))
+    rows.sort()
+    return rows
+
+
 def main():
     import argparse
     ap = argparse.ArgumentParser()
@@ -21,18 +36,10 @@ def main():
     ap.add_argument("--skip-first-ms", type=float, default=0.0)
     a = ap.parse_args()
     src, out, title, skip_ms = a.src, a.out, a.title, a.skip_first_ms
-    rows = []
-    for p in glob.glob(f"{src}/**/*kernel_trace.csv", recursive=True):
-        for r in csv.DictReader(open(p, newline="")):
-            s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
-            name = r["Kernel_Name"].split("(")[0].strip()
-            grid = r.get("Grid_Size") or "x".join(r.get(k, "1") for k in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z"))
-            wg = r.get("Workgroup_Size") or "x".join(r.get(k, "1") for k in ("Workgroup_Size_X", "Workgroup_Size_Y", "Workgroup_Size_Z"))
-            rows.append((s, e, name, grid, wg))
+    rows = read_kernel_trace(src)
     if not rows:
         open(out, "w").write("no kernel_trace.csv rows found\n")
         return
-    rows.sort()
     t0 = rows[0][0] + int(skip_ms * 1e6)
     rows = [r for r in rows if r[0] >= t0]
     span = (rows[-1][1] - rows[0][0]) / 1e6
