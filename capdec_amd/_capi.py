@@ -142,6 +142,8 @@ SIGNATURES = {
     "capdec_wte_lookup": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "capdec_decode_greedy": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP]),
     "capdec_decode_greedy_forced": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP]),
+    "capdec_decode_sample": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
+                                       _VP, _VP, _VP, _VP]),
     "capdec_decode_beam": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP,
                                      _VP, _VP]),
     "capdec_gemm_f32": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
@@ -158,6 +160,7 @@ SIGNATURES = {
     "capdec_decode_stats": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "capdec_set_compact": (C.c_int, [_VP, C.c_int]),
     "capdec_decode_step_rows": (C.c_int, [_VP, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "capdec_decode_chunks": (C.c_int, [_VP, C.POINTER(C.c_int)]),
     "capdec_timer_start": (C.c_int, [_VP]),
     "capdec_timer_stop_ms": (C.c_int, [_VP, c_float_p]),
     "capdec_profile_enable": (C.c_int, [_VP, C.c_int]),

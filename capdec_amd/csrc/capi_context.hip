@@ -81,6 +81,10 @@ bool tuning_from_env(Tuning *t, std::string *err) {
     env_flag("CAPDEC_TRAIN_ATTN_BLK", &t->train_attn_blk);
     env_flag("CAPDEC_LMHEAD_K3", &t->lmhead_k3);
     env_int("CAPDEC_LMHEAD_K3_MAX", &t->lmhead_k3_max);
+    if (env_int("CAPDEC_SAMPLE_ROWS", &t->sample_rows) && t->sample_rows < 1) {
+        *err = "create: CAPDEC_SAMPLE_ROWS must be >= 1";
+        return false;
+    }
     env_flag("CAPDEC_KV_DIRECT", &t->kv_direct);
     env_flag("CAPDEC_CLIP_TRUNC", &t->clip_trunc);
     env_flag("CAPDEC_RN_PACKED", &t->rn_packed);
@@ -177,7 +181,7 @@ void capdec_destroy(capdec_ctx *c) {
     DBuf *bufs[] = {&c->h, &c->x, &c->qkv, &c->att, &c->ff, &c->xl, &c->tmax, &c->tsum, &c->cval, &c->cidx,
                     &c->lse, &c->topv, &c->topi, &c->kc, &c->vc, &c->tokens, &c->scores, &c->seq, &c->stopped,
                     &c->done, &c->anc, &c->next_tok, &c->alive, &c->gids, &c->glens, &c->m_hid, &c->m_lin, &c->m_seq,
-                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->lmflag, &c->xpk2, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
+                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->lmflag, &c->xpk2, &c->slogits, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
                     &c->r_a, &c->r_b, &c->r_c, &c->r_d, &c->r_e, &c->r_f, &c->r_col, &c->r_pk1, &c->r_pk2, &c->r_xpk,
                     &c->r_ypk, &c->r_xi, &c->r_idp, &c->r_zero};
     for (DBuf *b : bufs) b->release();
@@ -274,6 +278,12 @@ int capdec_decode_step_rows(capdec_ctx *c, int *rows, int cap, int *n) {
     CAPDEC_CHECK(c && n && (rows || cap <= 0), "null argument");
     *n = (int)c->stat_step_rows.size();
     for (int i = 0; i < *n && i < cap; ++i) rows[i] = c->stat_step_rows[i];
+    return 0;
+}
+
+int capdec_decode_chunks(capdec_ctx *c, int *chunks) {
+    CAPDEC_CHECK(c && chunks, "null argument");
+    *chunks = c->stat_chunks;
     return 0;
 }
 

@@ -357,6 +357,12 @@ int launch_greedy_step(hipStream_t st, const int *top_idx, int rows, int step, i
                        int *ids, int *lens, uint8_t *done, int *next_tok, int *alive_count,
                        const int *cmap = nullptr, int k = 1, const int *forced = nullptr, const float *top_val = nullptr,
                        const float *lse = nullptr, float *stats = nullptr);
+// sample.hip: one nucleus-sampling decode step over materialised logits [rows, ld], the activation rows row0 .. row0 + rows
+// of the step -- writes what greedy_step_kernel writes (plus logp [captions, T], may be nullptr).  u [captions, T]
+// (nullptr: Philox keyed by (seed, cap_off + caption, step)).
+int launch_sample_top_p(hipStream_t st, const float *logits, int ld, int rows, int row0, int V, float inv_temp, float top_p,
+                        uint64_t seed, const float *u, int cap_off, int step, int T, int stop_id, int alt_stop_id, int *ids,
+                        int *lens, uint8_t *done, int *next_tok, int *alive_count, float *logp, const int *cmap);
 // mean over the rows with label != ignore_index of logsumexp(logits[row]) - logits[row][label]; nll_ws: rows floats
 int launch_cross_entropy_mean(hipStream_t st, const float *logits, int ld, const int *labels, int rows, int V,
                               int ignore_index, float *nll_ws, float *out);

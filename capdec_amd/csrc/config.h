@@ -34,6 +34,8 @@ struct Tuning {
     bool lmhead_k3 = true;        // CAPDEC_LMHEAD_K3=0: the wide lm_head keeps k candidates per tile (no exact second pass)
     int lmhead_k3_max = 60;       // CAPDEC_LMHEAD_K3_MAX: per mille of the rows taking the second pass above which a decode
                                   //   call goes back to k per tile (checked at the poll points; break-even is ~80)
+    int sample_rows = 2048;       // CAPDEC_SAMPLE_ROWS: rows of fp32 logits the sampling decode materialises at a time (2048 rows of
+                                  //   GPT-2's vocabulary = 412 MB); a step with more rows loops lm_head + sampler over row blocks
     bool kv_direct = true;        // CAPDEC_KV_DIRECT=0: the attention kernel appends K / V itself
     bool clip_trunc = true;       // CAPDEC_CLIP_TRUNC=0: the CLIP text tower computes all 77 positions of every caption (default: only
                                   //   the positions up to a chunk's last EOT; captions sorted by length)

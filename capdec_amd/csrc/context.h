@@ -4,7 +4,8 @@
 //   weights.hip       capdec_load_* (uploads; Conv1D transposes; BatchNorm folding)
 //   gemm_dispatch.hip the GEMM planner: operand planes cache, which kernel / split for a projection and for the fused
 //                     lm_head, capdec_gemm_f32
-//   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam decode loop
+//   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam / sampling decode loop
+//                     (the sampling kernel itself: sample.hip)
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
 //                     forward share (tlayer_self_front / tlayer_tail)
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
@@ -157,6 +158,7 @@ struct capdec_ctx {
                                                              // formats (train forward f16x2, decode in a one-plane mode) keeps both
     DBuf x3_tmp, xpk, apk, fpk, a_tmp;   // scratch planes for un-cached matrices; packed LayerNorm output; packed fp32-A
     int stat_steps = 0, stat_compactions = 0;      // last decode call: steps run, compactions done,
+    int stat_chunks = 0;                           // ... and the chunks its captions were split into (capdec_decode_chunks)
     long long stat_row_steps = 0;                  // activation rows pushed through the GPT-2 body (prefill excluded)
     std::vector<int> stat_step_rows;               // ... per decode step (capdec_decode_step_rows)
     bool batch_invariant = false;   // capdec_set_batch_invariant: no launch-size dependent summation order (no split-K, pinned kernel variants)
@@ -177,6 +179,7 @@ struct capdec_ctx {
     int train_scope = 0;                     // capdec_train_set_scope: survives capdec_train_reset and weight reloads
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
     unsigned long long train_drop_seed = 0;  // ... key of the Philox keep-mask stream (counter = element, train step)
+    DBuf slogits;          // sampling decode: fp32 logits of one row block, [min(rows, tune.sample_rows), ld] (decode.hip: lm_head_sample)
     DBuf lmflag, xpk2;     // fused lm_head with 3 candidates per tile: [count, total, rows...] of the rows whose top 5 need
                            // the exact second pass; their compacted packed A operand (decode.hip: lm_head_select)
     DBuf m_hid, m_lin, m_seq, m_x, m_qkv, m_att, m_ff;

@@ -1,5 +1,5 @@
 // The KV-cached batched decode: the pre-LN block stack (GPT-2, and the CLIP towers that run on the same stack), the fused
-// lm_head + candidate selection, the greedy / beam drivers with finished-caption compaction -- host-side orchestration
+// lm_head + candidate selection, the greedy / beam / sampling drivers with finished-caption compaction -- host-side orchestration
 // only: every operation is a launcher of common.h enqueued on the context's stream.  (The mapping networks: mapper.hip.)
 #include "context.h"
 
@@ -153,6 +153,46 @@ static int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k,
                              c->topv.as<float>(), c->topi.as<int>());
 }
 
+// ln_f over `R` rows of h (row stride ldh floats, starting at h0) then the plain lm_head GEMM over wte:
+// -> logits fp32 [R, ld]  (the full rows: capdec_gpt2_logits and the sampling decode; greedy / beam never materialise them)
+static int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float *logits, int ld) {
+    const Gpt2 &g = c->gpt;
+    const int d = g.d;
+    if (use_packed_a(c, d))   // same operand path as the decode loop's fused lm_head (bf16 mode: bf16 operands)
+        return ln_gemm_packed(c, h0, ldh, g.lnfw, g.lnfb, g.eps, g.wte, logits, ld, R, g.vocab, d, nullptr, CAPDEC_ACT_NONE);
+    CAPDEC_TRY(c->xl.ensure((size_t)R * d * 4));
+    { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, h0, ldh, g.lnfw, g.lnfb, g.eps, c->xl.as<float>(), d, R, d)); }
+    return gemm(c, c->xl.as<float>(), d, g.wte, d, logits, ld, R, g.vocab, d, nullptr, CAPDEC_ACT_NONE);
+}
+
+// The sampling decode's arguments (capdec_decode_sample); u / logp point at the chunk's first caption, cap_off is its
+// index within the call -- the Philox counter is (cap_off + caption, step) and nothing else, so a caption's draws do not
+// depend on the chunking, on the compaction or on the rest of the batch.
+struct SampleArgs {
+    float top_p;
+    uint64_t seed;
+    const float *u;     // [n, T] or nullptr (Philox)
+    float *logp;        // [n, T] or nullptr
+    int cap_off;
+};
+
+// One sampling step over `R` activation rows: lm_head_logits + the nucleus-sampling kernel, tune.sample_rows rows at a time
+// (the fp32 logits of 5000 rows of GPT-2's vocabulary are 1 GB).  Writes what lm_head_select + launch_greedy_step write.
+static int lm_head_sample(capdec_ctx *c, const float *h0, int ldh, int R, float inv_temp, const SampleArgs &a, int step,
+                          int T, int stop_id, int alt_stop_id, int *ids, int *lens, const int *cmap) {
+    const int V = c->gpt.vocab, ld = (V + 63) / 64 * 64, blk = std::min(R, std::max(1, c->tune.sample_rows));
+    CAPDEC_TRY(c->slogits.ensure((size_t)blk * ld * 4));
+    for (int r0 = 0; r0 < R; r0 += blk) {
+        const int nr = std::min(blk, R - r0);
+        CAPDEC_TRY(lm_head_logits(c, h0 + (size_t)r0 * ldh, ldh, nr, c->slogits.as<float>(), ld));
+        ProfScope ps(c, F_SELECT);
+        CAPDEC_TRY(launch_sample_top_p(c->stream, c->slogits.as<float>(), ld, nr, r0, V, inv_temp, a.top_p, a.seed, a.u, a.cap_off,
+                                       step, T, stop_id, alt_stop_id, ids, lens, c->done.as<uint8_t>(), c->next_tok.as<int>(),
+                                       c->alive.as<int>(), a.logp, cmap));
+    }
+    return 0;
+}
+
 // geometry only (the CLIP towers attend straight from the qkv activations and never touch a cache)
 void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd) {
     kv.rows = rows;
@@ -208,7 +248,8 @@ static int chunk_captions(capdec_ctx *c, int n, int beam, int ctx) {
 // ---------------------------------------------------------------------------- decode drivers
 static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int beam, bool greedy, int stop_id,
                         int alt_stop_id, int T, float temperature, int *ids, int *lens, float *scores, int *order,
-                        const int *forced = nullptr, float *stats = nullptr, int kv_stat_off = 0) {
+                        const int *forced = nullptr, float *stats = nullptr, int kv_stat_off = 0,
+                        const SampleArgs *smp = nullptr) {     // smp: the greedy loop with the arg-max replaced by a draw
     const Gpt2 &g = c->gpt;
     const int d = g.d;
     const int ctx = P + T - 1;
@@ -248,6 +289,7 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     } else {
         CAPDEC_HIP(hipMemsetAsync(ids, 0, (size_t)nc * T * 4, c->stream));
         CAPDEC_HIP(hipMemsetAsync(lens, 0, (size_t)nc * 4, c->stream));
+        if (smp && smp->logp) CAPDEC_HIP(hipMemsetAsync(smp->logp, 0, (size_t)nc * T * 4, c->stream));
     }
     CAPDEC_HIP(hipMemsetAsync(c->done.p, 0, (size_t)rows, c->stream));
     CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
@@ -260,8 +302,11 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     sp.P = P;
     sp.beam = beam;
     CAPDEC_TRY(gpt2_body(c, sp, kv));
-    CAPDEC_TRY(lm_head_select(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp));
-    if (greedy) {
+    if (!smp) CAPDEC_TRY(lm_head_select(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp));
+    if (smp) {
+        CAPDEC_TRY(lm_head_sample(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, inv_temp, *smp, 0, T, stop_id,
+                                  alt_stop_id, ids, lens, nullptr));
+    } else if (greedy) {
         ProfScope ps(c, F_SELECT);
         CAPDEC_TRY(launch_greedy_step(c->stream, c->topi.as<int>(), nc, 0, T, stop_id, alt_stop_id, ids, lens,
                                       c->done.as<uint8_t>(), c->next_tok.as<int>(), c->alive.as<int>(), nullptr, k, forced,
@@ -324,6 +369,10 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
         sd.anc_stride = ctx;
         sd.cmap = cmap;
         CAPDEC_TRY(gpt2_body(c, sd, kv));
+        if (smp) {
+            CAPDEC_TRY(lm_head_sample(c, c->h.as<float>(), d, arows, inv_temp, *smp, i, T, stop_id, alt_stop_id, ids, lens, cmap));
+            continue;
+        }
         CAPDEC_TRY(lm_head_select(c, c->h.as<float>(), d, arows, k, inv_temp));
         ProfScope ps(c, F_SELECT);
         if (greedy) {
@@ -344,7 +393,7 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
 
 static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int beam, bool greedy, int stop_id,
                          int alt_stop_id, int T, float temperature, int *ids, int *lens, float *scores,
-                         int *order, const int *forced = nullptr, float *stats = nullptr) {
+                         int *order, const int *forced = nullptr, float *stats = nullptr, const SampleArgs *smp = nullptr) {
     CAPDEC_CHECK(c && c->gpt.loaded, "decode: GPT-2 weights not loaded");
     CAPDEC_CHECK(n >= 0 && P >= 1 && T >= 1, "decode: bad sizes");
     CAPDEC_CHECK(P + T - 1 <= c->gpt.n_pos, "decode: prefix + entry_length exceeds n_positions");
@@ -354,6 +403,7 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int b
     CAPDEC_HIP(hipSetDevice(c->device));
     c->stat_steps = n > 0 ? 1 : 0;
     c->stat_compactions = 0;
+    c->stat_chunks = 0;
     c->stat_row_steps = 0;
     c->stat_step_rows.clear();
     c->stat_kv_slots = c->stat_kv_pos = 0.0;
@@ -366,6 +416,7 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int b
     }
     const int ctx = P + T - 1;
     const int chunk = chunk_captions(c, n, beam, ctx);
+    c->stat_chunks = (n + chunk - 1) / chunk;
     // lm_head second-pass bookkeeping ([count, total, rows...], lm_head_select): sized once for the largest step, total zeroed
     CAPDEC_TRY(c->lmflag.ensure(((size_t)std::min(chunk, n) * beam + 2) * 4));
     CAPDEC_HIP(hipMemsetAsync(c->lmflag.p, 0, 2 * sizeof(int), c->stream));
@@ -374,11 +425,15 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int b
     c->k3_rows = 0;
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int nc = std::min(chunk, n - c0);
+        SampleArgs sa;
+        if (smp) sa = SampleArgs{smp->top_p, smp->seed, smp->u ? smp->u + (size_t)c0 * T : nullptr,
+                                 smp->logp ? smp->logp + (size_t)c0 * T : nullptr, c0};
         CAPDEC_TRY(decode_chunk(c, prefix + (size_t)c0 * P * c->gpt.d, nc, P, beam, greedy, stop_id, alt_stop_id, T,
                                 temperature, ids + (size_t)c0 * beam * T, lens + (size_t)c0 * beam,
                                 scores ? scores + (size_t)c0 * beam : nullptr,
                                 order ? order + (size_t)c0 * beam : nullptr,
-                                forced ? forced + (size_t)c0 * T : nullptr, stats ? stats + (size_t)c0 * T * 3 : nullptr, c0));
+                                forced ? forced + (size_t)c0 * T : nullptr, stats ? stats + (size_t)c0 * T * 3 : nullptr, c0,
+                                smp ? &sa : nullptr));
     }
     CAPDEC_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -408,15 +463,9 @@ int capdec_gpt2_logits(capdec_ctx *c, const float *embeds, int n, int L, int all
     sp.beam = 1;
     CAPDEC_TRY(gpt2_body(c, sp, kv));
     const int R = all_positions ? n * L : n;
-    CAPDEC_TRY(c->xl.ensure((size_t)R * d * 4));
     const float *h0 = all_positions ? c->h.as<float>() : c->h.as<float>() + (size_t)(L - 1) * d;
     const int ldh = all_positions ? d : L * d;
-    if (use_packed_a(c, d))   // same operand path as the decode loop's fused lm_head (bf16 mode: bf16 operands)
-        return ln_gemm_packed(c, h0, ldh, g.lnfw, g.lnfb, g.eps, g.wte, logits, g.vocab, R, g.vocab, d, nullptr,
-                              CAPDEC_ACT_NONE);
-    { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, h0, ldh, g.lnfw, g.lnfb, g.eps, c->xl.as<float>(), d, R, d)); }
-    CAPDEC_TRY(gemm(c, c->xl.as<float>(), d, g.wte, d, logits, g.vocab, R, g.vocab, d, nullptr, CAPDEC_ACT_NONE));
-    return 0;
+    return lm_head_logits(c, h0, ldh, R, logits, g.vocab);
 }
 
 int capdec_cross_entropy(capdec_ctx *c, const float *logits, int ld, const int32_t *labels, int rows, int vocab,
@@ -456,6 +505,16 @@ int capdec_decode_greedy_forced(capdec_ctx *c, const float *prefix, int n, int P
     c->compact = compact;
     lens.release();
     return rc;
+}
+
+int capdec_decode_sample(capdec_ctx *c, const float *prefix, int n, int P, int stop_id, int alt_stop_id, int entry_length,
+                         float temperature, float top_p, uint64_t seed, const float *u, int32_t *ids, int32_t *lens,
+                         float *logp) {
+    CAPDEC_CHECK(top_p == top_p && temperature == temperature, "decode_sample: top_p or temperature is NaN");
+    CAPDEC_CHECK(c && (n == 0 || (prefix && ids && lens)), "decode_sample: null argument");
+    const SampleArgs smp{top_p, seed, u, logp, 0};
+    return decode_common(c, prefix, n, P, 1, true, stop_id, alt_stop_id, entry_length, temperature, ids, lens, nullptr,
+                         nullptr, nullptr, nullptr, &smp);
 }
 
 int capdec_decode_beam(capdec_ctx *c, const float *prefix, int n, int P, int beam, int stop_id, int entry_length,

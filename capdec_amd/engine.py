@@ -398,6 +398,31 @@ class Engine:
                                             int(entry_length), ids.data_ptr(), lens.data_ptr()), "capdec_decode_greedy")
         return ids, lens
 
+    def decode_sample(self, prefix_embed: torch.Tensor, stop_id: int, entry_length: int = 67, temperature: float = 1.0,
+                      top_p: float = 0.8, seed: int = 0, u: Optional[torch.Tensor] = None, alt_stop_id: int = 764,
+                      return_logp: bool = False):
+        """nucleus-sampling decode (capdec_decode_sample): -> ids [n, T] (zero padded), lens [n] (including the stop
+        token) and, with ``return_logp``, logp [n, T] of the chosen tokens under the unfiltered temperature-scaled
+        distribution.  ``u`` [n, T] in [0, 1) injects the uniforms; None draws them from the device Philox keyed by
+        (``seed``, caption index, step)"""
+        top_p, temperature = float(top_p), float(temperature)
+        if top_p != top_p or temperature != temperature:
+            raise CapdecError("decode_sample: top_p or temperature is NaN")
+        n, P = int(prefix_embed.shape[0]), int(prefix_embed.shape[1])
+        if u is not None and tuple(u.shape) != (n, int(entry_length)):
+            raise CapdecError(f"decode_sample: u must be [n, entry_length] = ({n}, {int(entry_length)}), got {tuple(u.shape)}")
+        p = self._dev(prefix_embed)
+        uu = self._dev(u) if u is not None else None
+        ids = torch.empty(n, entry_length, device=self.device, dtype=torch.int32)
+        lens = torch.empty(n, device=self.device, dtype=torch.int32)
+        logp = torch.empty(n, entry_length, device=self.device, dtype=torch.float32) if return_logp else None
+        self._sync_stream()
+        self._chk(self.lib.capdec_decode_sample(self._h, p.data_ptr(), n, P, int(stop_id), int(alt_stop_id), int(entry_length),
+                                                temperature, top_p, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                uu.data_ptr() if uu is not None else None, ids.data_ptr(), lens.data_ptr(),
+                                                logp.data_ptr() if logp is not None else None), "capdec_decode_sample")
+        return (ids, lens, logp) if return_logp else (ids, lens)
+
     def decode_greedy_forced(self, prefix_embed: torch.Tensor, forced_ids: torch.Tensor):
         """teacher-forced greedy decode: feeds ``forced_ids`` [n, T] and returns (arg-max ids [n, T], stats [n, T, 3] =
         (top-1 logit, top-2 logit, logsumexp) of every step)"""
@@ -521,6 +546,12 @@ class Engine:
         buf, n = (C.c_int * 1024)(), C.c_int(0)
         self._chk(self.lib.capdec_decode_step_rows(self._h, buf, 1024, C.byref(n)), "decode_step_rows")
         return [int(buf[i]) for i in range(min(n.value, 1024))]
+
+    def decode_chunks(self) -> int:
+        """how many chunks the KV budget split the captions of the last decode call into (capdec_decode_chunks)"""
+        n = C.c_int(0)
+        self._chk(self.lib.capdec_decode_chunks(self._h, C.byref(n)), "decode_chunks")
+        return n.value
 
     def decode_counters(self) -> Dict[str, float]:
         """kv_slots_per_position: mean number of distinct K/V slots a (caption, position) of the last beam decode read

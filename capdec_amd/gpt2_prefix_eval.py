@@ -2,7 +2,9 @@
 ``generate2`` (:118-198) with the reference signatures, plus batched variants
 (``embed`` [N, P, 768]) that the throughput path uses.  The per-token Python loop, the
 no-cache re-forward and the per-token host syncs of the reference are replaced by one call
-into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``)."""
+into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``).  ``generate_samples`` /
+``generate_samples_batch`` make ``top_p``, ``temperature`` and ``entry_count`` live: nucleus sampling
+(``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178)."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -12,6 +14,7 @@ import torch
 
 from ._capi import CapdecError
 from .gpt2_prefix import ClipCaptionModel
+from .train import _next_seed
 
 ALT_STOP_ID = 764   # hard-coded second stop id of generate2 (reference gpt2_prefix_eval.py:187)
 
@@ -40,6 +43,33 @@ def decode_beam_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_ind
     """embed [N, P, d] -> (ids [N, beam, T], lens [N, beam], scores [N, beam], order [N, beam]),
     beams sorted by mean log-prob descending (the order generate_beam returns)."""
     return model.engine.decode_beam(embed, stop_token_index, beam_size, entry_length, temperature)
+
+
+def sample_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, entry_length: int = 67,
+               top_p: float = 0.8, temperature: float = 1., seed: Optional[int] = None, u: Optional[torch.Tensor] = None,
+               alt_stop_id: int = ALT_STOP_ID, return_logp: bool = False):
+    """embed [N, P, d] -> ids int32 [N, entry_length] (zero padded), lens int32 [N] (including the stop token), drawn
+    by nucleus sampling: one uniform per (caption, step), from ``u`` [N, entry_length] or from the device Philox keyed by
+    (``seed``, caption index, step); ``seed=None`` takes the process's next key
+    (``train._next_seed``: torch's global seed and the number of keys drawn so far), so successive calls differ and a
+    program that seeds torch and makes the same calls in the same order repeats its captions."""
+    return model.engine.decode_sample(embed, stop_token_index, entry_length, temperature, top_p,
+                                      _next_seed() if seed is None else seed, u, alt_stop_id, return_logp)
+
+
+def generate_samples_batch(model, tokenizer, embed: torch.Tensor, entry_count: int = 1, entry_length: int = 67,
+                           top_p: float = 0.8, temperature: float = 1., stop_token: str = '.',
+                           seed: Optional[int] = None) -> List[List[str]]:
+    """embed [N, P, d] -> ``entry_count`` sampled texts per caption.  Every prefix row is repeated ``entry_count``
+    times; each repeat is a caption index of its own (caption r, entry e -> index r * entry_count + e) and so has its
+    own draws."""
+    if entry_count < 1:
+        raise CapdecError("generate_samples_batch: entry_count must be >= 1")
+    stop = tokenizer.encode(stop_token)[0]
+    ids, lens = sample_ids(model, embed.repeat_interleave(entry_count, dim=0), stop, entry_length, top_p, temperature, seed)
+    ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+    return [[tokenizer.decode(list(ids[r * entry_count + e, :lens[r * entry_count + e]])) for e in range(entry_count)]
+            for r in range(embed.shape[0])]
 
 
 def generate2_batch(model, tokenizer, embed: torch.Tensor, entry_length: int = 67, stop_token: str = '.') -> List[str]:
@@ -82,7 +112,8 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
               top_p=0.8, temperature=1., stop_token: str = '.'):
     """reference gpt2_prefix_eval.py:118-198 -> str.  ``top_p`` is accepted and has no effect,
     exactly as in the reference: the filter never removes the arg-max (:172), and the next
-    token is ``argmax`` (:177); ``temperature`` > 0 does not change an arg-max either."""
+    token is ``argmax`` (:177); ``temperature`` > 0 does not change an arg-max either.  ``generate_samples`` /
+    ``generate_samples_batch`` are the entry points where the three parameters act."""
     model.eval()
     prefix, prompt_ids = _prefix_from(model, tokenizer, tokens, prompt, embed)
     if prefix.shape[0] != 1:
@@ -98,3 +129,19 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
         # first token stops -- and raises; keep the error behaviour
         raise TypeError("iteration over a 0-d array")
     return tokenizer.decode(out)
+
+
+def generate_samples(model, tokenizer, tokens=None, prompt=None, embed=None, entry_count=1, entry_length=67,
+                     top_p=0.8, temperature=1., stop_token: str = '.', seed: Optional[int] = None) -> List[str]:
+    """``generate2``'s signature plus ``seed`` -> ``entry_count`` texts drawn by nucleus sampling from one caption
+    ([1, P, d]); prompt tokens stay in front of every text, as in ``generate2``."""
+    model.eval()
+    prefix, prompt_ids = _prefix_from(model, tokenizer, tokens, prompt, embed)
+    if prefix.shape[0] != 1:
+        raise CapdecError("generate_samples takes one caption ([1, P, d]); use generate_samples_batch for [N, P, d]")
+    if entry_count < 1:
+        raise CapdecError("generate_samples: entry_count must be >= 1")
+    stop = tokenizer.encode(stop_token)[0]
+    ids, lens = sample_ids(model, prefix.repeat_interleave(entry_count, dim=0), stop, entry_length, top_p, temperature, seed)
+    ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+    return [tokenizer.decode((prompt_ids or []) + [int(t) for t in ids[e, :lens[e]]]) for e in range(entry_count)]

@@ -21,8 +21,9 @@ _seed_counter = [0]
 
 
 def _next_seed() -> int:
-    """a fresh Philox key per call, derived from torch's global seed so that
-    ``torch.manual_seed`` makes runs repeatable"""
+    """a fresh Philox key per call: a function of torch's global seed and of how many keys this process has drawn so far
+    (the noise injection, the dropouts and the sampling decode share the count).  A run that seeds torch and makes the
+    same calls in the same order repeats; ``torch.manual_seed`` does not rewind the count."""
     _seed_counter[0] += 1
     return (torch.initial_seed() * 1000003 + _seed_counter[0]) & 0xFFFFFFFFFFFFFFFF
 

@@ -32,6 +32,8 @@ extern "C" {
 #endif
 
 #define CAPDEC_ABI_VERSION 6   /* 6: capdec_load_mapper_encdec (MappingType.TransformerDecoder, inference only);
+                                     (capdec_decode_sample was added WITHOUT a new number: the addition changes no existing
+                                     symbol, and a library built from older sources is refused through capdec_build_id)
                                   5: capdec_set_compact, capdec_decode_step_rows (the workload in which captions stop);
                                   4: train step -- GPT-2's dropouts (capdec_train_set_dropout / _masks), capdec_train_loss, loss == NULL
                                      enqueues without waiting, the scope survives capdec_train_reset;
@@ -353,6 +355,25 @@ int capdec_decode_greedy_forced(capdec_ctx *ctx, const float *d_prefix, int n, i
 int capdec_decode_beam(capdec_ctx *ctx, const float *d_prefix, int n, int P, int beam, int stop_id,
                        int entry_length, float temperature, int32_t *d_ids, int32_t *d_lens,
                        float *d_scores, int32_t *d_order);
+/* Nucleus-sampling decode: the greedy loop with the arg-max replaced by one draw per step.  For a row of logits l, with
+ * s = l / (temperature > 0 ? temperature : 1) and p = softmax(s): token j is in the nucleus iff it is the arg-max or the
+ * sum of p[i] over all p[i] > p[j] is <= top_p (the filter of reference gpt2_prefix_eval.py:166-175; exactly equal
+ * probabilities are treated alike); q = p restricted to the nucleus and renormalised; the token is the first j in ascending
+ * id order whose running sum of q exceeds the step's uniform (the last nucleus token if rounding leaves the total below it).
+ * top_p <= 0 keeps the arg-max only (= capdec_decode_greedy), top_p >= 1 is plain multinomial sampling.
+ * Uniforms: d_u [n, entry_length] in [0, 1) (the convention of capdec_noise_inject's d_noise / d_u), or, when d_u is NULL,
+ * the device Philox4x32-10 keyed by (seed, caption index within the call, step) and nothing else: a caption's draws do
+ * not depend on the KV budget's chunking, on finished-caption compaction or on the other captions of the batch.
+ * d_ids / d_lens as for capdec_decode_greedy (rows stop at stop_id or alt_stop_id; zero padded; lens include the stop
+ * token); d_logp (may be NULL) [n, entry_length]: log-probability of each chosen token under the unfiltered,
+ * temperature-scaled distribution, 0 after the stop.  Limits and errors as for greedy; a NaN top_p or temperature is an
+ * error.  Each step materialises the fp32 logits of at most CAPDEC_SAMPLE_ROWS rows (default 2048) at a time. */
+int capdec_decode_sample(capdec_ctx *ctx, const float *d_prefix, int n, int P, int stop_id, int alt_stop_id,
+                         int entry_length, float temperature, float top_p, uint64_t seed,
+                         const float *d_u,      /* [n, entry_length] or NULL */
+                         int32_t *d_ids,        /* [n, entry_length] */
+                         int32_t *d_lens,       /* [n] */
+                         float *d_logp);        /* [n, entry_length] or NULL */
 /* Image preprocessing in front of capdec_clip_encode_image: the `preprocess` transform clip.load returns
  * (reference predictions_runner.py:212, embeddings_generator.py:72) = Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
  * ToTensor -> Normalize(mean, std); stretch != 0 = clip_transform_full (predictions_runner.py:116-122): Resize((n_px,
@@ -374,6 +395,9 @@ int capdec_set_compact(capdec_ctx *ctx, int on);
  * prefill); *n = how many steps there were (<= entry_length - 1).  At most `cap` entries are written.  With compaction the
  * sequence steps down at the poll points (every 8 steps) as captions finish; without it it is constant. */
 int capdec_decode_step_rows(capdec_ctx *ctx, int *rows, int cap, int *n);
+/* *chunks = how many chunks the KV budget (capdec_set_kv_budget, clamped to the free device memory) split the captions of
+ * the last decode call into; 0 for an empty call.  (Added with capdec_decode_sample, again without a new ABI number.) */
+int capdec_decode_chunks(capdec_ctx *ctx, int *chunks);
 /* kv_slots_per_position: over the last capdec_decode_beam call, the mean number of DISTINCT K/V cache slots one
  * (caption, position) of the decode attention read (1.0 = all beams of a caption share their whole history, `beam` =
  * none of it): the decode attention loads each distinct slot once, so its HBM traffic -- and its roofline -- scale with
