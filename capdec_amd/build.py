@@ -13,9 +13,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libcapdec_hip.so")
 SOURCES = ["capi_context.hip", "weights.hip", "gemm_dispatch.hip", "decode.hip", "mapper.hip", "train_step.hip", "train_mapper.hip", "train_ops.hip", "train_optim.hip", "clip.hip", "comm.hip", "gemm_f32.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_h2w.hip", "gemm_pp.hip", "elementwise.hip", "attention.hip", "resnet.hip", "select.hip", "sample.hip", "preprocess.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "config.h"), os.path.join(CSRC, "context.h"), os.path.join(CSRC, "train.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "gemm_epilogue_w.h"), os.path.join(CSRC, "gemm_epilogue_lds.h"), os.path.join(CSRC, "bf16x3.h"), os.path.join(os.path.dirname(HERE), "include", "capdec.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
-# measurement variant (-DCAPDEC_MEASURE: ablations that compute wrong results on purpose, ring-depth / occupancy overrides,
-# per-block phase stamps, the diverged-beam hook): tools/ and bench.py's untimed tail load it explicitly; the product path
-# (capdec_amd._capi.load_library()) never does
+# measurement variant: the product objects plus capi_context.hip compiled with -DCAPDEC_MEASURE, which adds ONE exported
+# function, the diverged-beam hook capdec_set_debug_diverge.  bench.py's untimed tail and one parity test load it explicitly;
+# the product path (capdec_amd._capi.load_library()) never does
+MEASURE_SRC = "capi_context.hip"
 MEASURE_LIB_PATH = os.path.join(LIB_DIR, "libcapdec_hip_measure.so")
 
 
@@ -48,9 +49,13 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True, measure: bool = False) -> str:
     """Compile every .hip translation unit to an object, link the shared library.
-    Incremental: only stale objects are rebuilt.  measure=True builds libcapdec_hip_measure.so (-DCAPDEC_MEASURE)."""
+    Incremental: only stale objects are rebuilt.  measure=True builds libcapdec_hip_measure.so: the product objects (stale
+    ones are rebuilt first) with MEASURE_SRC alone compiled a second time, with -DCAPDEC_MEASURE."""
+    if measure:
+        build(force=False, verbose=verbose)
     os.makedirs(LIB_DIR, exist_ok=True)
-    obj_dir = os.path.join(LIB_DIR, "obj_measure" if measure else "obj")
+    prod_dir = os.path.join(LIB_DIR, "obj")
+    obj_dir = os.path.join(LIB_DIR, "obj_measure") if measure else prod_dir
     lib_path = MEASURE_LIB_PATH if measure else LIB_PATH
     flags = FLAGS + (["-DCAPDEC_MEASURE"] if measure else [])
     os.makedirs(obj_dir, exist_ok=True)
@@ -61,9 +66,10 @@ def build(force: bool = False, verbose: bool = True, measure: bool = False) -> s
     id_changed = not os.path.exists(id_file) or open(id_file).read().strip() != build_id
     for src in SOURCES:
         sp = os.path.join(CSRC, src)
-        op = os.path.join(obj_dir, src.replace(".hip", ".o"))
+        mine = not measure or src == MEASURE_SRC
+        op = os.path.join(obj_dir if mine else prod_dir, src.replace(".hip", ".o"))
         objs.append(op)
-        if force or _stale(op, [sp] + HEADERS) or (src == "capi_context.hip" and id_changed):
+        if mine and (force or _stale(op, [sp] + HEADERS) or (src == "capi_context.hip" and id_changed)):
             cmd = [hipcc, *flags, "-c", sp, "-o", op]
             if src == "capi_context.hip":
                 cmd.insert(-4, f'-DCAPDEC_BUILD_ID="{build_id}"')

@@ -158,13 +158,9 @@ __global__ __launch_bounds__(256, OCC) void attn_decode_beams_kernel(const float
     // slot table visible: the table (and the DMA ring) are PRIVATE to the wavefront and a wavefront's LDS operations
     // complete in order, so a wavefront-scope fence is all the ordering needed -- a block barrier would make every
     // wavefront wait for the slowest of four unrelated (caption, head) pairs' first loads
-    if (ring_off < 0) {                                            // (CAPDEC_ATT_WSYNC=0: the round-2 block barrier, for A/B)
-        __syncthreads();
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const KV *kbase = kc + ((size_t)srow0 * heads + head) * hstride + sub * 4;
     const KV *vbase = vc + ((size_t)srow0 * heads + head) * hstride + sub * 4;
     const int slot_stride = heads * ctx * 64;      // offsets inside one caption's K / V region fit 32 bits (<= 8 x 16 x 256 x 64)
@@ -739,11 +735,9 @@ static int attn_decode_typed(hipStream_t st, const float *qkv, const KvCache &c,
     KV *kl = c.kp<KV>(layer), *vl = c.vp<KV>(layer);
     // positions known to sit in slot 0 whatever the table says: the whole history for greedy rows, the CLIP prefix for
     // beams (c.prefix_len; 0 = unknown)
-    const Tuning &tn = c.tune ? *c.tune : default_tuning();     // (the overrides below exist in measurement builds only)
-    const int pre_on = tn.att_preload;
-    const int npre = !pre_on ? 0 : (anc == nullptr ? L : c.prefix_len);
+    const int npre = anc == nullptr ? L : c.prefix_len;
     // (Round 5 tried a kernel of its own for greedy rows on the bf16 cache -- eight lanes per key, 16-byte loads, the K / V
-    //  of the whole history requested before the first use -- and CAPDEC_ATT_NA=4 here: 157 / 143 us against 150 / 141 us per
+    //  of the whole history requested before the first use -- and four positions per group here: 157 / 143 us against 150 / 141 us per
     //  launch at 5000 captions.  That launch is not latency-bound: 5.5 KB runs at a 9.7 KB stride read at 4.4 TB/s whatever
     //  the structure (profiles/r5_att_greedy_b16_ab.txt).)
     {
@@ -751,20 +745,16 @@ static int attn_decode_typed(hipStream_t st, const float *qkv, const KvCache &c,
         if (total <= 0) return 0;
         size_t lds = ((size_t)4 * beam * L * sizeof(int) + 1023) & ~(size_t)1023;   // ancestor slots (the DMA ring, if any, follows)
         CAPDEC_CHECK(lds + 32 * 1024 <= 160 * 1024, "attention: context too long for the slot table in LDS");
-        const int wsync = tn.att_wsync;
-        const int dma_on = tn.att_dma && wsync;
         dim3 grid((total + 3) / 4), block(256);
-        // waves per SIMD the register allocation is sized for: beam <= 4 fits 4 without spilling; beam 5 needs 124
-        // registers at 4 waves; CAPDEC_ATT_OCC=3 / CAPDEC_ATT_NA=4 are measurement knobs (default = measured best)
-        const int occ5 = tn.att_occ == 3 ? 3 : 4;
+        // OCC = waves per SIMD the register allocation is sized for: beam <= 4 fits 4 without spilling; beam 5 needs 124
+        // registers at 4 waves (measured best)
         // positions per group in flight (NA): 2 when the launch is HBM-bound (5000 captions: 0.429 vs 0.435 ms), 4 when
-        // fewer than two rounds of wavefronts make it latency-bound (625 captions: 66.6 vs 68.7 us); CAPDEC_ATT_NA forces
-        const int na_env = tn.att_na;
-        const int na4 = na_env ? (na_env == 4) : (!c.fixed_variant && total <= 16384);
+        // fewer than two rounds of wavefronts make it latency-bound (625 captions: 66.6 vs 68.7 us)
+        const bool na4 = !c.fixed_variant && total <= 16384;
 #define LAUNCH_BEAMS_V(B, OCC, NAV, CURV)                                                                       \
     ATT_BIG_LDS((attn_decode_beams_kernel<B, KV, OCC, NAV, CURV, false>), lds);                                    \
     hipLaunchKernelGGL((attn_decode_beams_kernel<B, KV, OCC, NAV, CURV, false>), grid, block, lds, st, qkv, kl, vl, total, \
-                       c.heads, c.ctx, c.heads * c.hd, L, anc, anc_stride, out, (char *)packed_out, cmap, fmt, npre, wsync ? 0 : -1)
+                       c.heads, c.ctx, c.heads * c.hd, L, anc, anc_stride, out, (char *)packed_out, cmap, fmt, npre, 0)
     // (LDS-DMA variant: NA = 2 for every launch size -- with its double buffer 16 positions per group are in flight, what
     //  NA = 4 gives the register-landed loop, and 38 KB of LDS per block still lets four blocks share a CU)
 #define LAUNCH_BEAMS_DMA(B, OCC)                                                                                \
@@ -772,24 +762,31 @@ static int attn_decode_typed(hipStream_t st, const float *qkv, const KvCache &c,
     hipLaunchKernelGGL((attn_decode_beams_kernel<B, float, OCC, 2, true, true>), grid, block, lds + 4 * 2 * (2 * 2 * 1024), st, \
                        qkv, (float *)kl, (float *)vl, total, c.heads, c.ctx, c.heads * c.hd, L, anc, anc_stride, out,  \
                        (char *)packed_out, cmap, fmt, npre, (int)lds)
+    // (if constexpr: only the forms a launch can reach are compiled -- NA = 4 up to beam 5; CUR for the widths the decode
+    //  drivers use most, greedy and beam 5, where the fp32 cache always takes the LDS-DMA form, laid out for fp32 keys)
+#define LAUNCH_BEAMS_NA(B, OCC, CURV)                                                                           \
+    if constexpr (B <= 5) {                                                                                     \
+        if (na4) { LAUNCH_BEAMS_V(B, OCC, 4, CURV); } else { LAUNCH_BEAMS_V(B, OCC, 2, CURV); }                 \
+    } else { LAUNCH_BEAMS_V(B, OCC, 2, CURV); }
 #define LAUNCH_BEAMS(B, OCC)                                                                                    \
-    if (cur_cached && (B == 1 || B == 5)) {       /* (the widths the decode drivers use most: greedy and beam 5) */ \
-        if (dma_on && sizeof(KV) == 4) { LAUNCH_BEAMS_DMA(B, OCC); }    /* (the LDS-DMA ring is laid out for fp32 keys) */  \
-        else if (na4) { LAUNCH_BEAMS_V(B, OCC, 4, true); } else { LAUNCH_BEAMS_V(B, OCC, 2, true); }             \
-    } else if (na4 && B <= 5) { LAUNCH_BEAMS_V(B, OCC, 4, false); }                                             \
-    else { LAUNCH_BEAMS_V(B, OCC, 2, false); }
+    if constexpr (B == 1 || B == 5) {                                                                           \
+        if (!cur_cached) { LAUNCH_BEAMS_NA(B, OCC, false) }                                                     \
+        else if constexpr (sizeof(KV) == 4) { LAUNCH_BEAMS_DMA(B, OCC); }                                       \
+        else { LAUNCH_BEAMS_NA(B, OCC, true) }                                                                  \
+    } else { LAUNCH_BEAMS_NA(B, OCC, false) }
         switch (beam) {
             case 1: LAUNCH_BEAMS(1, 4); break;      // greedy: the same single-pass kernel with one row per caption
             case 2: LAUNCH_BEAMS(2, 4); break;
             case 3: LAUNCH_BEAMS(3, 4); break;
             case 4: LAUNCH_BEAMS(4, 4); break;
-            case 5: if (occ5 == 3) { LAUNCH_BEAMS(5, 3); } else { LAUNCH_BEAMS(5, 4); } break;
+            case 5: LAUNCH_BEAMS(5, 4); break;
             case 6: LAUNCH_BEAMS(6, 2); break;
             case 7: LAUNCH_BEAMS(7, 2); break;
             case 8: LAUNCH_BEAMS(8, 2); break;
             default: CAPDEC_CHECK(false, "attention: beam must be in 1..8");
         }
 #undef LAUNCH_BEAMS
+#undef LAUNCH_BEAMS_NA
 #undef LAUNCH_BEAMS_DMA
 #undef LAUNCH_BEAMS_V
         CAPDEC_HIP(hipGetLastError());
@@ -982,14 +979,13 @@ size_t attn_cross_lds_bytes(int nq, int nkv, int hd, int group) {
 }
 
 int launch_attn_cross(hipStream_t st, const float *q, int ldq, size_t q_cap_stride, const float *k, const float *v,
-                      int ldkv, float *out, int n, int nq, int nkv, int heads, int hd, int group) {
+                      int ldkv, float *out, int n, int nq, int nkv, int heads, int hd) {
     CAPDEC_CHECK(nq >= 1 && nkv >= 1 && heads >= 1 && hd >= 1 && ldq >= heads * hd && ldkv >= heads * hd,
                  "cross attention: bad geometry");
-    CAPDEC_CHECK(group == 0 || group == 1 || group == 2 || group == 4, "cross attention: group must be 0 (auto), 1, 2 or 4");
     CAPDEC_CHECK(attn_cross_lds_bytes(nq, nkv, hd, 1) <= 160 * 1024, "cross attention: too many rows for LDS");
     if (n <= 0) return 0;
     // units per block: measured in DESIGN.md (ATTN_CROSS_GROUP_LDS: two units while six such blocks fit a CU's 160 KB)
-    if (group == 0) group = attn_cross_lds_bytes(nq, nkv, hd, 2) <= ATTN_CROSS_GROUP_LDS ? 2 : 1;
+    const int group = attn_cross_lds_bytes(nq, nkv, hd, 2) <= ATTN_CROSS_GROUP_LDS ? 2 : 1;
     const size_t lds = attn_cross_lds_bytes(nq, nkv, hd, group);
     CAPDEC_CHECK(lds <= 160 * 1024, "cross attention: too many rows for LDS");
     if (lds > 64 * 1024)

@@ -66,16 +66,12 @@ bool tuning_from_env(Tuning *t, std::string *err) {
     env_int("CAPDEC_H2_PERSIST", &t->h2_persist);
     if (env_int("CAPDEC_H2W", &t->h2w)) {
         const int v = t->h2w;
-        bool ok = v == 0 || v == 1 || v == 2 || v == 8 || v == 10 || v == 14;
-#ifdef CAPDEC_MEASURE
-        ok = ok || v == 3 || v == 6 || v == 12;
-#endif
-        if (!ok) {
+        if (!(v == 0 || v == 1 || v == 2 || v == 8 || v == 10 || v == 14)) {
             *err = "create: CAPDEC_H2W=" + std::to_string(v) + " is not a geometry of this build (0, 1, 2, 8, 10, 14)";
             return false;
         }
     }
-    env_int("CAPDEC_PP", &t->pp);
+    env_flag("CAPDEC_PP", &t->pp);
     env_flag("CAPDEC_LMHEAD_WIDE", &t->lmhead_wide);
     env_flag("CAPDEC_TRAIN_F16X2", &t->train_f16x2);
     env_flag("CAPDEC_TRAIN_ATTN_BLK", &t->train_attn_blk);
@@ -92,25 +88,6 @@ bool tuning_from_env(Tuning *t, std::string *err) {
     t->hook_packa = getenv("CAPDEC_HOOK_PACKA") != nullptr;
     t->hook_cache = getenv("CAPDEC_HOOK_CACHE") != nullptr;
     if (const char *e = getenv("CAPDEC_RCCL_LIB")) t->rccl_lib = e;
-#ifdef CAPDEC_MEASURE
-    int v;
-    if (env_int("CAPDEC_H2_NS", &v) && (v == 3 || v == 5)) t->h2_ns = v;
-    env_int("CAPDEC_H2_ABL", &t->h2_abl);
-    if (env_int("CAPDEC_X1_NS", &v) && v == 4) t->x1_ns = 4;
-    env_int("CAPDEC_ABL_DMA", &t->x3_abl_dma);
-    env_int("CAPDEC_X3_TILE_M", &t->x3_tile_m);
-    env_int("CAPDEC_GEMM_BK", &t->f32_bk);
-    env_int("CAPDEC_LMHEAD_BK", &t->f32_lmhead_bk);
-    env_int("CAPDEC_ATT_PRELOAD", &t->att_preload);
-    env_int("CAPDEC_ATT_WSYNC", &t->att_wsync);
-    env_int("CAPDEC_ATT_DMA", &t->att_dma);
-    if (env_int("CAPDEC_ATT_OCC", &v) && v == 3) t->att_occ = 3;
-    env_int("CAPDEC_ATT_NA", &t->att_na);
-    env_int("CAPDEC_PP_ABL", &t->pp_abl);
-    if (const char *e = getenv("CAPDEC_PP_STAMPS")) t->pp_stamps = e;
-    env_int("CAPDEC_LMHEAD_K1", &t->lmhead_k1);
-    if (env_int("CAPDEC_ED_ATTN_GROUP", &v) && (v == 1 || v == 2 || v == 4)) t->ed_attn_group = v;
-#endif
     return true;
 }
 
@@ -223,7 +200,7 @@ int capdec_set_batch_invariant(capdec_ctx *c, int on) {
     return 0;
 }
 #ifdef CAPDEC_MEASURE
-int capdec_set_debug_diverge(capdec_ctx *c, int on) {      // measurement builds only (include/capdec.h)
+int capdec_set_debug_diverge(capdec_ctx *c, int on) {      // the ONE difference of a measurement build (include/capdec.h)
     CAPDEC_CHECK(c, "null context");
     c->diverge = on != 0;
     return 0;

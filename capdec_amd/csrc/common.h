@@ -165,7 +165,7 @@ int launch_gemm_f32(hipStream_t st, const float *A, int lda, const float *Bt, in
 // lm_head: logits tile never leaves the CU; per (row, 128-column tile) emits max, sum exp(x - max)
 // and the top-k (value, column) pairs.
 int launch_gemm_f32_topk(hipStream_t st, const float *A, int lda, const float *Bt, int ldb, int M, int N, int K,
-                         int k, float inv_temp, const TopkOut &o, const Tuning *tune = nullptr);
+                         int k, float inv_temp, const TopkOut &o);
 inline int gemm_tiles_n(int N) { return (N + GEMM_BN - 1) / GEMM_BN; }
 
 // gemm_bf16x3.hip: the same two GEMMs on the bf16 matrix cores with operands split into three bf16
@@ -200,19 +200,19 @@ int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked,
 int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
                             float inv_temp, const TopkOut &o);
 // round-3 wide-tile kernels with ONE accumulator set (gemm_h2w.hip); scale = 2^(t - 11), t = pack-time pre-scale
-// exponent of the weights; `which`: 2 = 256x128 (two blocks per CU), 3 = 256x256 (8 waves), 6 = 256x256 (4 waves), 8 = 128x192
+// exponent of the weights; `which`: 2 = 256x128, 8 = 128x192 (two blocks per CU)
 int h2w_plan(int M, int N, int K);
 int launch_absmax_bits(hipStream_t st, const float *w, size_t n, unsigned *d_out);
 int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
                     int K, const GemmEpilogue &epi, float scale);
 int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                         float inv_temp, const TopkOut &o, const Tuning *tune = nullptr);
+                         float inv_temp, const TopkOut &o);
 // round-4 ping-pong kernels (gemm_pp.hip): ONE 8-wavefront block per CU, the two wavefronts of a SIMD alternate between a
-// load phase and a matrix phase; `which`: 10 = 256x128 (two accumulator sets), 11 = 256x128, 12 = 256x256, 13 = 128x256 (one set)
+// load phase and a matrix phase; `which`: 10 = 256x128 (two accumulator sets), 14 = 256x192 (one set)
 int launch_gemm_pp(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
                    int K, const GemmEpilogue &epi, float scale);
-// planner: 0 = keep the kernels of rounds 2-3, else a ping-pong geometry (10 = 256x128, 14 = 256x192, 12 = 256x256)
-int pp_plan(int M, int N, int K, bool wide_ok, bool can_split, int mode = 2);
+// planner: 0 = keep the kernels of rounds 2-3, else a ping-pong geometry (10 = 256x128, 14 = 256x192)
+int pp_plan(int M, int N, int K, bool wide_ok, bool can_split);
 size_t pp_splitk_ws_bytes(int which, int M, int N, int K);
 // exact second pass of the fused lm_head (decode.hip): k = 5 lists for the *m_dev rows of a compacted packed A operand
 int launch_gemm_h2w_topk_dev(hipStream_t st, const void *Apacked, const void *Bpacked, const int *m_dev, int N, int K,
@@ -284,7 +284,6 @@ struct KvCache {
     bool bf16 = false;
     int prefix_len = 0;           // decode: positions [0, prefix_len) of every row live in slot 0 (the CLIP prefix)
     bool fixed_variant = false;   // batch-invariant mode: the launch-size dependent kernel variants are pinned
-    const Tuning *tune = nullptr; // the context's environment knobs (measurement builds read the attention overrides)
     size_t layer_stride() const { return (size_t)rows * heads * ctx * hd; }      // elements
     size_t elem_bytes() const { return bf16 ? 2 : 4; }
     template <typename T> T *kp(int layer) const { return reinterpret_cast<T *>(k) + (size_t)layer * layer_stride(); }
@@ -312,11 +311,11 @@ int launch_attn_mapper(hipStream_t st, const float *q, int ldq, const float *k, 
                        int n, int seq, int heads, int hd);
 // Encoder-decoder mapper: nq query rows per caption attend to nkv key / value rows from pointers of their own (row
 // strides ldq / ldkv; q_cap_stride = elements between two captions' query blocks, 0 = one block shared by all), out
-// [n, nq, heads * hd].  group = (caption, head) units per block: 1, 2, 4, or 0 = chosen from the LDS need.
+// [n, nq, heads * hd].  A block serves two (caption, head) units while their LDS need stays below ATTN_CROSS_GROUP_LDS.
 constexpr size_t ATTN_CROSS_GROUP_LDS = 26 * 1024;
 size_t attn_cross_lds_bytes(int nq, int nkv, int hd, int group);
 int launch_attn_cross(hipStream_t st, const float *q, int ldq, size_t q_cap_stride, const float *k, const float *v,
-                      int ldkv, float *out, int n, int nq, int nkv, int heads, int hd, int group = 0);
+                      int ldkv, float *out, int n, int nq, int nkv, int heads, int hd);
 
 // select.hip
 int launch_topk_merge(hipStream_t st, const float *tile_max, const float *tile_sum, const float *cand_val,

@@ -1,21 +1,24 @@
 // Every environment knob of libcapdec_hip.so in ONE place.  capdec_create parses the environment once into the context's
 // Tuning (capi_context.hip: tuning_from_env); the launchers of the other translation units receive a pointer to it through
-// GemmEpilogue::tune / KvCache::tune / their arguments -- no translation unit reads the environment on its own, nothing
+// GemmEpilogue::tune / their arguments -- no translation unit reads the environment on its own, nothing
 // is latched in function-local statics, and two contexts created under different environments behave differently, as
 // the tests that monkeypatch the environment expect.
 //
-// PRODUCT knobs select among correct code paths (A/B switches kept for regression hunting; every default is the
-// measured-fastest setting, none is needed for normal use).  MEASUREMENT knobs exist only in builds with -DCAPDEC_MEASURE
-// (capdec_amd/lib/libcapdec_hip_measure.so, used by tools/ and by bench.py's untimed tail): ablations that produce wrong
-// results on purpose, ring-depth / occupancy overrides, per-block phase stamps, the diverged-beam hook.  The shipped
-// library contains none of that code.
+// Every knob selects among correct code paths (A/B switches kept for regression hunting; every default is the
+// measured-fastest setting, none is needed for normal use).  There are no measurement knobs: the ablations, ring-depth /
+// occupancy overrides, extra tile geometries and phase stamps of rounds 2-6 gave their figures (profiles/, docs/rounds.md)
+// and are gone together with every kernel variant only they reached.  The measurement library
+// (capdec_amd/lib/libcapdec_hip_measure.so, used by bench.py's untimed tail and one parity test) is this library plus ONE
+// exported function, capdec_set_debug_diverge (capi_context.hip, compiled a second time for it); it reads the same environment.
+// Changed with that clean-up: CAPDEC_PP is a flag like its neighbours.  Its former modes 1 and 3 (also / only the 256 x 256
+// tile for large launches, which only ever acted in measurement builds) are read as "on", the default; in the shipped
+// library CAPDEC_PP=3 used to mean "never" for every reachable launch.
 #pragma once
 #include <string>
 
 namespace capdec {
 
 struct Tuning {
-    // ---- product
     int gemm_mode = 3;            // CAPDEC_GEMM_MODE: f32 0 | bf16x3 1 | bf16 2 | f16x2 3 (default) | f16 4
     bool batch_invariant = false; // CAPDEC_BATCH_INVARIANT
     bool compact = true;          // CAPDEC_COMPACT=0: finished captions stay in the batch
@@ -28,8 +31,7 @@ struct Tuning {
     int h2_persist = 512;         // CAPDEC_H2_PERSIST: blocks of the persistent form (0 = one block per tile)
     int h2w = 1;                  // CAPDEC_H2W: 0 = round-2 kernels only, 1 = planners, 2 / 8 = force a round-3 wide tile,
                                   //             10 / 14 = force a round-4 ping-pong tile (tests)
-    int pp = 2;                   // CAPDEC_PP: ping-pong planner: 0 never, 2 mid-size launches (default); 1 / 3 (also / only large
-                                  //             launches: the 256 x 256 tile) act in measurement builds only
+    bool pp = true;               // CAPDEC_PP=0: no ping-pong tiles from the planner (default: mid-size launches take them)
     bool lmhead_wide = true;      // CAPDEC_LMHEAD_WIDE=0: 128-row lm_head tiles at every size
     bool lmhead_k3 = true;        // CAPDEC_LMHEAD_K3=0: the wide lm_head keeps k candidates per tile (no exact second pass)
     int lmhead_k3_max = 60;       // CAPDEC_LMHEAD_K3_MAX: per mille of the rows taking the second pass above which a decode
@@ -48,23 +50,6 @@ struct Tuning {
     bool hook_packa = false;      // CAPDEC_HOOK_PACKA: capdec_gemm_f32 (test hook) packs A first (the LayerNorm -> GEMM path)
     bool hook_cache = false;      // CAPDEC_HOOK_CACHE: ... and treats both operands as resident (micro-benchmarks)
     std::string rccl_lib;         // CAPDEC_RCCL_LIB: path of librccl for the C-ABI communicator
-    // ---- measurement (read only with -DCAPDEC_MEASURE; constants otherwise)
-    int h2_ns = 4;                // CAPDEC_H2_NS: ring depth 3 | 4 | 5 of the 128 x 128 kernel
-    int h2_abl = 0;               // CAPDEC_H2_ABL 1..6: ablations, WRONG results
-    int x1_ns = 3;                // CAPDEC_X1_NS=4: two blocks per CU for the one-plane kernels
-    int x3_abl_dma = 0;           // CAPDEC_ABL_DMA (bf16x3 kernels)
-    int x3_tile_m = 0;            // CAPDEC_X3_TILE_M=64
-    int f32_bk = 0;               // CAPDEC_GEMM_BK
-    int f32_lmhead_bk = 16;       // CAPDEC_LMHEAD_BK
-    int att_preload = 1;          // CAPDEC_ATT_PRELOAD=0
-    int att_wsync = 1;            // CAPDEC_ATT_WSYNC=0
-    int att_dma = 1;              // CAPDEC_ATT_DMA=0
-    int att_occ = 4;              // CAPDEC_ATT_OCC=3
-    int att_na = 0;               // CAPDEC_ATT_NA=2 | 4
-    int pp_abl = 0;               // CAPDEC_PP_ABL 1..8 (gemm_pp.hip)
-    std::string pp_stamps;        // CAPDEC_PP_STAMPS=<file>: per-block phase stamps of the ping-pong GEMM
-    int ed_attn_group = 0;        // CAPDEC_ED_ATTN_GROUP=1 | 2 | 4: (caption, head) units per block of the encoder-decoder mapper's attention
-    int lmhead_k1 = 0;            // CAPDEC_LMHEAD_K1=1: the k = 1 lm_head epilogue whatever k is (WRONG results)
 };
 
 // parses the environment; on a malformed value returns false and sets *err (capdec_create then fails: a typo must not

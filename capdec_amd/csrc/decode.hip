@@ -259,7 +259,6 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     KvCache kv;
     CAPDEC_TRY(ensure_kv(c, kv, rows, ctx));
     kv.fixed_variant = c->batch_invariant;
-    kv.tune = &c->tune;
     kv.prefix_len = P;
     CAPDEC_TRY(ensure_body_ws(c, std::max(nc * P, rows), d));
     CAPDEC_TRY(c->next_tok.ensure((size_t)rows * 4));

@@ -215,7 +215,7 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
         { ProfScope ps(c, F_LN); CAPDEC_TRY(launch_layernorm(c->stream, h, ldh, lnw, lnb, eps, x, K, M, K)); }
         if (c->gemm_mode == GEMM_F32) {
             ProfScope ps(c, F_LMHEAD, flops);
-            return launch_gemm_f32_topk(c->stream, x, K, W, K, M, N, K, k, inv_temp, o, &c->tune);
+            return launch_gemm_f32_topk(c->stream, x, K, W, K, M, N, K, k, inv_temp, o);
         }
         const void *pl = nullptr;
         CAPDEC_TRY(planes_of(c, W, N, K, true, &pl));
@@ -234,7 +234,7 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
         const int h2w = c->tune.h2w;
         if (wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2)) {   // (CAPDEC_H2W >= 2: forced, tests)
             *k3 = k3_ok;
-            return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o, &c->tune);
+            return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o);
         }
         return launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o);
     }

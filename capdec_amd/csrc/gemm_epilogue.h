@@ -183,7 +183,7 @@ __device__ __forceinline__ void epilogue_store_packed_t(const f32x16 (&acc)[2][2
 // torch.topk walk expect.  Round 4 form: per round the VALUE of the best remaining logit comes from a max3 tree and
 // four v_max_f32 DPP steps, its lowest COLUMN from an equality scan and four v_min_u32 DPP steps, then the winner is
 // retired -- ~45 VALU instructions where the former (value, column) pair tournament with its two-key comparisons took
-// ~80; the selection rounds were a fifth of the fused lm_head's time (CAPDEC_LMHEAD_K1 measurement).
+// ~80; the selection rounds were a fifth of the fused lm_head's time (measured with the k = 1 epilogue in place of k = 5).
 __device__ __forceinline__ int row16_min_i(int v) {
     v = min(v, dpp_i<DPP_XOR1>(v));
     v = min(v, dpp_i<DPP_XOR2>(v));

@@ -1,7 +1,7 @@
 // Coalesced GEMM epilogues: the accumulators of a wavefront go through an LDS transposition before they leave the CU.
 //
-// Why (round 4, tools/pp_stamps.py): in the TR accumulator layout a lane owns four consecutive columns of ONE row, so a
-// float4 store instruction of the direct epilogues (gemm_epilogue.h, gemm_epilogue_w.h) touches 64 different rows -- 64
+// Why (round 4, per-block phase stamps: profiles/r4_gemm_pp.txt): in the TR accumulator layout a lane owns four consecutive columns of ONE row, so a
+// float4 store instruction of the direct epilogues (gemm_epilogue.h) touches 64 different rows -- 64
 // partly written 128-byte lines per instruction, ~600 cycles each: a 256 x 256 tile took 17-20 us to store (a quarter of
 // its whole time at 25 000 rows; most of a 625-caption launch's fixed cost), the packed outputs (8-byte pieces) more.
 // Here every wavefront writes a 32-row block of its tile into its own LDS slab [32][W + 4] fp32 (16 ds_write_b128 at
@@ -27,7 +27,6 @@ struct EpiArgs {
     const char *resid_pk = nullptr;    // packed residual of the output's format
     int fmt = PK_F16X2;
     const QkvScatter *sc = nullptr;    // decode-step qkv projection: K / V thirds straight into the cache
-    bool nt = false;                   // fp32 C: non-temporal stores (the result is not re-read by this kernel)
 };
 
 template <int TJ> struct EpiSlab {
@@ -102,12 +101,7 @@ __device__ __forceinline__ void epilogue_lds_wave(const f32x16 (&acc)[TI][TJ], f
                     v[0].x = post_resid_const<ACT>(v[0].x + r4.x); v[0].y = post_resid_const<ACT>(v[0].y + r4.y);
                     v[0].z = post_resid_const<ACT>(v[0].z + r4.z); v[0].w = post_resid_const<ACT>(v[0].w + r4.w);
                 }
-                if (a.nt) {
-                    typedef float nt_f4 __attribute__((ext_vector_type(4)));
-                    nt_f4 w; w[0] = v[0].x; w[1] = v[0].y; w[2] = v[0].z; w[3] = v[0].w;
-                    __builtin_nontemporal_store(w, reinterpret_cast<nt_f4 *>(a.C + (size_t)row * a.ldc + col));
-                }
-                else *reinterpret_cast<float4 *>(a.C + (size_t)row * a.ldc + col) = v[0];
+                *reinterpret_cast<float4 *>(a.C + (size_t)row * a.ldc + col) = v[0];
             } else if constexpr (MODE == 2) {
                 const QkvScatter &sc = *a.sc;
                 if (col < sc.d) {

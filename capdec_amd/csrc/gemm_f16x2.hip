@@ -125,8 +125,6 @@ __host__ __device__ constexpr int waitcnt_imm(int vm, int lgkm) {
 
 // TR: MFMA operands swapped (D^T), a lane ends with four consecutive columns of one row (see gemm_bf16x3.hip).
 // am = sum hi_a hi_b, ac = sum (hi_a lo_b + lo_a hi_b) (weight 2^-11, applied by h2_join).
-// ABL (measurement only, CAPDEC_H2_ABL; results are WRONG for ABL != 0): 1 = no s_barrier in the loop, 2 = no LDS-DMA in
-// the loop, 3 = no fragment reads in the loop, 4 = neither barrier nor DMA, 5 / 6 = all blocks load the same few panels
 // KIND: 0 = f16x2 (the fp32-accurate scheme above).  1 / 2 = ONE-plane fp16 / bf16 operands (formats PK_F16X1 /
 // PK_BF16X1: the reduced-precision modes, one MFMA per product): the same ring, DMA pieces and fragment reads, but a
 // stage holds TWO consecutive k-steps of the single plane where f16x2 holds the two planes of one k-step (both are
@@ -145,7 +143,7 @@ struct ConvGeo {
     const char *zero = nullptr;   // >= ncs * 8 KB + 8 KB of zeros: the operand rows of the padding
 };
 
-template <bool TR, int NS, int ABL = 0, int KIND = 0, bool CONV = false>
+template <bool TR, int NS, int KIND = 0, bool CONV = false>
 __device__ __forceinline__ void h2p_mainloop(const _Float16 *__restrict__ Apk, const _Float16 *__restrict__ Bpk, int K,
                                              int tm, int tn, char *smem, f32x16 (&am)[2][2], f32x16 (&ac)[2][2],
                                              int ks0 = 0, int nks = -1, const ConvGeo cg = ConvGeo()) {
@@ -156,11 +154,8 @@ __device__ __forceinline__ void h2p_mainloop(const _Float16 *__restrict__ Apk, c
     const int half = lane >> 5, l32 = lane & 31;
     const int nkf = K / (KIND == 0 ? X3_BK : 2 * X3_BK);                       // stages of the whole K (panel stride)
     const int nk = nks < 0 ? nkf : nks;                                        // stages of THIS block, even
-    // (ABL 5 / 6: every block loads one of 4 x 4 / 8 x 8 panels -- a 3 MB / 6 MB working set per launch: what the loop
-    //  does when (nearly) every operand piece is an L2 hit)
-    const int tml = ABL == 5 ? (tm & 3) : ABL == 6 ? (tm & 7) : tm, tnl = ABL == 5 ? (tn & 3) : ABL == 6 ? (tn & 7) : tn;
-    const _Float16 *ap = Apk + ((size_t)tml * nkf + ks0) * (H2_BLOCK_B / 2) + t * 8;   // this thread's 16-B piece
-    const _Float16 *bp = Bpk + ((size_t)tnl * nkf + ks0) * (H2_BLOCK_B / 2) + t * 8;
+    const _Float16 *ap = Apk + ((size_t)tm * nkf + ks0) * (H2_BLOCK_B / 2) + t * 8;    // this thread's 16-B piece
+    const _Float16 *bp = Bpk + ((size_t)tn * nkf + ks0) * (H2_BLOCK_B / 2) + t * 8;
     char *dst0 = smem + wave * 1024;                                           // wave-uniform LDS base of its pieces
     // CONV: running (stage, tap, stage-in-tap) of the NEXT tile to send (the DMAs are issued in increasing stage order,
     // clamped at the last one) and this thread's source for the current tap
@@ -243,9 +238,8 @@ __device__ __forceinline__ void h2p_mainloop(const _Float16 *__restrict__ Apk, c
     //  completed, or it puts an lgkmcnt(0) in front of the next MFMAs -- behind the freshly issued reads)
 #define H2_SYNC()                                                                        \
     asm volatile("" ::: "memory");                                                       \
-    if constexpr (ABL == 2 || ABL == 4) __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));   \
-    else __builtin_amdgcn_s_waitcnt(waitcnt_imm(4 * (NS - 2), 0));                       \
-    if constexpr (ABL != 1 && ABL != 4) __builtin_amdgcn_s_barrier();                    \
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(4 * (NS - 2), 0));                            \
+    __builtin_amdgcn_s_barrier();                                                        \
     asm volatile("" ::: "memory");
     // one memory operation in the shadow of each MFMA: 8 fragment reads, then the 4 DMA pieces
 #define H2_INTERLEAVE()                                                                    \
@@ -284,15 +278,15 @@ __device__ __forceinline__ void h2p_mainloop(const _Float16 *__restrict__ Apk, c
     int s0 = 0;                                                  // kt % NS
     for (int kt = 0; kt < nk; kt += 2) {
         const int s1 = s0 + 1 == NS ? 0 : s0 + 1, s2 = s1 + 1 == NS ? 0 : s1 + 1;
-        if constexpr (ABL != 3) H2_READ(f1, s1)                  // tile kt+1
-        if constexpr (ABL != 2 && ABL != 4) H2_DMA(s0, min(kt + NS, nk - 1))   // unconditional (clamped): exact vmcnt count
+        H2_READ(f1, s1)                                          // tile kt+1
+        H2_DMA(s0, min(kt + NS, nk - 1))                         // unconditional (clamped): exact vmcnt count
         H2_MFMAS(f0)                                             // tile kt
-        if constexpr (ABL == 0) { H2_INTERLEAVE() }
+        H2_INTERLEAVE()
         H2_SYNC()
-        if constexpr (ABL != 3) H2_READ(f0, s2)                  // tile kt+2
-        if constexpr (ABL != 2 && ABL != 4) H2_DMA(s1, min(kt + 1 + NS, nk - 1))
+        H2_READ(f0, s2)                                          // tile kt+2
+        H2_DMA(s1, min(kt + 1 + NS, nk - 1))
         H2_MFMAS(f1)                                             // tile kt+1
-        if constexpr (ABL == 0) { H2_INTERLEAVE() }
+        H2_INTERLEAVE()
         H2_SYNC()
         s0 = s2;
     }
@@ -344,7 +338,7 @@ __device__ __forceinline__ EpiArgs h2_epi_args(float *C, int ldc, int M, int N, 
     return ea;
 }
 
-template <bool VEC4, int NS, int ABL = 0>
+template <bool VEC4, int NS>
 __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__restrict__ Apk,
                                                              const _Float16 *__restrict__ Bpk, float *C, int ldc, int M,
                                                              int N, int K, const float *__restrict__ bias,
@@ -361,7 +355,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__r
         int tm, tn;
         tile_coords(tiles_m, tiles_n, tm, tn, tile);
         f32x16 am[2][2], ac[2][2];
-        h2p_mainloop<true, NS, ABL>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier: the ring is free again
+        h2p_mainloop<true, NS>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier: the ring is free again
         h2_join(am, ac);
         if constexpr (VEC4) {
             const EpiArgs ea = h2_epi_args(C, ldc, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, resid, ldr, act, packed_out, PK_F16X2, &sc);
@@ -435,7 +429,7 @@ int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked,
         const bool can_split = epi.splitk_ws && !epi.resid_packed && !epi.packed_out && !sc.kc;
         int which = 0;
         if (tn.h2w >= 10) which = (tn.h2w == 10 || epi.wide_ok) ? tn.h2w : 0;
-        else if (tn.h2w == 1 && tn.pp && M > 4 * GEMM_BM) which = pp_plan(M, N, K, epi.wide_ok, can_split, tn.pp);
+        else if (tn.h2w == 1 && tn.pp && M > 4 * GEMM_BM) which = pp_plan(M, N, K, epi.wide_ok, can_split);
         if (which) return launch_gemm_pp(st, which, Apacked, Bpacked, C, ldc, M, N, K, epi, 1.0f / H2_LO_SCALE);
     }
     const int S = (vec4 && epi.splitk_ws && !epi.resid_packed) ? gemm_splitk_slices(M, N, K, tn) : 1;
@@ -459,28 +453,6 @@ int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked,
     hipLaunchKernelGGL((gemm_f16x2p_kernel<V4, NSV>), dim3(grid_h2), dim3(256), 0, st, (const _Float16 *)Apacked, \
                        (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, resid_arg, epi.ldr, epi.act, tiles_m,      \
                        tiles_n, (char *)epi.packed_out, sc)
-#ifdef CAPDEC_MEASURE
-    // CAPDEC_H2_ABL 1..6: ablations of the main loop (WRONG results); CAPDEC_H2_NS: ring depth 3 / 5
-    if (vec4 && tn.h2_abl >= 1 && tn.h2_abl <= 6) {
-#define LAUNCH_H2A(A)                                                                                               \
-    hipLaunchKernelGGL((gemm_f16x2p_kernel<true, H2_NS, A>), dim3(tiles_m * tiles_n), dim3(256), 0, st,               \
-                       (const _Float16 *)Apacked, (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, epi.resid,   \
-                       epi.ldr, epi.act, tiles_m, tiles_n, (char *)epi.packed_out, sc)
-        switch (tn.h2_abl) {
-            case 1: LAUNCH_H2A(1); break;
-            case 2: LAUNCH_H2A(2); break;
-            case 3: LAUNCH_H2A(3); break;
-            case 4: LAUNCH_H2A(4); break;
-            case 5: LAUNCH_H2A(5); break;
-            default: LAUNCH_H2A(6);
-        }
-#undef LAUNCH_H2A
-        CAPDEC_HIP(hipGetLastError());
-        return 0;
-    }
-    if (vec4 && tn.h2_ns == 3) { LAUNCH_H2(true, 3); CAPDEC_HIP(hipGetLastError()); return 0; }
-    if (vec4 && tn.h2_ns == 5) { LAUNCH_H2(true, 5); CAPDEC_HIP(hipGetLastError()); return 0; }
-#endif
     if (vec4) LAUNCH_H2(true, H2_NS);
     else LAUNCH_H2(false, H2_NS);
 #undef LAUNCH_H2
@@ -503,7 +475,7 @@ int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpa
 }
 
 // ---- one-plane (reduced-precision) kernels on the same main loop: KIND 1 = fp16 operands, 2 = bf16 operands
-// (NS = 4: 64 KB, two blocks per CU; NS = 3: 48 KB and <= 168 registers, THREE blocks per CU -- CAPDEC_X1_NS picks)
+// (NS = 4: 64 KB, two blocks per CU; NS = 3: 48 KB and <= 168 registers, THREE blocks per CU -- the vec4 form)
 template <bool VEC4, int KIND, int NS>
 __global__ __launch_bounds__(256, (NS == 3 ? 3 : 2)) void gemm_x1_kernel(const _Float16 *__restrict__ Apk, const _Float16 *__restrict__ Bpk,
                                                          float *C, int ldc, int M, int N, int K,
@@ -516,7 +488,7 @@ __global__ __launch_bounds__(256, (NS == 3 ? 3 : 2)) void gemm_x1_kernel(const _
         int tm, tn;
         tile_coords(tiles_m, tiles_n, tm, tn, tile);
         f32x16 am[2][2], ac[2][2];
-        h2p_mainloop<true, NS, 0, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);
+        h2p_mainloop<true, NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);
         if constexpr (VEC4) {
             const EpiArgs ea = h2_epi_args(C, ldc, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, resid, ldr, act, packed_out, out_fmt, &sc);
             epilogue_lds<H2Tile>(am, smem, ea);
@@ -539,7 +511,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x1_topk_kernel(const _Float16 *__
     int tm, tn;
     tile_coords(tiles_m, tiles_n, tm, tn);
     f32x16 am[2][2], ac[2][2];
-    h2p_mainloop<false, H2_NS, 0, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier
+    h2p_mainloop<false, H2_NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier
     epilogue_topk<KSEL, 2, true>(am, reinterpret_cast<float *>(smem), M, N, tm * GEMM_BM, tn * GEMM_BN, tn, tiles_n, inv_temp,
                                  tile_max, tile_sum, cand_val, cand_idx);
 }
@@ -559,7 +531,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x1_topk_dev_kernel(const _Float16
         int tm, tn;
         tile_coords(tiles_m, tiles_n, tm, tn, tile);
         f32x16 am[2][2], ac[2][2];
-        h2p_mainloop<false, H2_NS, 0, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier
+        h2p_mainloop<false, H2_NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier
         epilogue_topk<5, 2, true>(am, reinterpret_cast<float *>(smem), M, N, tm * GEMM_BM, tn * GEMM_BN, tn, tiles_n, inv_temp,
                                   tile_max, tile_sum, cand_val, cand_idx);
         __syncthreads();                                                             // the ring is free again
@@ -593,7 +565,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x1_splitk_kernel(const _Float16 *
     tile_coords(tiles_m, tiles_n, tm, tn, blockIdx.x - slice * ntiles);
     const int nks = K / (2 * X3_BK) / S;                 // stages (two k-steps each) of this slice
     f32x16 am[2][2], ac[2][2];
-    h2p_mainloop<true, H2_NS, 0, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac, slice * nks, nks);
+    h2p_mainloop<true, H2_NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac, slice * nks, nks);
     const EpiArgs ea = h2_epi_args(part + (size_t)slice * M * N, N, M, N, tm * GEMM_BM, tn * GEMM_BN, nullptr, nullptr, 0,
                                    CAPDEC_ACT_NONE, nullptr, PK_F16X2, nullptr);
     epilogue_lds_wave<2, 2, 0, CAPDEC_ACT_NONE>(am, reinterpret_cast<float *>(smem + (threadIdx.x >> 6) * EpiSlab<2>::BYTES),
@@ -634,11 +606,10 @@ int launch_gemm_x1(hipStream_t st, const void *Apacked, const void *Bpacked, flo
             return launch_splitk_reduce(st, part, S, M, N, epi, C, ldc, fmt);
         }
     }
-    // three blocks per CU measured +3 % at 25 000 rows, +1.3 % on the greedy bf16 workload; CAPDEC_X1_NS=4: two blocks
-    const int ns3 = tuning_of(epi).x1_ns == 4 ? 0 : 1;
+    // vec4: ring of 3, three blocks per CU (measured +3 % at 25 000 rows, +1.3 % on the greedy bf16 workload against two)
     // persistent blocks for grids of up to four rounds (768 slots with three blocks per CU, 512 with two)
     const int persist = tuning_of(epi).h2_persist;
-    const int slots = persist > 0 ? ((vec4 && ns3) ? persist * 3 / 2 : persist) : 0;
+    const int slots = persist > 0 ? (vec4 ? persist * 3 / 2 : persist) : 0;
     const int grid_x1 = (slots > 0 && tiles_m * tiles_n <= 4 * slots) ? std::min(tiles_m * tiles_n, slots) : tiles_m * tiles_n;
 #define LAUNCH_X1V(V4, KD, NSV)                                                                                         \
     hipLaunchKernelGGL((gemm_x1_kernel<V4, KD, NSV>), dim3(grid_x1), dim3(256), 0, st, (const _Float16 *)Apacked, \
@@ -646,7 +617,7 @@ int launch_gemm_x1(hipStream_t st, const void *Apacked, const void *Bpacked, flo
                        epi.packed_out ? (const float *)epi.resid_packed : epi.resid, epi.ldr, epi.act, tiles_m,       \
                        tiles_n, (char *)epi.packed_out, fmt, sc)
 #define LAUNCH_X1K(KD)                                                                        \
-    if (vec4) { if (ns3) LAUNCH_X1V(true, KD, 3); else LAUNCH_X1V(true, KD, 4); }             \
+    if (vec4) LAUNCH_X1V(true, KD, 3);                                                        \
     else LAUNCH_X1V(false, KD, 4)
     if (fmt == PK_F16X1) { LAUNCH_X1K(1); } else { LAUNCH_X1K(2); }
 #undef LAUNCH_X1K
@@ -688,7 +659,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_packed_kernel(const _Float16 *
     int tm, tn;
     tile_coords(tiles_m, tiles_n, tm, tn);
     f32x16 am[2][2], ac[2][2];
-    h2p_mainloop<true, H2_NS, 0, KIND, true>(Apk, Bpk, K, tm, tn, smem, am, ac, 0, -1, cg);
+    h2p_mainloop<true, H2_NS, KIND, true>(Apk, Bpk, K, tm, tn, smem, am, ac, 0, -1, cg);
     if constexpr (KIND == 0) h2_join(am, ac);
     const EpiArgs ea = h2_epi_args(C, ldc, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, packed_out ? nullptr : resid, ldr, act, packed_out,
                                    fmt, nullptr);

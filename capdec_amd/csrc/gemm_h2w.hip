@@ -21,9 +21,7 @@
 //
 // One template serves the geometries (waves WM x WN, wave tile TI x TJ, ring depth NS):
 //   W256x128: 2x2 waves, 4x2 tiles, 256x128 block tile, 24 KB stages, NS = 3 (72 KB): two blocks per CU
-//   W256x256: 2x4 waves (512 threads), 256x256 block tile, 32 KB stages, NS = 4 (128 KB): one block per CU
 //   W128x192: 2x2 waves, 2x3 tiles, 20 KB stages, NS = 4 (80 KB): two blocks per CU -- column tiles of 192
-//   W256x256q: 2x2 waves, 4x4 tiles (128x128 per wavefront, AGPR accumulators), one wavefront per SIMD (measurement)
 #include <algorithm>
 #include <cstdlib>
 
@@ -40,9 +38,8 @@ __host__ __device__ constexpr int waitcnt_imm_w(int vm, int lgkm) {
     return (vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14);
 }
 
-template <int WM_, int WN_, int TI_, int TJ_, int NS_, int MINW_, bool ACCMAJOR_ = false>
+template <int WM_, int WN_, int TI_, int TJ_, int NS_, int MINW_>
 struct WGeo {
-    static constexpr bool ACCMAJOR = ACCMAJOR_;   // the three MFMAs of an accumulator back to back (measurement)
     static constexpr int WM = WM_, WN = WN_, TI = TI_, TJ = TJ_, NS = NS_, MINW = MINW_;
     static constexpr int NW = WM * WN, THREADS = 64 * NW;
     static constexpr int BM = WM * TI * 32, BN = WN * TJ * 32;
@@ -150,19 +147,12 @@ __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, c
     }
 #define W_MM1(x, y, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0)
 #define W_MM(x, y, c) (TR ? W_MM1(y, x, c) : W_MM1(x, y, c))
-    // the MFMAs of row group i of the tile held in fragment set F (bs[j] = 2^11 hi_b[j])
-#define W_GROUP(F, i)                                                                                      \
-    if constexpr (G::ACCMAJOR) {                                                                           \
-        _Pragma("unroll") for (int j = 0; j < TJ; ++j) {                                                   \
-            acc[i][j] = W_MM(F##a[i][1], F##b[j][0], acc[i][j]);                                           \
-            acc[i][j] = W_MM(F##a[i][0], bs[j], acc[i][j]);                                                \
-            acc[i][j] = W_MM(F##a[i][0], F##b[j][1], acc[i][j]);                                           \
-        }                                                                                                  \
-    } else {   /* term-major: consecutive MFMAs never share an accumulator */                              \
-        _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][1], F##b[j][0], acc[i][j]); \
-        _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][0], bs[j], acc[i][j]);      \
-        _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][0], F##b[j][1], acc[i][j]); \
-    }
+    // the MFMAs of row group i of the tile held in fragment set F (bs[j] = 2^11 hi_b[j]), term-major: consecutive MFMAs
+    // never share an accumulator (accumulator-major order measured -4 %)
+#define W_GROUP(F, i)                                                                                       \
+    _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][1], F##b[j][0], acc[i][j]);     \
+    _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][0], bs[j], acc[i][j]);          \
+    _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][0], F##b[j][1], acc[i][j]);
 #define W_SYNC()                                                                       \
     asm volatile("" ::: "memory");                                                     \
     __builtin_amdgcn_s_waitcnt(waitcnt_imm_w(PPW * (NS - 2), 0));                      \
@@ -293,12 +283,9 @@ __global__ __launch_bounds__(G::THREADS, G::MINW) void gemm_h2w_topk_dev_kernel(
 }
 
 using W256x128 = WGeo<2, 2, 4, 2, 3, 2>;      // 4 waves, 72 KB, two blocks per CU
-#ifdef CAPDEC_MEASURE
-using W256x256 = WGeo<2, 4, 4, 2, 4, 2>;      // 8 waves, 128 KB, one block per CU (measured: -4 .. -27 %)
-// (measured and removed from the build, profiles/r3_gemm_geometries.txt: WGeo<2,2,2,2,3,3> = 128x128 at three blocks per CU
-//  and WGeo<2,2,2,2,4,2> at two: +-0 against the round-2 kernel; WGeo<2,2,4,2,3,2,true>, accumulator-major MFMA order: -4 %)
-using W256x256q = WGeo<2, 2, 4, 4, 4, 1>;     // 4 waves x (128 x 128), 128 KB, ONE wavefront per SIMD (accumulators in AGPRs: -40 %)
-#endif
+// (measured and removed, profiles/r3_gemm_geometries.txt: 128x128 at three blocks per CU, WGeo<2,2,2,2,3,3>, and at two,
+//  WGeo<2,2,2,2,4,2>: +-0 against the round-2 kernel; 256x256 on 8 waves, one block per CU: -4 .. -27 %; 256x256 on 4 waves
+//  of 128 x 128, one wavefront per SIMD with the accumulators in AGPRs: -40 %)
 using W128x192 = WGeo<2, 2, 2, 3, 4, 2>;      // 4 waves x (64 x 96), 80 KB, two blocks per CU: column tiles of 192
 
 // max |w| of a device matrix as the bit pattern of a non-negative float (atomicMax on the bits is order preserving)
@@ -362,10 +349,6 @@ int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *
                     int K, const GemmEpilogue &epi, float scale) {
     switch (which) {
         case 2: return launch_h2w<W256x128>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, 512);
-#ifdef CAPDEC_MEASURE
-        case 3: return launch_h2w<W256x256>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, 256);
-        case 6: return launch_h2w<W256x256q>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, 256);
-#endif
         case 8: return launch_h2w<W128x192>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, 512);
         default: CAPDEC_CHECK(false, "gemm_h2w: unknown geometry");
     }
@@ -374,18 +357,12 @@ int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *
 
 // fused lm_head on the 256 x 128 tile: same partial lists per (row, 128-column tile) as launch_gemm_f16x2p_topk
 int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                         float inv_temp, const TopkOut &o, const Tuning *tune) {
+                         float inv_temp, const TopkOut &o) {
     CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_h2w_topk: K must be a multiple of 64");
     using G = W256x128;
     const int tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
     dim3 grid(tiles_m * tiles_n), block(G::THREADS);
     const float scale = inv_temp / H2_LO_SCALE;
-#ifdef CAPDEC_MEASURE
-    // CAPDEC_LMHEAD_K1=1 (WRONG results): run the k = 1 epilogue whatever k is -- what the top-k selection rounds cost
-    if (tune && tune->lmhead_k1) k = 1;
-#else
-    (void)tune;
-#endif
     CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
         hipLaunchKernelGGL((gemm_h2w_topk_kernel<G, KS>), grid, block, 0, st, (const _Float16 *)Apacked,
                            (const _Float16 *)Bpacked, M, N, K, scale, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,

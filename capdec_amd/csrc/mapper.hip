@@ -27,7 +27,7 @@ int tlayer_tail(capdec_ctx *c, const TMapLayer &w, const TLayerBufs &b, int M, i
 static int encdec_chunk(capdec_ctx *c, const float *x, int n, float *out) {
     Mapper &m = c->map;
     const int d = m.d, E = m.enc_dim, C = m.clip_len, P = m.P, L = m.n_layers, H = m.heads;
-    const int Me = n * C, Md = n * P, grp = c->tune.ed_attn_group;
+    const int Me = n * C, Md = n * P;
     // refused before the first launch (the loader checked the same: a context cannot hold such a mapper)
     CAPDEC_CHECK(attn_cross_lds_bytes(C, C, E / H, 1) <= 160 * 1024 && attn_cross_lds_bytes(P, C, d / H, 1) <= 160 * 1024 &&
                  attn_cross_lds_bytes(P, P, d / H, 1) <= 160 * 1024, "mapper_forward: one head's keys, values and queries exceed 160 KB of LDS");
@@ -47,7 +47,7 @@ static int encdec_chunk(capdec_ctx *c, const float *x, int n, float *out) {
     const TLayerBufs eb{ref, xn, qkv, att, ref, xn, ff, ref};       // in place: x = mid = out, one scratch for both norms
     for (int l = 0; l < L; ++l) {
         CAPDEC_TRY(tlayer_self_front(c, m.layers[l], eb, Me, E, true));
-        { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, qkv, 3 * E, (size_t)C * 3 * E, qkv + E, qkv + 2 * E, 3 * E, att, n, C, C, H, E / H, grp)); }
+        { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, qkv, 3 * E, (size_t)C * 3 * E, qkv + E, qkv + 2 * E, 3 * E, att, n, C, C, H, E / H)); }
         CAPDEC_TRY(tlayer_tail(c, m.layers[l], eb, Me, E, m.enc_hidden, true));
     }
     // ---- decoder
@@ -73,10 +73,10 @@ static int encdec_chunk(capdec_ctx *c, const float *x, int n, float *out) {
         }
         if (cross) {
             const float *kl = kvc + (size_t)(l / 2) * 2 * d;
-            { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, ql, d, q_cap, kl, kl + d, (int)ldc, att, n, P, C, H, d / H, grp)); }
+            { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, ql, d, q_cap, kl, kl + d, (int)ldc, att, n, P, C, H, d / H)); }
         } else {
             CAPDEC_TRY(gemm(c, seq, d, w.wkv, d, kv, 2 * d, Md, 2 * d, d, nullptr, CAPDEC_ACT_NONE));   // the stream itself, not norm1 of it
-            { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, ql, d, q_cap, kv, kv + d, 2 * d, att, n, P, P, H, d / H, grp)); }
+            { ProfScope ps(c, F_MAP_ATTN); CAPDEC_TRY(launch_attn_cross(c->stream, ql, d, q_cap, kv, kv + d, 2 * d, att, n, P, P, H, d / H)); }
         }
         CAPDEC_TRY(tlayer_tail(c, w, TLayerBufs{seq, xn, nullptr, att, seq, xn, ff, l == 2 * L - 1 ? out : seq}, Md, d, m.mlp_hidden, true));
     }

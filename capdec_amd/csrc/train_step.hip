@@ -281,7 +281,6 @@ static int train_step(capdec_ctx *c, const float *prefix, const int *tokens, int
     }
     KvCache kv;
     kv_geometry(kv, B, S, g.n_head, 64);
-    kv.tune = &c->tune;
     for (int i = 0; i < nl; ++i) {
         const Gpt2Layer &w = g.layers[i];
         float *h = hs + Rd * i, *hn = hs + Rd * (i + 1);

@@ -28,8 +28,8 @@ class Engine:
     """One context per GPU / rank."""
 
     def __init__(self, device: int = 0, kv_budget_bytes: int = 0, measure: bool = False):
-        """measure=True: the context lives in libcapdec_hip_measure.so (built with -DCAPDEC_MEASURE: ablation / override
-        knobs, the diverged-beam hook) -- tools/ and bench.py's untimed tail only, never the product path"""
+        """measure=True: the context lives in libcapdec_hip_measure.so (the product library plus the diverged-beam hook)
+        -- bench.py's untimed tail and one parity test only, never the product path"""
         if not torch.cuda.is_available():
             raise CapdecError("capdec_amd needs a HIP device (MI355X); none is visible and there is no CPU fallback")
         if measure:

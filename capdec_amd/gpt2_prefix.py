@@ -90,8 +90,8 @@ class _HipModule:
             yield torch.empty(0, device=dev, dtype=torch.float32)
 
     def use_measurement_build(self, on: bool = True):
-        """measurement tooling only (bench.py's untimed tail, tools/): move this module to a context of the library's
-        -DCAPDEC_MEASURE build (ablation / override knobs, the diverged-beam hook).  The current context -- weights, KV
+        """measurement tooling only (bench.py's untimed tail): move this module to a context of the library's
+        -DCAPDEC_MEASURE build (the product library plus the diverged-beam hook).  The current context -- weights, KV
         cache, workspaces -- is released; the weights are uploaded again on the next use."""
         if bool(on) != self._measure:
             if self._engine is not None:

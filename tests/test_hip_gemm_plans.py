@@ -36,19 +36,19 @@ KNOBS = ("CAPDEC_GEMM_MODE", "CAPDEC_HOOK_PACKA", "CAPDEC_HOOK_CACHE", "CAPDEC_H
          "CAPDEC_BATCH_INVARIANT")
 
 # ---- kernels as (name, template arguments): what the trace shows, mangled or demangled (kernel_signature)
-H2P = ("gemm_f16x2p_kernel", (1, 4, 0))                   # 128 x 128, two accumulator sets, float4 epilogue through LDS
-H2P_SC = ("gemm_f16x2p_kernel", (0, 4, 0))                # ... scalar epilogue (N % 4 != 0 or an unaligned stride)
+H2P = ("gemm_f16x2p_kernel", (1, 4))                      # 128 x 128, two accumulator sets, float4 epilogue through LDS
+H2P_SC = ("gemm_f16x2p_kernel", (0, 4))                   # ... scalar epilogue (N % 4 != 0 or an unaligned stride)
 H2P_SK = ("gemm_f16x2p_splitk_kernel", ())
-PP10 = ("gemm_pp_kernel", (4, 2, 2, 2, 5, 1, 0))          # ping-pong 256 x 128 (P256x128), 512 threads
-PP14 = ("gemm_pp_kernel", (4, 2, 2, 3, 4, 0, 0))          # ping-pong 256 x 192 (P256x192s)
+PP10 = ("gemm_pp_kernel", (4, 2, 2, 2, 5, 1))             # ping-pong 256 x 128 (P256x128), 512 threads
+PP14 = ("gemm_pp_kernel", (4, 2, 2, 3, 4, 0))             # ping-pong 256 x 192 (P256x192s)
 PP10_SK = ("gemm_pp_splitk_kernel", (4, 2, 2, 2, 5, 1))
 PP14_SK = ("gemm_pp_splitk_kernel", (4, 2, 2, 3, 4, 0))
-W2 = ("gemm_h2w_kernel", (2, 2, 4, 2, 3, 2, 0))           # one accumulator set, 256 x 128 (W256x128)
-W8 = ("gemm_h2w_kernel", (2, 2, 2, 3, 4, 2, 0))           # one accumulator set, 128 x 192 (W128x192)
+W2 = ("gemm_h2w_kernel", (2, 2, 4, 2, 3, 2))              # one accumulator set, 256 x 128 (W256x128)
+W8 = ("gemm_h2w_kernel", (2, 2, 2, 3, 4, 2))              # one accumulator set, 128 x 192 (W128x192)
 X3P = ("gemm_bf16x3p_kernel", (1,))
 X3P_SC = ("gemm_bf16x3p_kernel", (0,))
 X3P_SK = ("gemm_bf16x3p_splitk_kernel", ())
-X3 = ("gemm_bf16x3_kernel", (2,))                         # fp32 A split inside the kernel (no packed A)
+X3 = ("gemm_bf16x3_kernel", ())                           # fp32 A split inside the kernel (no packed A)
 F32 = ("gemm_f32_kernel", (32, 2))
 F32_BK16 = ("gemm_f32_kernel", (16, 3))                   # N >= 3072 or K >= 2048
 KIND = {"f16": 1, "bf16": 2}
@@ -475,8 +475,10 @@ def _script(argv):
 def test_kernel_signature_reads_both_name_forms():
     assert kernel_signature("_ZN6capdec21gemm_pp_splitk_kernelINS_4PGeoILi4ELi2ELi2ELi2ELi5ELb1EEEEEvPKDF16_S4_Pfiiiiiif") == PP10_SK
     assert kernel_signature("void capdec::gemm_pp_splitk_kernel<capdec::PGeo<4, 2, 2, 2, 5, true> >") == PP10_SK
-    assert kernel_signature("_ZN6capdec18gemm_f16x2p_kernelILb1ELi4ELi0EEEvPKDF16_S2_PfiiiiPKfS5_iiiiPcNS_10QkvScatterE") == H2P
-    assert kernel_signature("_ZN6capdec15gemm_h2w_kernelINS_4WGeoILi2ELi2ELi2ELi3ELi4ELi2ELb0EEEEEvPKDF16_S4_PfiiiiPKfS7_iiiiPcf") == W8
+    assert kernel_signature("_ZN6capdec18gemm_f16x2p_kernelILb1ELi4EEEvPKDF16_S2_PfiiiiPKfS5_iiiiPcNS_10QkvScatterE") == H2P
+    assert kernel_signature("_ZN6capdec15gemm_h2w_kernelINS_4WGeoILi2ELi2ELi2ELi3ELi4ELi2EEEEEvPKDF16_S4_PfiiiiPKfS7_iiiiPcf") == W8
+    assert kernel_signature("_ZN6capdec18gemm_bf16x3_kernelEPKfiPKDF16bPfiiiiS1_S1_iiii") == X3          # not a template: no arguments
+    assert kernel_signature("capdec::gemm_bf16x3_kernel(float const*, int, __bf16 const*, float*, int, int, int, int)") == X3
     assert kernel_signature("capdec::splitk_reduce_ln_kernel") == ("splitk_reduce_ln_kernel", ())
     assert kernel_signature("capdec::pack_planes_h2_kernel") is None
 

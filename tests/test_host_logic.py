@@ -39,8 +39,19 @@ def test_c_abi_exports_every_header_symbol():
     # ... and no measurement code is compiled in: no ablation / override knob is even named in the binary
     strs = subprocess.run(["strings", _capi.LIB_PATH], capture_output=True, text=True).stdout
     knobs = set(re.findall(r"CAPDEC_[A-Z0-9_]+", strs))
-    assert not {k for k in knobs if "ABL" in k or k in ("CAPDEC_H2_NS", "CAPDEC_X1_NS", "CAPDEC_ATT_OCC", "CAPDEC_ATT_NA",
-                                                        "CAPDEC_PP_STAMPS", "CAPDEC_LMHEAD_K1", "CAPDEC_GEMM_BK")}, knobs
+    # (the ablations and overrides of rounds 2-6 are retired: a knob the binary names is one that config.h documents)
+    documented = set(re.findall(r"CAPDEC_[A-Z0-9_]+", open(os.path.join(ROOT, "capdec_amd", "csrc", "config.h")).read()))
+    assert not {k for k in knobs if "ABL" in k or "STAMPS" in k}, knobs
+    assert {k for k in knobs if not k.startswith("CAPDEC_ACT_")} <= documented, knobs - documented
+    # the measurement library is the product library plus the diverged-beam hook and nothing else: one more exported
+    # symbol, the very same environment knobs
+    mlib = build.build(measure=True, verbose=False)
+    assert mlib == _capi.MEASURE_LIB_PATH
+    mout = subprocess.run(["nm", "-D", "--defined-only", mlib], capture_output=True, text=True).stdout
+    mexported = {l.split()[-1] for l in mout.splitlines() if " T " in l and "capdec_" in l.split()[-1][:7]}
+    assert mexported == exported | {"capdec_set_debug_diverge"}, mexported ^ exported
+    mstrs = subprocess.run(["strings", mlib], capture_output=True, text=True).stdout
+    assert set(re.findall(r"CAPDEC_[A-Z0-9_]+", mstrs)) == knobs
 
 
 def test_ctypes_signatures_match_header_prototypes():

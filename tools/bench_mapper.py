@@ -6,8 +6,7 @@ FLOP are the algorithm's, from the shapes (``flop_*`` below) -- what the hoists 
 
     python tools/bench_mapper.py [--captions 5000 625] [--rounds 5] [--reps 10] [--out FILE.json]
 
-``--ablate`` adds the encoder-decoder mapper with 1, 2 and 4 (caption, head) units per attention block
-(CAPDEC_ED_ATTN_GROUP, a knob of the measurement build; the product chooses from the LDS need).  Needs an MI355X."""
+Needs an MI355X."""
 from __future__ import annotations
 
 import argparse
@@ -38,17 +37,8 @@ def flop_encdec(L: int) -> float:
     return 2.0 * D * C * ENC + enc + dec
 
 
-def make(kind: str, L: int, env: dict) -> Engine:
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        e = Engine(0, measure=bool(env))          # the knobs are read once, when the context is created
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+def make(kind: str, L: int) -> Engine:
+    e = Engine(0)
     if kind == "transformer":
         e.load_mapper_transformer(synth.hot_transformer_mapper_state_dict(43, D, P, C, L))
     else:
@@ -61,17 +51,13 @@ def main():
     ap.add_argument("--captions", type=int, nargs="*", default=[5000, 625])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--ablate", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mapper needs an MI355X"
-    cfgs = [("TransformerMapper(8)", "transformer", 8, {}, flop_transformer_mapper(8)),
-            ("EncoderDecoder(4)", "encdec", 4, {}, flop_encdec(4)),
-            ("EncoderDecoder(8)", "encdec", 8, {}, flop_encdec(8))]
-    if args.ablate:
-        for g in (1, 2, 4):
-            cfgs.append((f"EncoderDecoder(4) attn_group={g}", "encdec", 4, {"CAPDEC_ED_ATTN_GROUP": str(g)}, flop_encdec(4)))
-    engines = [make(kind, L, env) for _, kind, L, env, _ in cfgs]
+    cfgs = [("TransformerMapper(8)", "transformer", 8, flop_transformer_mapper(8)),
+            ("EncoderDecoder(4)", "encdec", 4, flop_encdec(4)),
+            ("EncoderDecoder(8)", "encdec", 8, flop_encdec(8))]
+    engines = [make(kind, L) for _, kind, L, _ in cfgs]
     result = {"shape": dict(D=D, P=P, C=C, d=d), "rounds": args.rounds, "reps": args.reps, "runs": []}
     for n in args.captions:
         x = synth.synthetic_clip_embeddings(n, D, seed=1).cuda()
@@ -89,7 +75,7 @@ def main():
                 b.record()
                 b.synchronize()
                 ms[i].append(a.elapsed_time(b) / args.reps)
-        for i, (name, kind, L, env, flop) in enumerate(cfgs):
+        for i, (name, kind, L, flop) in enumerate(cfgs):
             e = engines[i]
             e.profile_reset()
             e.profile_enable(True)

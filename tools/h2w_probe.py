@@ -10,7 +10,7 @@ from capdec_amd.engine import Engine
 
 
 def main():
-    eng = Engine(0, measure=os.environ.get("CAPDEC_MEASURE_LIB") == "1")   # CAPDEC_MEASURE_LIB=1: the -DCAPDEC_MEASURE build (ablation knobs)
+    eng = Engine(0)
     res = {"h2w": os.environ.get("CAPDEC_H2W", "default"), "mode": eng.gemm_mode()}
     g = torch.Generator().manual_seed(1)
     worst = 0.0
@@ -30,7 +30,7 @@ def main():
     # loops get their own context
     eng.close()
     os.environ["CAPDEC_HOOK_CACHE"] = "1"
-    eng = Engine(0, measure=os.environ.get("CAPDEC_MEASURE_LIB") == "1")
+    eng = Engine(0)
     Ms = [int(v) for v in sys.argv[1:]] or [25000]
     custom = [tuple(int(x) for x in t.split(",")) for t in os.environ.get("PROBE_SHAPES", "").split(";") if t]
     for M in ([0] if custom else Ms):

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Correctness (vs fp64) + timing of the forced GEMM geometries on the decode loop's shapes, one process per geometry:
-#   gpurun --timeout 900 -- 'bash tools/pp_probe.sh "0 2 10 11 12 13" "3125 25000"'
+#   bash tools/pp_probe.sh "0 2 8 10 14" "3125 25000"
 set -u
-GEOS=${1:-"0 10 11 12 13"}
+GEOS=${1:-"0 2 8 10 14"}
 MS=${2:-"3125 25000"}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"
