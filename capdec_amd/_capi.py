@@ -144,6 +144,8 @@ SIGNATURES = {
     "capdec_decode_greedy_forced": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP]),
     "capdec_decode_sample": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
                                        _VP, _VP, _VP, _VP]),
+    "capdec_score": (C.c_int, [_VP, _VP, _VP, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP, _VP]),
+    "capdec_score_chunks": (C.c_int, [_VP, C.POINTER(C.c_int)]),
     "capdec_decode_beam": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP,
                                      _VP, _VP]),
     "capdec_gemm_f32": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,

@@ -81,6 +81,10 @@ bool tuning_from_env(Tuning *t, std::string *err) {
         *err = "create: CAPDEC_SAMPLE_ROWS must be >= 1";
         return false;
     }
+    if (env_int("CAPDEC_SCORE_ROWS", &t->score_rows) && t->score_rows < 1) {
+        *err = "create: CAPDEC_SCORE_ROWS must be >= 1";
+        return false;
+    }
     env_flag("CAPDEC_KV_DIRECT", &t->kv_direct);
     env_flag("CAPDEC_CLIP_TRUNC", &t->clip_trunc);
     env_flag("CAPDEC_RN_PACKED", &t->rn_packed);
@@ -158,7 +162,7 @@ void capdec_destroy(capdec_ctx *c) {
     DBuf *bufs[] = {&c->h, &c->x, &c->qkv, &c->att, &c->ff, &c->xl, &c->tmax, &c->tsum, &c->cval, &c->cidx,
                     &c->lse, &c->topv, &c->topi, &c->kc, &c->vc, &c->tokens, &c->scores, &c->seq, &c->stopped,
                     &c->done, &c->anc, &c->next_tok, &c->alive, &c->gids, &c->glens, &c->m_hid, &c->m_lin, &c->m_seq,
-                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->lmflag, &c->xpk2, &c->slogits, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
+                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->lmflag, &c->xpk2, &c->slogits, &c->s_plan, &c->s_rows, &c->s_logit, &c->s_bad, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
                     &c->r_a, &c->r_b, &c->r_c, &c->r_d, &c->r_e, &c->r_f, &c->r_col, &c->r_pk1, &c->r_pk2, &c->r_xpk,
                     &c->r_ypk, &c->r_xi, &c->r_idp, &c->r_zero};
     for (DBuf *b : bufs) b->release();
@@ -261,6 +265,12 @@ int capdec_decode_step_rows(capdec_ctx *c, int *rows, int cap, int *n) {
 int capdec_decode_chunks(capdec_ctx *c, int *chunks) {
     CAPDEC_CHECK(c && chunks, "null argument");
     *chunks = c->stat_chunks;
+    return 0;
+}
+
+int capdec_score_chunks(capdec_ctx *c, int *chunks) {
+    CAPDEC_CHECK(c && chunks, "null argument");
+    *chunks = c->stat_score_chunks;
     return 0;
 }
 

@@ -38,6 +38,9 @@ struct Tuning {
                                   //   call goes back to k per tile (checked at the poll points; break-even is ~80)
     int sample_rows = 2048;       // CAPDEC_SAMPLE_ROWS: rows of fp32 logits the sampling decode materialises at a time (2048 rows of
                                   //   GPT-2's vocabulary = 412 MB); a step with more rows loops lm_head + sampler over row blocks
+    int score_rows = 16384;       // CAPDEC_SCORE_ROWS: padded activation rows (captions x (prefix + longest caption - 1)) one chunk of
+                                  //   capdec_score pushes through the GPT-2 body at a time (16384 rows = 1.2 GB of K / V + 0.4 GB of
+                                  //   activations at GPT-2 small); a chunk always holds at least one caption
     bool kv_direct = true;        // CAPDEC_KV_DIRECT=0: the attention kernel appends K / V itself
     bool clip_trunc = true;       // CAPDEC_CLIP_TRUNC=0: the CLIP text tower computes all 77 positions of every caption (default: only
                                   //   the positions up to a chunk's last EOT; captions sorted by length)

@@ -6,6 +6,7 @@
 //                     lm_head, capdec_gemm_f32
 //   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam / sampling decode loop
 //                     (the sampling kernel itself: sample.hip)
+//   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
 //                     forward share (tlayer_self_front / tlayer_tail)
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
@@ -180,6 +181,9 @@ struct capdec_ctx {
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
     unsigned long long train_drop_seed = 0;  // ... key of the Philox keep-mask stream (counter = element, train step)
     DBuf slogits;          // sampling decode: fp32 logits of one row block, [min(rows, tune.sample_rows), ld] (decode.hip: lm_head_sample)
+    DBuf s_plan, s_rows, s_logit, s_bad;   // capdec_score (score.hip): the call's plan [lens | row offsets | h rows | targets], a
+                                           // chunk's scored rows of h [R, d], their label logits [R], first tainted position [nc]
+    int stat_score_chunks = 0;             // chunks of the last capdec_score call (capdec_score_chunks)
     DBuf lmflag, xpk2;     // fused lm_head with 3 candidates per tile: [count, total, rows...] of the rows whose top 5 need
                            // the exact second pass; their compacted packed A operand (decode.hip: lm_head_select)
     DBuf m_hid, m_lin, m_seq, m_x, m_qkv, m_att, m_ff;
@@ -310,5 +314,10 @@ struct StackCfg {
 int ensure_body_ws(capdec_ctx *c, int M, int d);
 int stack_body(capdec_ctx *c, const StackCfg &g, const StepShape &s, const KvCache &kv);
 void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd);
+// ... the pieces of the decode loop that capdec_score (score.hip) runs as they are: GPT-2's blocks on c->h; ln_f over R rows
+// of h (row stride ldh) + the fused lm_head -> c->lse [R], c->topv / c->topi [R, k]; the KV cache of `rows` sequences
+int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv);
+int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp);
+int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads = 0, int hd = 0, int layers = 0);
 
 }  // namespace capdec

@@ -101,7 +101,7 @@ int stack_body(capdec_ctx *c, const StackCfg &g, const StepShape &s, const KvCac
     return 0;
 }
 
-static int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv) {
+int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv) {
     const Gpt2 &g = c->gpt;
     StackCfg cfg{&g.layers, g.n_layer, g.d, g.eps, CAPDEC_ACT_GELU_NEW, true, true};
     return stack_body(c, cfg, s, kv);
@@ -109,7 +109,7 @@ static int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv) {
 
 // ln_f over `R` rows of h (row stride ldh floats, starting at h0) then the fused lm_head:
 // -> lse [R], topv/topi [R, k]
-static int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp) {
+int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp) {
     const Gpt2 &g = c->gpt;
     const int d = g.d, nt = gemm_tiles_n(g.vocab);
     CAPDEC_TRY(c->tmax.ensure((size_t)R * nt * 4));
@@ -201,7 +201,7 @@ void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd) {
     kv.hd = hd;
     kv.k = kv.v = nullptr;
 }
-static int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads = 0, int hd = 0, int layers = 0) {
+int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads, int hd, int layers) {
     const Gpt2 &g = c->gpt;
     kv.rows = rows;
     kv.heads = heads ? heads : g.n_head;

@@ -454,6 +454,46 @@ class Engine:
                                           order.data_ptr()), "capdec_decode_beam")
         return ids, lens, scores, order
 
+    # ------------------------------------------------------------------ scoring
+    def score(self, prefix_embed: torch.Tensor, tokens: torch.Tensor, lens=None, ignore_id: int = -1,
+              temperature: float = 1.0, return_top1: bool = False):
+        """teacher-forced log-probabilities of given captions (capdec_score): ``prefix_embed`` [n, P, d], ``tokens``
+        [n, L], ``lens`` [n] in 0..L (None: every caption has L tokens) -> device tensors logp [n, L] (0 past ``lens``
+        and where the label is ``ignore_id``), sum [n], count [n] and, with ``return_top1``, the arg-max id [n, L] of
+        every scored position.  ``lens`` is read on the host (the call plans its chunks from it): pass a list, a numpy
+        array or a host tensor to avoid a device round trip."""
+        temperature = float(temperature)
+        if temperature != temperature:
+            raise CapdecError("score: temperature is NaN")
+        if prefix_embed.dim() != 3 or tokens.dim() != 2 or prefix_embed.shape[0] != tokens.shape[0]:
+            raise CapdecError(f"score: prefix_embed [n, P, d] and tokens [n, L] expected, got {tuple(prefix_embed.shape)} "
+                              f"and {tuple(tokens.shape)}")
+        n, P, L = int(prefix_embed.shape[0]), int(prefix_embed.shape[1]), int(tokens.shape[1])
+        hl = None
+        if lens is not None:
+            hl = np.ascontiguousarray((lens.detach().cpu().numpy() if isinstance(lens, torch.Tensor) else np.asarray(lens))
+                                      .reshape(-1).astype(np.int32))
+            if hl.shape[0] != n:
+                raise CapdecError(f"score: lens must have one entry per caption ({n}), got {hl.shape[0]}")
+        p = self._dev(prefix_embed)
+        t = self._dev(tokens, torch.int32)
+        logp = torch.empty(n, L, device=self.device, dtype=torch.float32)
+        ssum = torch.empty(n, device=self.device, dtype=torch.float32)
+        count = torch.empty(n, device=self.device, dtype=torch.int32)
+        top1 = torch.empty(n, L, device=self.device, dtype=torch.int32) if return_top1 else None
+        self._sync_stream()
+        self._chk(self.lib.capdec_score(self._h, p.data_ptr(), t.data_ptr(),
+                                        hl.ctypes.data_as(_capi.c_int_p) if hl is not None else None, n, P, L, int(ignore_id),
+                                        temperature, logp.data_ptr(), ssum.data_ptr(), count.data_ptr(),
+                                        top1.data_ptr() if top1 is not None else None), "capdec_score")
+        return (logp, ssum, count, top1) if return_top1 else (logp, ssum, count)
+
+    def score_chunks(self) -> int:
+        """how many chunks the last :meth:`score` call split its captions into (capdec_score_chunks)"""
+        n = C.c_int(0)
+        self._chk(self.lib.capdec_score_chunks(self._h, C.byref(n)), "score_chunks")
+        return n.value
+
     # ------------------------------------------------------------------ caption-shard communicator (RCCL through the C ABI)
     def comm_unique_id(self) -> bytes:
         """rank 0: the 128-byte communicator id every rank passes to :meth:`comm_init`"""

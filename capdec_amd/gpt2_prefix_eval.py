@@ -72,6 +72,42 @@ def generate_samples_batch(model, tokenizer, embed: torch.Tensor, entry_count: i
             for r in range(embed.shape[0])]
 
 
+def score_ids(model: ClipCaptionModel, embed: torch.Tensor, tokens: torch.Tensor, lens=None, ignore_id: int = -1,
+              temperature: float = 1., return_top1: bool = False):
+    """embed [N, P, d], tokens [N, L], lens [N] (None: all L) -> (logp [N, L], sum [N], count [N][, top1 [N, L]]) device
+    tensors: the log-probability the model gives every token of the given captions (capdec_score; the logits are never
+    materialised)."""
+    return model.engine.score(embed, tokens, lens, ignore_id, temperature, return_top1)
+
+
+def score_captions(model, tokenizer, embed: torch.Tensor, texts, temperature: float = 1.):
+    """embed [N, P, d] and ``texts`` -- one string per prefix row, or a list of K strings per row (K candidates repeat
+    their prefix row, like ``generate_samples_batch``'s entries) -> ``(sum logp, token count)`` per text, shaped like
+    ``texts``.  A text is scored as ``tokenizer.encode`` gives it: include the stop token to score the caption as the
+    decoders emit it."""
+    n = int(embed.shape[0])
+    texts = list(texts)
+    if len(texts) != n:
+        raise CapdecError(f"score_captions: {len(texts)} texts for {n} prefix rows")
+    flat = all(isinstance(t, str) for t in texts)
+    rows = [[t] for t in texts] if flat else [list(t) for t in texts]
+    if any(isinstance(t, str) for t in texts) and not flat:
+        raise CapdecError("score_captions: texts is either one string per row or one list of strings per row")
+    K = len(rows[0]) if rows else 0
+    if K < 1 or any(len(r) != K for r in rows):
+        raise CapdecError("score_captions: every prefix row needs the same number (>= 1) of candidate texts")
+    enc = [[int(t) for t in tokenizer.encode(s)] for r in rows for s in r]
+    lens = [len(e) for e in enc]
+    L = max(max(lens), 1)
+    tokens = torch.zeros(n * K, L, dtype=torch.int32)
+    for i, e in enumerate(enc):
+        tokens[i, :len(e)] = torch.tensor(e, dtype=torch.int32)
+    _, s, c = score_ids(model, embed.repeat_interleave(K, dim=0) if K > 1 else embed, tokens, lens, -1, temperature)
+    s, c = s.cpu().tolist(), c.cpu().tolist()
+    out = [(float(a), int(b)) for a, b in zip(s, c)]
+    return out if flat else [out[r * K:(r + 1) * K] for r in range(n)]
+
+
 def generate2_batch(model, tokenizer, embed: torch.Tensor, entry_length: int = 67, stop_token: str = '.') -> List[str]:
     stop = tokenizer.encode(stop_token)[0]
     ids, lens = decode_greedy_ids(model, embed, stop, entry_length)

@@ -205,6 +205,33 @@ def validation_loss(model: ClipCaptionModel, val_dataset, batch_size: int, prefi
     return val_loss / max(1, len(loader))
 
 
+def token_nll(model: ClipCaptionModel, val_dataset, batch_size: int) -> float:
+    """mean negative log-likelihood per scored token over the WHOLE of ``val_dataset`` (items ``(tokens, mask, prefix)``):
+    eval mode, no noise injection, labels 0 ignored (``ignore_index=0`` of train.py:349), through ``Engine.score`` -- the
+    logits are never materialised, so ``batch_size`` only bounds the host-side batches.
+
+    Not the number ``validation_loss`` returns: that one is the mean of per-batch means over a shuffled, ``drop_last``
+    loader (every batch weighs the same whatever its token count, and the last incomplete batch is dropped); this one
+    is sum(-logp) / count over every token of every item, in dataset order.  The two agree when the set is one full
+    batch."""
+    from torch.utils.data import DataLoader
+    loader = DataLoader(val_dataset, batch_size=batch_size, shuffle=False, drop_last=False)
+    was_training = model.training
+    model.eval()
+    total, count = 0.0, 0
+    try:
+        for tokens, _mask, prefix in loader:
+            prefix = prefix.to(device, dtype=torch.float32)
+            embed = model.clip_project(prefix).view(-1, model.prefix_length, model.gpt_embedding_size)
+            _, s, c = model.engine.score(embed, tokens, None, ignore_id=0)
+            total += float(s.double().sum())
+            count += int(c.sum())
+    finally:
+        if was_training:
+            model.train()
+    return -total / count if count else float("nan")
+
+
 def train(dataset, model: ClipCaptionModel, args, warmup_steps: int = 5000, output_dir: str = ".", output_prefix: str = "",
           val_dataset=None):
     """reference train.py:317-392: ``dataset`` yields ``(tokens, mask, prefix)`` like train.ClipCocoDataset.__getitem__

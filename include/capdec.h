@@ -374,6 +374,36 @@ int capdec_decode_sample(capdec_ctx *ctx, const float *d_prefix, int n, int P, i
                          int32_t *d_ids,        /* [n, entry_length] */
                          int32_t *d_lens,       /* [n] */
                          float *d_logp);        /* [n, entry_length] or NULL */
+
+/* ---- scoring ------------------------------------------------------------------------- */
+/* Teacher-forced log-probabilities of GIVEN captions; the [rows, vocab] logits never exist in HBM.
+ * Caption r has prefix rows d_prefix[r] [P, d], token ids d_tokens[r, 0..L) and a length len[r] in 0..L.  The model input is
+ * cat(d_prefix[r], wte(tok[r, :len[r]-1])) + wpe, and for i < len[r]
+ *     d_logp[r, i] = s[tok[r, i]] - logsumexp(s),   s = logits at position P-1+i, times 1 / (temperature > 0 ? temperature : 1)
+ * -- `logits[:, P-1:-1]` against `tokens` of reference train.py:349, the `softmax().log()` of generate_beam, and the logp
+ * capdec_decode_sample reports.
+ *   - positions i >= len[r] get d_logp = 0 (and d_top1 = 0);
+ *   - a label equal to ignore_id gets d_logp = 0 and is not counted (ignore_id = -1: none; ignore_id = 0 with every len = L is
+ *     the train loss's convention);
+ *   - d_sum[r] = the sum of d_logp[r, :] over the counted positions, d_count[r] = how many there are;
+ *   - d_top1[r, i] (optional) = the arg-max id at that position;
+ *   - an id outside [0, vocab) is never used as an address: as an input it looks up row 0, and from the position it feeds on
+ *     the caption's d_logp -- and its d_sum -- are NaN; as a label it gives NaN at its own position (capdec_cross_entropy
+ *     and the train step treat such ids the same way);
+ *   - len[r] = 0 is legal: sum 0, count 0.
+ * h_lens is a HOST array ([n]; NULL = every caption has L tokens): the call plans its chunks from the lengths before it
+ * launches anything, and a device array would cost a synchronisation per call.  A chunk is a run of whole captions in
+ * input order whose padded row count, captions x (P + the chunk's longest len - 1), stays within CAPDEC_SCORE_ROWS (default
+ * 16384; at least one caption); a caption's results do not depend on the chunk it lands in beyond the summation order of
+ * the GEMMs, and not at all under capdec_set_batch_invariant (every chunk is then padded to the call's longest caption).
+ * Limits: those of capdec_gpt2_logits, P + L - 1 <= min(n_positions, 1024); head_dim 64.  A NaN temperature is an error.
+ * (Added without a new ABI number, like capdec_decode_sample.) */
+int capdec_score(capdec_ctx *ctx, const float *d_prefix /* [n, P, d] */, const int32_t *d_tokens /* [n, L] */,
+                 const int32_t *h_lens /* HOST [n], NULL = all L */, int n, int P, int L, int ignore_id,
+                 float temperature, float *d_logp /* [n, L] */, float *d_sum /* [n] or NULL */,
+                 int32_t *d_count /* [n] or NULL */, int32_t *d_top1 /* [n, L] or NULL */);
+/* *chunks = how many chunks the last capdec_score call split its captions into; 0 for an empty call. */
+int capdec_score_chunks(capdec_ctx *ctx, int *chunks);
 /* Image preprocessing in front of capdec_clip_encode_image: the `preprocess` transform clip.load returns
  * (reference predictions_runner.py:212, embeddings_generator.py:72) = Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
  * ToTensor -> Normalize(mean, std); stretch != 0 = clip_transform_full (predictions_runner.py:116-122): Resize((n_px,
