@@ -93,6 +93,12 @@ class ClipResNetWeights(C.Structure):
                 ("v_w", c_float_p), ("v_b", c_float_p), ("c_w", c_float_p), ("c_b", c_float_p)]
 
 
+class LogitsProcessors(C.Structure):
+    """capdec_logits_processors"""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int), ("min_length", C.c_int),
+                ("top_k", C.c_int)]
+
+
 #: every symbol include/capdec.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 ABI_VERSION = 6          # include/capdec.h: CAPDEC_ABI_VERSION
@@ -144,6 +150,8 @@ SIGNATURES = {
     "capdec_decode_greedy_forced": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP]),
     "capdec_decode_sample": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
                                        _VP, _VP, _VP, _VP]),
+    "capdec_set_logits_processors": (C.c_int, [_VP, C.POINTER(LogitsProcessors)]),
+    "capdec_set_logit_bias": (C.c_int, [_VP, c_float_p, C.c_int]),
     "capdec_score": (C.c_int, [_VP, _VP, _VP, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP, _VP]),
     "capdec_score_chunks": (C.c_int, [_VP, C.POINTER(C.c_int)]),
     "capdec_decode_beam": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP,

@@ -162,7 +162,7 @@ void capdec_destroy(capdec_ctx *c) {
     DBuf *bufs[] = {&c->h, &c->x, &c->qkv, &c->att, &c->ff, &c->xl, &c->tmax, &c->tsum, &c->cval, &c->cidx,
                     &c->lse, &c->topv, &c->topi, &c->kc, &c->vc, &c->tokens, &c->scores, &c->seq, &c->stopped,
                     &c->done, &c->anc, &c->next_tok, &c->alive, &c->gids, &c->glens, &c->m_hid, &c->m_lin, &c->m_seq,
-                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->lmflag, &c->xpk2, &c->slogits, &c->s_plan, &c->s_rows, &c->s_logit, &c->s_bad, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
+                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->lmflag, &c->xpk2, &c->slogits, &c->s_plan, &c->s_rows, &c->s_logit, &c->s_bad, &c->pbias, &c->pcorr, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
                     &c->r_a, &c->r_b, &c->r_c, &c->r_d, &c->r_e, &c->r_f, &c->r_col, &c->r_pk1, &c->r_pk2, &c->r_xpk,
                     &c->r_ypk, &c->r_xi, &c->r_idp, &c->r_zero};
     for (DBuf *b : bufs) b->release();
@@ -252,6 +252,47 @@ int capdec_decode_stats(capdec_ctx *c, int *steps, int *compactions, long long *
 int capdec_set_compact(capdec_ctx *c, int on) {
     CAPDEC_CHECK(c, "null context");
     c->compact = on != 0;
+    return 0;
+}
+
+int capdec_set_logits_processors(capdec_ctx *c, const capdec_logits_processors *p) {
+    CAPDEC_CHECK(c, "null context");
+    if (!p) {
+        c->proc = LogitsProc();
+        return 0;
+    }
+    CAPDEC_CHECK(p->repetition_penalty > 0.f && p->repetition_penalty < INFINITY,
+                 "set_logits_processors: repetition_penalty must be a finite number > 0 (1 = off)");
+    CAPDEC_CHECK(p->no_repeat_ngram_size >= 0 && p->min_length >= 0 && p->top_k >= 0,
+                 "set_logits_processors: no_repeat_ngram_size, min_length and top_k must be >= 0 (0 = off)");
+    c->proc.theta = p->repetition_penalty;
+    c->proc.ngram = p->no_repeat_ngram_size;
+    c->proc.min_len = p->min_length;
+    c->proc.top_k = p->top_k;
+    return 0;
+}
+
+int capdec_set_logit_bias(capdec_ctx *c, const float *h_bias, int vocab) {
+    CAPDEC_CHECK(c, "null context");
+    if (!h_bias) {
+        c->proc_bias_n = 0;
+        return 0;
+    }
+    CAPDEC_CHECK(c->gpt.loaded, "set_logit_bias: GPT-2 weights not loaded");
+    CAPDEC_CHECK(vocab == c->gpt.vocab, "set_logit_bias: the bias must have one entry per vocabulary token");
+    int finite = 0;
+    for (int j = 0; j < vocab; ++j) {
+        const float b = h_bias[j];
+        CAPDEC_CHECK(b == b && b != INFINITY, "set_logit_bias: entries must be finite or -inf (NaN or +inf found)");
+        finite += b != -INFINITY;
+    }
+    // a step bans at most entry_length + 1 <= 1025 tokens (the history, the two stop ids): a row can always emit one
+    CAPDEC_CHECK(finite >= 1026, "set_logit_bias: fewer than 1026 finite entries");
+    CAPDEC_HIP(hipSetDevice(c->device));
+    CAPDEC_HIP(hipStreamSynchronize(c->stream));              // (a decode still in flight reads the old values)
+    CAPDEC_TRY(c->pbias.ensure((size_t)vocab * sizeof(float)));
+    CAPDEC_HIP(hipMemcpy(c->pbias.p, h_bias, (size_t)vocab * sizeof(float), hipMemcpyHostToDevice));
+    c->proc_bias_n = vocab;
     return 0;
 }
 

@@ -362,6 +362,25 @@ int launch_greedy_step(hipStream_t st, const int *top_idx, int rows, int step, i
 int launch_sample_top_p(hipStream_t st, const float *logits, int ld, int rows, int row0, int V, float inv_temp, float top_p,
                         uint64_t seed, const float *u, int cap_off, int step, int T, int stop_id, int alt_stop_id, int *ids,
                         int *lens, uint8_t *done, int *next_tok, int *alive_count, float *logp, const int *cmap);
+// process.hip: the logits processors (capdec_set_logits_processors) over materialised logits [rows, ld], in place; logits
+// row r is activation row row0 + r of the step and finds its history -- hist [captions, beam, T], the first `step` entries
+// -- through cmap and beam as the greedy / beam step kernels find their rows.  bias [V] or nullptr.
+struct LogitsProc {
+    float theta = 1.0f;                    // repetition penalty (1 = off)
+    int ngram = 0, min_len = 0, top_k = 0; // 0 = off; top_k acts in the sampling decode only
+};
+int launch_logits_process(hipStream_t st, float *logits, int ld, int rows, int row0, int V, const int *cmap, int beam,
+                          const int *hist, int T, int step, const LogitsProc &p, const float *bias, int stop_id,
+                          int alt_stop_id);
+// ... logsumexp and the k best of every row, one pass: what launch_topk_merge leaves in lse [rows], top_val / top_idx [rows, k]
+int launch_logits_select(hipStream_t st, const float *logits, int ld, int rows, int V, int k, float inv_temp, float *lse,
+                         float *top_val, int *top_idx);
+// ... everything below a row's top_k-th largest value becomes -inf (no launch when top_k <= 0 or top_k >= V); corr [rows]
+// (may be nullptr) receives logsumexp(kept) - logsumexp(all) of the scaled row, which launch_logp_shift adds to the logp
+// of the rows that emitted a token at `step`
+int launch_logits_topk(hipStream_t st, float *logits, int ld, int rows, int V, int top_k, float inv_temp, float *corr);
+int launch_logp_shift(hipStream_t st, const float *corr, int rows, int row0, const int *cmap, const int *lens, int step, int T,
+                      float *logp);
 // mean over the rows with label != ignore_index of logsumexp(logits[row]) - logits[row][label]; nll_ws: rows floats
 int launch_cross_entropy_mean(hipStream_t st, const float *logits, int ld, const int *labels, int rows, int V,
                               int ignore_index, float *nll_ws, float *out);

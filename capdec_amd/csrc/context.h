@@ -5,7 +5,7 @@
 //   gemm_dispatch.hip the GEMM planner: operand planes cache, which kernel / split for a projection and for the fused
 //                     lm_head, capdec_gemm_f32
 //   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam / sampling decode loop
-//                     (the sampling kernel itself: sample.hip)
+//                     (the sampling kernel itself: sample.hip; the logits processors' kernels: process.hip)
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
 //                     forward share (tlayer_self_front / tlayer_tail)
@@ -180,10 +180,14 @@ struct capdec_ctx {
     int train_scope = 0;                     // capdec_train_set_scope: survives capdec_train_reset and weight reloads
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
     unsigned long long train_drop_seed = 0;  // ... key of the Philox keep-mask stream (counter = element, train step)
-    DBuf slogits;          // sampling decode: fp32 logits of one row block, [min(rows, tune.sample_rows), ld] (decode.hip: lm_head_sample)
+    DBuf slogits;          // sampling decode, logits processors: fp32 logits of one row block, [min(rows, tune.sample_rows), ld]
+                           // (decode.hip: lm_head_sample, lm_head_process)
     DBuf s_plan, s_rows, s_logit, s_bad;   // capdec_score (score.hip): the call's plan [lens | row offsets | h rows | targets], a
                                            // chunk's scored rows of h [R, d], their label logits [R], first tainted position [nc]
     int stat_score_chunks = 0;             // chunks of the last capdec_score call (capdec_score_chunks)
+    capdec::LogitsProc proc;               // capdec_set_logits_processors (defaults: every processor off)
+    int proc_bias_n = 0;                   // capdec_set_logit_bias: entries of `pbias` (0 = no bias)
+    DBuf pbias, pcorr;     // the logit bias [vocab]; a row block's logp shift under top_k (decode.hip: lm_head_process)
     DBuf lmflag, xpk2;     // fused lm_head with 3 candidates per tile: [count, total, rows...] of the rows whose top 5 need
                            // the exact second pass; their compacted packed A operand (decode.hip: lm_head_select)
     DBuf m_hid, m_lin, m_seq, m_x, m_qkv, m_att, m_ff;

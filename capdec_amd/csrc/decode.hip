@@ -193,6 +193,54 @@ static int lm_head_sample(capdec_ctx *c, const float *h0, int ldh, int R, float 
     return 0;
 }
 
+// Does this call run the logits processors (capdec_set_logits_processors / capdec_set_logit_bias)?  top_k counts in the
+// sampling decode only.
+static bool processors_on(const capdec_ctx *c, bool sampling) {
+    const LogitsProc &p = c->proc;
+    return p.theta != 1.0f || p.ngram > 0 || p.min_len > 0 || c->proc_bias_n > 0 || (sampling && p.top_k > 0);
+}
+
+// One step over `R` activation rows with the logits processors: per block of tune.sample_rows rows, lm_head_logits, the
+// processors in place (process.hip), then the one-pass selection at the block's offset into c->lse / c->topv / c->topi
+// (greedy, beam: what lm_head_select leaves, the step kernels follow unchanged) or, with `smp`, top_k and the
+// nucleus-sampling kernel (what lm_head_sample does).  hist: the rows' histories [captions, beam, T] -- `ids` or
+// BeamState::tokens; `step` entries of each are read.
+static int lm_head_process(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const SampleArgs *smp,
+                           int step, int T, int beam, int stop_id, int alt_stop_id, const int *hist, int *ids, int *lens,
+                           const int *cmap) {
+    const int V = c->gpt.vocab, ld = (V + 63) / 64 * 64, blk = std::min(R, std::max(1, c->tune.sample_rows));
+    const LogitsProc &p = c->proc;
+    const float *bias = c->proc_bias_n > 0 ? c->pbias.as<float>() : nullptr;
+    const bool cut = smp && p.top_k > 0 && p.top_k < V;
+    CAPDEC_TRY(c->slogits.ensure((size_t)blk * ld * 4));
+    if (!smp) {
+        CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
+        CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
+        CAPDEC_TRY(c->topi.ensure((size_t)R * k * 4));
+    } else if (cut && smp->logp) {
+        CAPDEC_TRY(c->pcorr.ensure((size_t)blk * 4));
+    }
+    float *lg = c->slogits.as<float>();
+    for (int r0 = 0; r0 < R; r0 += blk) {
+        const int nr = std::min(blk, R - r0);
+        CAPDEC_TRY(lm_head_logits(c, h0 + (size_t)r0 * ldh, ldh, nr, lg, ld));
+        ProfScope ps(c, F_SELECT);
+        CAPDEC_TRY(launch_logits_process(c->stream, lg, ld, nr, r0, V, cmap, beam, hist, T, step, p, bias, stop_id, alt_stop_id));
+        if (!smp) {
+            CAPDEC_TRY(launch_logits_select(c->stream, lg, ld, nr, V, k, inv_temp, c->lse.as<float>() + r0,
+                                            c->topv.as<float>() + (size_t)r0 * k, c->topi.as<int>() + (size_t)r0 * k));
+            continue;
+        }
+        float *corr = cut && smp->logp ? c->pcorr.as<float>() : nullptr;
+        if (cut) CAPDEC_TRY(launch_logits_topk(c->stream, lg, ld, nr, V, p.top_k, inv_temp, corr));
+        CAPDEC_TRY(launch_sample_top_p(c->stream, lg, ld, nr, r0, V, inv_temp, smp->top_p, smp->seed, smp->u, smp->cap_off, step, T,
+                                       stop_id, alt_stop_id, ids, lens, c->done.as<uint8_t>(), c->next_tok.as<int>(),
+                                       c->alive.as<int>(), smp->logp, cmap));
+        if (corr) CAPDEC_TRY(launch_logp_shift(c->stream, corr, nr, r0, cmap, lens, step, T, smp->logp));
+    }
+    return 0;
+}
+
 // geometry only (the CLIP towers attend straight from the qkv activations and never touch a cache)
 void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd) {
     kv.rows = rows;
@@ -256,6 +304,7 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     const int rows = nc * beam;
     const int k = (greedy && stats) ? 2 : beam;   // candidates kept per row (teacher-forced statistics: top-2)
     const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);
+    const bool proc = !forced && processors_on(c, smp != nullptr);      // (teacher forcing ignores the processors)
     KvCache kv;
     CAPDEC_TRY(ensure_kv(c, kv, rows, ctx));
     kv.fixed_variant = c->batch_invariant;
@@ -301,10 +350,15 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     sp.P = P;
     sp.beam = beam;
     CAPDEC_TRY(gpt2_body(c, sp, kv));
-    if (!smp) CAPDEC_TRY(lm_head_select(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp));
+    const int *hist = greedy ? ids : bs.tokens;       // the rows' own histories, for the logits processors
+    if (proc)       // (one row per caption and an empty history: nothing is read through `hist` yet)
+        CAPDEC_TRY(lm_head_process(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp, smp, 0, T, 1, stop_id,
+                                   alt_stop_id, hist, ids, lens, nullptr));
+    else if (!smp) CAPDEC_TRY(lm_head_select(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp));
     if (smp) {
-        CAPDEC_TRY(lm_head_sample(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, inv_temp, *smp, 0, T, stop_id,
-                                  alt_stop_id, ids, lens, nullptr));
+        if (!proc)
+            CAPDEC_TRY(lm_head_sample(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, inv_temp, *smp, 0, T, stop_id,
+                                      alt_stop_id, ids, lens, nullptr));
     } else if (greedy) {
         ProfScope ps(c, F_SELECT);
         CAPDEC_TRY(launch_greedy_step(c->stream, c->topi.as<int>(), nc, 0, T, stop_id, alt_stop_id, ids, lens,
@@ -368,11 +422,16 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
         sd.anc_stride = ctx;
         sd.cmap = cmap;
         CAPDEC_TRY(gpt2_body(c, sd, kv));
-        if (smp) {
+        if (proc) {
+            CAPDEC_TRY(lm_head_process(c, c->h.as<float>(), d, arows, k, inv_temp, smp, i, T, beam, stop_id, alt_stop_id, hist,
+                                       ids, lens, cmap));
+            if (smp) continue;
+        } else if (smp) {
             CAPDEC_TRY(lm_head_sample(c, c->h.as<float>(), d, arows, inv_temp, *smp, i, T, stop_id, alt_stop_id, ids, lens, cmap));
             continue;
+        } else {
+            CAPDEC_TRY(lm_head_select(c, c->h.as<float>(), d, arows, k, inv_temp));
         }
-        CAPDEC_TRY(lm_head_select(c, c->h.as<float>(), d, arows, k, inv_temp));
         ProfScope ps(c, F_SELECT);
         if (greedy) {
             CAPDEC_TRY(launch_greedy_step(c->stream, c->topi.as<int>(), arows, i, T, stop_id, alt_stop_id, ids, lens,
@@ -399,6 +458,8 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int b
     CAPDEC_CHECK(P + T - 1 <= 1024 && T <= 1024, "decode: context or entry_length > 1024 not supported");
     CAPDEC_CHECK(beam >= 1 && beam <= 8, "decode: beam size must be in 1..8");
     CAPDEC_CHECK(c->gpt.d / c->gpt.n_head == 64, "decode: head_dim must be 64");
+    CAPDEC_CHECK(forced || c->proc_bias_n == 0 || c->proc_bias_n == c->gpt.vocab,
+                 "decode: the logit bias was set for another vocabulary");
     CAPDEC_HIP(hipSetDevice(c->device));
     c->stat_steps = n > 0 ? 1 : 0;
     c->stat_compactions = 0;

@@ -3,7 +3,10 @@ CUDA(HIP) tensors to the C ABI.  torch is plumbing only (device memory, streams)
 arithmetic happens in libcapdec_hip.so."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import dataclasses
+import math
 import os
 from typing import Dict, Optional, Tuple
 
@@ -22,6 +25,41 @@ def _f32(t: torch.Tensor) -> np.ndarray:
 
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(_capi.c_float_p)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class LogitsProcessors:
+    """What steers a decode (capdec_set_logits_processors / capdec_set_logit_bias; the contract: include/capdec.h).  The
+    defaults switch everything off.  ``top_k`` acts in the sampling decode only; ``logit_bias`` is a HOST vector [vocab]
+    (tensor, array or list) of finite or ``-inf`` entries."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_length: int = 0
+    top_k: int = 0
+    logit_bias: Optional[object] = None
+
+    def __post_init__(self):
+        t = self.repetition_penalty
+        if not (isinstance(t, (int, float)) and t > 0 and math.isfinite(t)):
+            raise CapdecError(f"LogitsProcessors: repetition_penalty must be a finite number > 0 (1 = off), got {t!r}")
+        for name in ("no_repeat_ngram_size", "min_length", "top_k"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise CapdecError(f"LogitsProcessors: {name} must be an integer >= 0 (0 = off), got {v!r}")
+
+    @property
+    def active(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or self.min_length > 0 or self.top_k > 0
+                or self.logit_bias is not None)
+
+    @classmethod
+    def of(cls, base: Optional["LogitsProcessors"] = None, **kw) -> Optional["LogitsProcessors"]:
+        """``base`` (may be None) with the keywords that are not None put on top; None when nothing is left switched on"""
+        kw = {k: v for k, v in kw.items() if v is not None}
+        if base is not None and not isinstance(base, cls):
+            raise CapdecError(f"logits_processors must be a LogitsProcessors, got {type(base).__name__}")
+        p = dataclasses.replace(base, **kw) if base is not None else cls(**kw)
+        return p if p.active else None
 
 
 class Engine:
@@ -387,8 +425,56 @@ class Engine:
         return out.view(*shape, -1)
 
     # ------------------------------------------------------------------ decode
+    def set_logits_processors(self, processors: Optional[LogitsProcessors] = None):
+        """the processors of the following decode calls (capdec_set_logits_processors; None: none).  The ``logit_bias`` of
+        ``processors`` is NOT touched here: :meth:`set_logit_bias`"""
+        if processors is None:
+            self._chk(self.lib.capdec_set_logits_processors(self._h, None), "set_logits_processors")
+            return
+        if not isinstance(processors, LogitsProcessors):
+            raise CapdecError(f"set_logits_processors takes a LogitsProcessors, got {type(processors).__name__}")
+        st = _capi.LogitsProcessors(float(processors.repetition_penalty), int(processors.no_repeat_ngram_size),
+                                    int(processors.min_length), int(processors.top_k))
+        self._chk(self.lib.capdec_set_logits_processors(self._h, C.byref(st)), "set_logits_processors")
+
+    def set_logit_bias(self, bias=None):
+        """a constant added to every row's logits in the following decode calls (capdec_set_logit_bias): a host vector
+        [vocab] of finite or ``-inf`` entries, validated by the library and uploaded once; None: none"""
+        if bias is None:
+            self._chk(self.lib.capdec_set_logit_bias(self._h, None, 0), "set_logit_bias")
+            return
+        b = bias.detach().to("cpu", torch.float32).numpy() if isinstance(bias, torch.Tensor) else np.asarray(bias, dtype=np.float32)
+        b = np.ascontiguousarray(b.reshape(-1))
+        self._chk(self.lib.capdec_set_logit_bias(self._h, _fp(b), int(b.shape[0])), "set_logit_bias")
+
+    @contextlib.contextmanager
+    def _processors(self, base=None, **kw):
+        """set the processors (and the bias) for the one decode call inside, clear them afterwards -- also when the call
+        raises.  With nothing switched on the context's state is left alone."""
+        p = LogitsProcessors.of(base, **kw)
+        if p is None:
+            yield
+            return
+        try:
+            self.set_logits_processors(p)
+            if p.logit_bias is not None:
+                self.set_logit_bias(p.logit_bias)
+            yield
+        finally:
+            self.set_logits_processors(None)
+            self.set_logit_bias(None)
+
     def decode_greedy(self, prefix_embed: torch.Tensor, stop_id: int, entry_length: int = 67,
-                      alt_stop_id: int = 764) -> Tuple[torch.Tensor, torch.Tensor]:
+                      alt_stop_id: int = 764, *, repetition_penalty: Optional[float] = None,
+                      no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None,
+                      logit_bias=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The keyword-only processors (None: off) are set for this call and cleared after it; without any, the call
+        runs under whatever :meth:`set_logits_processors` / :meth:`set_logit_bias` left on the context."""
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias):
+            return self._decode_greedy(prefix_embed, stop_id, entry_length, alt_stop_id)
+
+    def _decode_greedy(self, prefix_embed, stop_id, entry_length, alt_stop_id):
         p = self._dev(prefix_embed)
         n, P, _ = p.shape
         ids = torch.empty(n, entry_length, device=self.device, dtype=torch.int32)
@@ -400,11 +486,19 @@ class Engine:
 
     def decode_sample(self, prefix_embed: torch.Tensor, stop_id: int, entry_length: int = 67, temperature: float = 1.0,
                       top_p: float = 0.8, seed: int = 0, u: Optional[torch.Tensor] = None, alt_stop_id: int = 764,
-                      return_logp: bool = False):
+                      return_logp: bool = False, *, repetition_penalty: Optional[float] = None,
+                      no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None, logit_bias=None,
+                      top_k: Optional[int] = None):
         """nucleus-sampling decode (capdec_decode_sample): -> ids [n, T] (zero padded), lens [n] (including the stop
         token) and, with ``return_logp``, logp [n, T] of the chosen tokens under the unfiltered temperature-scaled
         distribution.  ``u`` [n, T] in [0, 1) injects the uniforms; None draws them from the device Philox keyed by
-        (``seed``, caption index, step)"""
+        (``seed``, caption index, step).  The keyword-only processors as in :meth:`decode_greedy`, plus ``top_k``"""
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias, top_k=top_k):
+            return self._decode_sample(prefix_embed, stop_id, entry_length, temperature, top_p, seed, u, alt_stop_id,
+                                       return_logp)
+
+    def _decode_sample(self, prefix_embed, stop_id, entry_length, temperature, top_p, seed, u, alt_stop_id, return_logp):
         top_p, temperature = float(top_p), float(temperature)
         if top_p != top_p or temperature != temperature:
             raise CapdecError("decode_sample: top_p or temperature is NaN")
@@ -438,10 +532,16 @@ class Engine:
         return ids, stats
 
     def decode_beam(self, prefix_embed: torch.Tensor, stop_id: int, beam_size: int = 5, entry_length: int = 67,
-                    temperature: float = 1.0):
+                    temperature: float = 1.0, *, repetition_penalty: Optional[float] = None,
+                    no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None, logit_bias=None):
         """-> ids [n, beam, T], lens [n, beam], mean-log-prob scores [n, beam] (sorted by score
         descending, like the list generate_beam returns) and order [n, beam] (reference's
-        internal beam index of each returned row)."""
+        internal beam index of each returned row).  The keyword-only processors as in :meth:`decode_greedy`."""
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias):
+            return self._decode_beam(prefix_embed, stop_id, beam_size, entry_length, temperature)
+
+    def _decode_beam(self, prefix_embed, stop_id, beam_size, entry_length, temperature):
         p = self._dev(prefix_embed)
         n, P, _ = p.shape
         ids = torch.empty(n, beam_size, entry_length, device=self.device, dtype=torch.int32)

@@ -177,6 +177,9 @@ class ClipCaptionModel(_HipModule):
         self.mapping_type = mapping_type
         self.gpt_dims = gpt2_dims
         self.gpt_embedding_size = gpt2_dims.n_embd
+        #: an ``engine.LogitsProcessors`` (or None) that ``generate2`` / ``generate_beam`` and, without keywords of their
+        #: own, the batched decode functions of gpt2_prefix_eval apply
+        self.logits_processors = None
         self.gpt = _Gpt2Facade(self)
         if mapping_type == MappingType.TransformerEncoder:
             self.clip_project = transformer_mapper.TransformerMapper(prefix_dim, self.gpt_embedding_size, prefix_length,

@@ -4,7 +4,12 @@
 no-cache re-forward and the per-token host syncs of the reference are replaced by one call
 into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``).  ``generate_samples`` /
 ``generate_samples_batch`` make ``top_p``, ``temperature`` and ``entry_count`` live: nucleus sampling
-(``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178)."""
+(``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178).
+
+Logits processors (``engine.LogitsProcessors``; the contract: include/capdec.h).  The batched functions take them as
+keyword-only arguments (None: not given); ``generate2`` / ``generate_beam`` keep the reference's signatures and read
+``model.logits_processors`` instead, which is also what a batched function starts from before its own keywords go on top.
+Whatever is switched on is set on the engine for the one decode call and cleared after it."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -13,6 +18,7 @@ import numpy as np
 import torch
 
 from ._capi import CapdecError
+from .engine import LogitsProcessors
 from .gpt2_prefix import ClipCaptionModel
 from .train import _next_seed
 
@@ -30,43 +36,74 @@ def _prefix_from(model, tokenizer, tokens, prompt, embed) -> Tuple[torch.Tensor,
     return model.gpt.transformer.wte(tokens), [int(t) for t in tokens.reshape(-1).tolist()]
 
 
+def _processor_kw(model, sampling: bool = False, **kw) -> dict:
+    """the processor keywords of the engine's decode call: ``model.logits_processors`` with the given (not None) keywords
+    on top; only what is switched on is passed, so a call without processors is the call it always was.  ``top_k`` goes
+    to the sampling decode only."""
+    p = LogitsProcessors.of(getattr(model, "logits_processors", None), **kw)
+    if p is None:
+        return {}
+    out = {}
+    if p.repetition_penalty != 1.0:
+        out["repetition_penalty"] = p.repetition_penalty
+    if p.no_repeat_ngram_size:
+        out["no_repeat_ngram_size"] = p.no_repeat_ngram_size
+    if p.min_length:
+        out["min_length"] = p.min_length
+    if p.logit_bias is not None:
+        out["logit_bias"] = p.logit_bias
+    if sampling and p.top_k:
+        out["top_k"] = p.top_k
+    return out
+
+
 # --------------------------------------------------------------------------- batched id-level API
 def decode_greedy_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, entry_length: int = 67,
-                      alt_stop_id: int = ALT_STOP_ID) -> Tuple[torch.Tensor, torch.Tensor]:
+                      alt_stop_id: int = ALT_STOP_ID, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                      min_length: Optional[int] = None, logit_bias=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """embed [N, P, d] -> ids int32 [N, entry_length] (zero padded), lens int32 [N] (tokens
     emitted INCLUDING the stop token) -- device tensors."""
-    return model.engine.decode_greedy(embed, stop_token_index, entry_length, alt_stop_id)
+    kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    return model.engine.decode_greedy(embed, stop_token_index, entry_length, alt_stop_id, **kw)
 
 
 def decode_beam_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, beam_size: int = 5,
-                    entry_length: int = 67, temperature: float = 1.0):
+                    entry_length: int = 67, temperature: float = 1.0, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                    min_length: Optional[int] = None, logit_bias=None):
     """embed [N, P, d] -> (ids [N, beam, T], lens [N, beam], scores [N, beam], order [N, beam]),
     beams sorted by mean log-prob descending (the order generate_beam returns)."""
-    return model.engine.decode_beam(embed, stop_token_index, beam_size, entry_length, temperature)
+    kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    return model.engine.decode_beam(embed, stop_token_index, beam_size, entry_length, temperature, **kw)
 
 
 def sample_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, entry_length: int = 67,
                top_p: float = 0.8, temperature: float = 1., seed: Optional[int] = None, u: Optional[torch.Tensor] = None,
-               alt_stop_id: int = ALT_STOP_ID, return_logp: bool = False):
+               alt_stop_id: int = ALT_STOP_ID, return_logp: bool = False, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+               min_length: Optional[int] = None, logit_bias=None,
+               top_k: Optional[int] = None):
     """embed [N, P, d] -> ids int32 [N, entry_length] (zero padded), lens int32 [N] (including the stop token), drawn
     by nucleus sampling: one uniform per (caption, step), from ``u`` [N, entry_length] or from the device Philox keyed by
     (``seed``, caption index, step); ``seed=None`` takes the process's next key
     (``train._next_seed``: torch's global seed and the number of keys drawn so far), so successive calls differ and a
     program that seeds torch and makes the same calls in the same order repeats its captions."""
+    kw = _processor_kw(model, True, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias, top_k=top_k)
     return model.engine.decode_sample(embed, stop_token_index, entry_length, temperature, top_p,
-                                      _next_seed() if seed is None else seed, u, alt_stop_id, return_logp)
+                                      _next_seed() if seed is None else seed, u, alt_stop_id, return_logp, **kw)
 
 
 def generate_samples_batch(model, tokenizer, embed: torch.Tensor, entry_count: int = 1, entry_length: int = 67,
                            top_p: float = 0.8, temperature: float = 1., stop_token: str = '.',
-                           seed: Optional[int] = None) -> List[List[str]]:
+                           seed: Optional[int] = None, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                           min_length: Optional[int] = None, logit_bias=None,
+                           top_k: Optional[int] = None) -> List[List[str]]:
     """embed [N, P, d] -> ``entry_count`` sampled texts per caption.  Every prefix row is repeated ``entry_count``
     times; each repeat is a caption index of its own (caption r, entry e -> index r * entry_count + e) and so has its
     own draws."""
     if entry_count < 1:
         raise CapdecError("generate_samples_batch: entry_count must be >= 1")
     stop = tokenizer.encode(stop_token)[0]
-    ids, lens = sample_ids(model, embed.repeat_interleave(entry_count, dim=0), stop, entry_length, top_p, temperature, seed)
+    ids, lens = sample_ids(model, embed.repeat_interleave(entry_count, dim=0), stop, entry_length, top_p, temperature, seed,
+                           repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias, top_k=top_k)
     ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
     return [[tokenizer.decode(list(ids[r * entry_count + e, :lens[r * entry_count + e]])) for e in range(entry_count)]
             for r in range(embed.shape[0])]
@@ -108,17 +145,20 @@ def score_captions(model, tokenizer, embed: torch.Tensor, texts, temperature: fl
     return out if flat else [out[r * K:(r + 1) * K] for r in range(n)]
 
 
-def generate2_batch(model, tokenizer, embed: torch.Tensor, entry_length: int = 67, stop_token: str = '.') -> List[str]:
+def generate2_batch(model, tokenizer, embed: torch.Tensor, entry_length: int = 67, stop_token: str = '.', *,
+                    repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                    min_length: Optional[int] = None, logit_bias=None) -> List[str]:
     stop = tokenizer.encode(stop_token)[0]
-    ids, lens = decode_greedy_ids(model, embed, stop, entry_length)
+    ids, lens = decode_greedy_ids(model, embed, stop, entry_length, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
     return [tokenizer.decode(list(ids[r, :lens[r]])) for r in range(ids.shape[0])]
 
 
 def generate_beam_batch(model, tokenizer, embed: torch.Tensor, beam_size: int = 5, entry_length: int = 67,
-                        temperature: float = 1., stop_token: str = '.') -> List[List[str]]:
+                        temperature: float = 1., stop_token: str = '.', *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                        min_length: Optional[int] = None, logit_bias=None) -> List[List[str]]:
     stop = tokenizer.encode(stop_token)[0]
-    ids, lens, _, _ = decode_beam_ids(model, embed, stop, beam_size, entry_length, temperature)
+    ids, lens, _, _ = decode_beam_ids(model, embed, stop, beam_size, entry_length, temperature, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
     return [[tokenizer.decode(ids[r, b, :int(lens[r, b])]) for b in range(ids.shape[1])] for r in range(ids.shape[0])]
 
@@ -126,7 +166,8 @@ def generate_beam_batch(model, tokenizer, embed: torch.Tensor, beam_size: int = 
 # --------------------------------------------------------------------------- reference signatures
 def generate_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 5, prompt=None, embed=None,
                   entry_length=67, temperature=1., stop_token: str = '.'):
-    """reference gpt2_prefix_eval.py:50-115 -> List[str] of ``beam_size`` texts, best first."""
+    """reference gpt2_prefix_eval.py:50-115 -> List[str] of ``beam_size`` texts, best first.  (Logits processors:
+    ``model.logits_processors``.)"""
     model.eval()
     prefix, prompt_ids = _prefix_from(model, tokenizer, None, prompt, embed)
     if prefix.shape[0] != 1:
@@ -149,7 +190,8 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
     """reference gpt2_prefix_eval.py:118-198 -> str.  ``top_p`` is accepted and has no effect,
     exactly as in the reference: the filter never removes the arg-max (:172), and the next
     token is ``argmax`` (:177); ``temperature`` > 0 does not change an arg-max either.  ``generate_samples`` /
-    ``generate_samples_batch`` are the entry points where the three parameters act."""
+    ``generate_samples_batch`` are the entry points where the three parameters act.  (Logits processors:
+    ``model.logits_processors``.)"""
     model.eval()
     prefix, prompt_ids = _prefix_from(model, tokenizer, tokens, prompt, embed)
     if prefix.shape[0] != 1:
@@ -168,7 +210,9 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
 
 
 def generate_samples(model, tokenizer, tokens=None, prompt=None, embed=None, entry_count=1, entry_length=67,
-                     top_p=0.8, temperature=1., stop_token: str = '.', seed: Optional[int] = None) -> List[str]:
+                     top_p=0.8, temperature=1., stop_token: str = '.', seed: Optional[int] = None, *,
+                     repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                     min_length: Optional[int] = None, logit_bias=None, top_k: Optional[int] = None) -> List[str]:
     """``generate2``'s signature plus ``seed`` -> ``entry_count`` texts drawn by nucleus sampling from one caption
     ([1, P, d]); prompt tokens stay in front of every text, as in ``generate2``."""
     model.eval()
@@ -178,6 +222,7 @@ def generate_samples(model, tokenizer, tokens=None, prompt=None, embed=None, ent
     if entry_count < 1:
         raise CapdecError("generate_samples: entry_count must be >= 1")
     stop = tokenizer.encode(stop_token)[0]
-    ids, lens = sample_ids(model, prefix.repeat_interleave(entry_count, dim=0), stop, entry_length, top_p, temperature, seed)
+    ids, lens = sample_ids(model, prefix.repeat_interleave(entry_count, dim=0), stop, entry_length, top_p, temperature, seed,
+                           repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias, top_k=top_k)
     ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
     return [tokenizer.decode((prompt_ids or []) + [int(t) for t in ids[e, :lens[e]]]) for e in range(entry_count)]

@@ -56,6 +56,11 @@ class Timer:
         return s
 
 
+def _given(**kw) -> Dict:
+    """the logits-processor keywords a caller did give (None = not given: ``model.logits_processors`` decides)"""
+    return {k: v for k, v in kw.items() if v is not None}
+
+
 def prefix_from_embeddings(model: ClipCaptionModel, embeddings: torch.Tensor, dont_normalize_prefix: bool = False,
                            modality_offset: Optional[torch.Tensor] = None) -> torch.Tensor:
     """reference :221-228 for a batch: ``prefix / prefix.norm(2,-1)``; ``+ offset``;
@@ -67,26 +72,33 @@ def prefix_from_embeddings(model: ClipCaptionModel, embeddings: torch.Tensor, do
 
 def caption_ids(model: ClipCaptionModel, embeddings: torch.Tensor, stop_token_index: int, beam: bool = True,
                 beam_size: int = 5, entry_length: int = 67, dont_normalize_prefix: bool = False,
-                modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1):
+                modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1, *,
+                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                min_length: Optional[int] = None, logit_bias=None):
     """The whole device-side path for this rank's shard of ``embeddings`` [N, D].
     Returns (ids [n_local, T] int32 of the best caption, lens [n_local]) and, for beam, the
-    mean-log-prob score of the best beam."""
+    mean-log-prob score of the best beam.  The keyword-only logits processors (None: ``model.logits_processors``'s) are
+    those of ``decode_beam_ids`` / ``decode_greedy_ids``."""
+    pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     lo, hi = cdist.shard_bounds(embeddings.shape[0], rank, world)
     pe = prefix_from_embeddings(model, embeddings[lo:hi], dont_normalize_prefix, modality_offset)
     if beam:
-        ids, lens, scores, _ = decode_beam_ids(model, pe, stop_token_index, beam_size, entry_length)
+        ids, lens, scores, _ = decode_beam_ids(model, pe, stop_token_index, beam_size, entry_length, **pk)
         return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
-    ids, lens = decode_greedy_ids(model, pe, stop_token_index, entry_length)
+    ids, lens = decode_greedy_ids(model, pe, stop_token_index, entry_length, **pk)
     return ids, lens, None
 
 
 def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptionModel, tokenizer,
                out_path: Optional[str] = None, beam: bool = True, entry_length: int = 67,
                dont_normalize_prefix: bool = False, modality_offset: Optional[torch.Tensor] = None,
-               rank: int = 0, world: int = 1, timer: Optional[Timer] = None) -> List[Dict]:
+               rank: int = 0, world: int = 1, timer: Optional[Timer] = None, *,
+               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+               min_length: Optional[int] = None, logit_bias=None) -> List[Dict]:
     """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  Writes the
     reference's predictions JSON (``[{"caption": lower-cased text, "image_id": id}]``, :260-261,
     :301) -- the whole list, not only every 99th flush."""
+    pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     cdist.check_world(rank, world)
     if len(data) != embeddings.shape[0]:
         raise ValueError(f"make_preds: {len(data)} data entries but {embeddings.shape[0]} embeddings")
@@ -94,13 +106,13 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
     if timer is not None:           # the reference's `with timer:` (:214-233) around this rank's share of the batch
         with timer.bind(model):
             ids, lens, _ = caption_ids(model, embeddings, stop, beam, 5, entry_length, dont_normalize_prefix,
-                                       modality_offset, rank, world)
+                                       modality_offset, rank, world, **pk)
         lo, hi = cdist.shard_bounds(embeddings.shape[0], rank, world)
         timer.add_items(hi - lo)
         print(timer)                # (:253)
     else:
         ids, lens, _ = caption_ids(model, embeddings, stop, beam, 5, entry_length, dont_normalize_prefix,
-                                   modality_offset, rank, world)
+                                   modality_offset, rank, world, **pk)
     ids, lens, _ = cdist.gather_ids(ids, lens, embeddings.shape[0])
     ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
     new_data = [{"caption": tokenizer.decode(list(ids[i, :int(lens[i])])).lower(), "image_id": d["image_id"]}
@@ -115,7 +127,8 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
                            tokenizer, out_path: Optional[str] = None, beam: bool = True, is_rn: bool = False,
                            entry_length: int = 67, dont_normalize_prefix: bool = False,
                            modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
-                           image_batch: int = 256) -> List[Dict]:
+                           image_batch: int = 256, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                           min_length: Optional[int] = None, logit_bias=None) -> List[Dict]:
     """The image half of the reference loop in front of ``make_preds`` (:156-161, :207-220): ``images[i]`` is what
     ``Image.open(filename).convert("RGB")`` gave for ``data[i]`` (a PIL image or a uint8 [H, W, 3] array), or ``None``
     for a file the reference would skip (:207-210: the entry is left out of the output).  ``preprocess`` and
@@ -143,7 +156,8 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
     stop = tokenizer.encode('.')[0]
     T = entry_length
     if feats:
-        ids, lens, _ = caption_ids(model, torch.cat(feats), stop, beam, 5, T, dont_normalize_prefix, modality_offset)
+        ids, lens, _ = caption_ids(model, torch.cat(feats), stop, beam, 5, T, dont_normalize_prefix, modality_offset,
+                                   **_given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias))
     else:                              # an empty shard (more ranks than images) still takes part in the gather
         dev = next(model.parameters()).device
         ids, lens = torch.zeros(0, T, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
@@ -160,7 +174,9 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
 def make_preds_from_captions(data: Sequence[Dict], clip_model, model: ClipCaptionModel, tokenizer, tokenize=None,
                              out_path: Optional[str] = None, beam: bool = True, entry_length: int = 67,
                              dont_normalize_prefix: bool = False, modality_offset: Optional[torch.Tensor] = None,
-                             rank: int = 0, world: int = 1, text_batch: int = 2048) -> List[Dict]:
+                             rank: int = 0, world: int = 1, text_batch: int = 2048, *,
+                             repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                             min_length: Optional[int] = None, logit_bias=None) -> List[Dict]:
     """The TEXT-input branch of the reference loop (:215-218: ``args.text_autoencoder`` or ``dataset_mode == 5`` -- "the
     image is actually text input"): ``caption_tokens = clip.tokenize(d['caption'])``; ``prefix =
     clip_model.encode_text(caption_tokens).float()``; then the common tail (:221-234) -- normalise, modality offset,
@@ -178,7 +194,8 @@ def make_preds_from_captions(data: Sequence[Dict], clip_model, model: ClipCaptio
         feats.append(clip_model.encode_text(toks).float())
     stop = tokenizer.encode('.')[0]
     if feats:
-        ids, lens, _ = caption_ids(model, torch.cat(feats), stop, beam, 5, entry_length, dont_normalize_prefix, modality_offset)
+        ids, lens, _ = caption_ids(model, torch.cat(feats), stop, beam, 5, entry_length, dont_normalize_prefix, modality_offset,
+                                   **_given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias))
     else:                              # an empty shard (more ranks than captions) still takes part in the gather
         dev = next(model.parameters()).device
         ids = torch.zeros(0, entry_length, dtype=torch.int32, device=dev)

@@ -375,6 +375,35 @@ int capdec_decode_sample(capdec_ctx *ctx, const float *d_prefix, int n, int P, i
                          int32_t *d_lens,       /* [n] */
                          float *d_logp);        /* [n, entry_length] or NULL */
 
+/* ---- logits processors --------------------------------------------------------------- */
+/* Context state, like capdec_set_compact: what the following capdec_decode_greedy / _beam / _sample calls apply to the
+ * raw logits l[0..vocab) of every row at every step i, before the division by the temperature.  A row's history
+ * g = (g_0 .. g_{i-1}) is what its own hypothesis has generated so far -- the caption's ids (greedy, sampling), that beam's
+ * tokens after the previous step's re-ordering (beam); prefix rows and prompt tokens folded into the prefix are not
+ * history.  In this order:
+ *   1. repetition_penalty theta > 0 (1 = off): for every DISTINCT j in g, l[j] <- l[j] / theta if l[j] > 0 else
+ *      l[j] * theta (a token that occurs twice is penalised once);
+ *   2. the bias of capdec_set_logit_bias: l <- l + b (entries finite or -inf; -inf bans the token);
+ *   3. no_repeat_ngram_size m (0 = off): if i >= m - 1, for every s with g[s .. s+m-2] == g[i-m+1 .. i-1]:
+ *      l[g[s+m-1]] <- -inf (m = 1 bans every token of g);
+ *   4. min_length (0 = off): if i < min_length, l[stop_id] <- -inf, and l[alt_stop_id] where the call has one;
+ *   5. top_k (0 = off; capdec_decode_sample only): j stays iff fewer than top_k entries are strictly greater than l[j]
+ *      (ties at the boundary stay), everything else becomes -inf.
+ * Then s = l / temperature and the call's own rule runs unchanged: arg-max; log-softmax, the stopped-beam rule and the
+ * length-averaged top-k; nucleus + draw.  Beam scores and the sampling d_logp are those of the processed distribution;
+ * d_logp's logsumexp runs over the logits after steps 1-4, before top_k and top_p (the convention d_logp has for top_p).
+ * With a processor or a bias set, a step materialises the fp32 logits of at most CAPDEC_SAMPLE_ROWS rows at a time, as
+ * capdec_decode_sample does; with none set the decode calls run exactly the launches they run without this state.
+ * capdec_decode_greedy_forced, capdec_score, capdec_gpt2_logits and the train step IGNORE the processors and the bias.
+ * Refused (capdec_last_error; the state is left as it was): theta <= 0, NaN or inf; a negative size.  NULL: none.
+ * (Added without a new ABI number, like capdec_decode_sample.) */
+typedef struct { float repetition_penalty; int no_repeat_ngram_size; int min_length; int top_k; } capdec_logits_processors;
+int capdec_set_logits_processors(capdec_ctx *ctx, const capdec_logits_processors *p);
+/* h_bias: HOST array [vocab], validated and uploaded once (NULL: no bias).  Refused: GPT-2 not loaded, vocab not the
+ * loaded vocabulary, a NaN or +inf entry, fewer than 1026 finite entries -- a step bans at most entry_length + 1 <= 1025
+ * tokens, so a row can always emit one. */
+int capdec_set_logit_bias(capdec_ctx *ctx, const float *h_bias, int vocab);
+
 /* ---- scoring ------------------------------------------------------------------------- */
 /* Teacher-forced log-probabilities of GIVEN captions; the [rows, vocab] logits never exist in HBM.
  * Caption r has prefix rows d_prefix[r] [P, d], token ids d_tokens[r, 0..L) and a length len[r] in 0..L.  The model input is
