@@ -154,6 +154,7 @@ SIGNATURES = {
     "capdec_set_logit_bias": (C.c_int, [_VP, c_float_p, C.c_int]),
     "capdec_score": (C.c_int, [_VP, _VP, _VP, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP, _VP]),
     "capdec_score_chunks": (C.c_int, [_VP, C.POINTER(C.c_int)]),
+    "capdec_nearest_tokens": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
     "capdec_decode_beam": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP,
                                      _VP, _VP]),
     "capdec_gemm_f32": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,

@@ -233,6 +233,11 @@ int launch_layernorm_packed(hipStream_t st, const float *x, int ldx, const float
 // elementwise.hip
 int launch_layernorm(hipStream_t st, const float *x, int ldx, const float *w, const float *b, float eps, float *y,
                      int ldy, int rows, int d);
+// x / max(||x||_2, 1e-12) per row of x [rows, d] (nnf.normalize in fp32), as a packed GEMM operand of format fmt (`packed`)
+// or as fp32 rows (`y`) -- exactly one is non-null.  A row holding a NaN or an inf is written as zeros and reported:
+// row_bad[row] = 1 (else 0; may be null), *any_bad |= 1 (may be null)
+int launch_l2norm_rows(hipStream_t st, const float *x, void *packed, float *y, int rows, int d, int fmt, int *row_bad,
+                       int *any_bad);
 int launch_embed_tokens(hipStream_t st, const int *tok, const float *wte, const float *wpe_row, float *h, int rows,
                         int d, const int *cmap = nullptr, int beam = 1);
 int launch_embed_prefix(hipStream_t st, const float *prefix, const float *wpe, float *h, int n, int P, int pos0,

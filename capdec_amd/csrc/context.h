@@ -7,6 +7,7 @@
 //   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam / sampling decode loop
 //                     (the sampling kernel itself: sample.hip; the logits processors' kernels: process.hip)
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
+//   nearest.hip       capdec_nearest_tokens: nearest table rows by cosine similarity (the normalised-wte cache, row blocks)
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
 //                     forward share (tlayer_self_front / tlayer_tail)
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
@@ -119,7 +120,7 @@ struct ResNet {
 };
 
 enum Family { F_GEMM = 0, F_LMHEAD, F_ATTN_DEC, F_ATTN_PRE, F_LN, F_EMBED, F_SELECT, F_MAP_ATTN, F_OTHER, F_GEMM_X3,
-              F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_COUNT };
+              F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_NEAREST, F_COUNT };
 extern const char *const kFamilyNames[F_COUNT];
 constexpr int PROF_SLOTS = 24;   // capdec_profile_get fills at most this many families (engine.py sizes its arrays by it)
 static_assert(F_COUNT <= PROF_SLOTS, "profile arrays too small");
@@ -185,6 +186,10 @@ struct capdec_ctx {
     DBuf s_plan, s_rows, s_logit, s_bad;   // capdec_score (score.hip): the call's plan [lens | row offsets | h rows | targets], a
                                            // chunk's scored rows of h [R, d], their label logits [R], first tainted position [nc]
     int stat_score_chunks = 0;             // chunks of the last capdec_score call (capdec_score_chunks)
+    DBuf wte_n;                            // capdec_nearest_tokens (nearest.hip): the loaded wte with every row L2-normalised, fp32
+    bool wte_n_valid = false;              // [vocab, d] -- built on first use, its operand planes cached by planes_of like a weight's;
+                                           // dropped with the wte it was made from (drop_wte_norm)
+    DBuf n_tab, n_bad;                     // ... a caller's table normalised for one call; [table flag | one flag per row of a block]
     capdec::LogitsProc proc;               // capdec_set_logits_processors (defaults: every processor off)
     int proc_bias_n = 0;                   // capdec_set_logit_bias: entries of `pbias` (0 = no bias)
     DBuf pbias, pcorr;     // the logit bias [vocab]; a row block's logp shift under top_k (decode.hip: lm_head_process)
@@ -288,6 +293,16 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
 // ... its exact second pass: k = 5 lists for the *m_dev rows of the packed operand Apk (in the format of the mode)
 int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_dev, int N, int K, float inv_temp,
                   const TopkOut &o);
+// The fused top-k GEMM WITHOUT a LayerNorm in front, fp32-accurate in every mode as gemm() is: the k best columns of every
+// row of A . Bt^T (Bt fp32 [N, K]) -> top_val / top_idx [M, k] (descending, equal values in ascending column order) and
+// lse [M]; o: the per-tile lists in between.  A is what topk_packed_a(c, K) says: the packed PK_F16X2 operand (modes f16x2,
+// bf16, f16 with K % 64 == 0 -> the two-fp16-plane kernels, the 256 x 128 tile from 2048 rows) or fp32 rows of stride K
+// (mode bf16x3 with K % 64 == 0 -> its own top-k kernel; otherwise the native fp32 one).  b_small: every |Bt| < 16 is known
+// (GemmEpilogue::wide_ok without measuring it).  cache: Bt is a resident matrix whose operand planes may be kept.  Never
+// the three-candidate shortcut of ln_gemm_topk; the 128-row tile alone in the batch-invariant mode.
+bool topk_packed_a(const capdec_ctx *c, int K);
+int gemm_topk(capdec_ctx *c, const void *A, const float *Bt, bool cache, bool b_small, int M, int N, int K, int k,
+              const TopkOut &o, float *lse, float *top_val, int *top_idx);
 
 // ---- mapper.hip: the TransformerLayer forward, x -> out on M rows of width w (hidden hid):
 //     a1 = norm1(x); qkv = a1 . [q | k | v]^T                                       tlayer_self_front (fused layers)
@@ -323,5 +338,8 @@ void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd);
 int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv);
 int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp);
 int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads = 0, int hd = 0, int layers = 0);
+
+// ---- nearest.hip
+void drop_wte_norm(capdec_ctx *c);      // the normalised copy of wte and its planes (wte was reloaded or updated)
 
 }  // namespace capdec

@@ -146,6 +146,79 @@ int launch_layernorm_packed(hipStream_t st, const float *x, int ldx, const float
     return 0;
 }
 
+// ---------------------------------------------------------------------------- L2 row normalisation (capdec_nearest_tokens)
+// y = x / max(||x||_2, 1e-12) per row (torch's nnf.normalize, fp32: sum of squares, sqrt, a division per element), written
+// as the packed A / B operand of the fused top-k GEMM (`packed`, format fmt: the fp32 unit row never goes to HBM) or as fp32
+// rows of stride d (`y`: the bf16x3 and f32 modes, d % 64 != 0, the cached table).  Exactly one of the two is non-null.  A
+// row holding a NaN or an inf is written as ZEROS -- the GEMM behind it then sees finite operands only -- and reported:
+// row_bad[row] = 1 (0 otherwise; may be null) and *any_bad |= 1 (may be null).  Same walk as layernorm_packed_kernel: one
+// wavefront per row, LN_RPW rows per wavefront with the next row's loads in flight, four adjacent rows per block at a time.
+template <int LN_RPW>
+__global__ __launch_bounds__(256) void l2norm_rows_kernel(const float *__restrict__ x, char *__restrict__ packed,
+                                                          float *__restrict__ y, int rows, int d, int fmt,
+                                                          int *__restrict__ row_bad, int *__restrict__ any_bad) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nv = d >> 2, nk = d / X3_BK;
+    const int row0 = blockIdx.x * 4 * LN_RPW + wave;
+    if (row0 >= rows) return;
+    float4 v[LN_MAXV], nx[LN_MAXV];
+#define L2_LOAD(dst, r)                                                                              \
+    _Pragma("unroll") for (int i = 0; i < LN_MAXV; ++i) {                                            \
+        const int idx = lane + 64 * i;                                                               \
+        dst[i] = (idx < nv && (r) < rows) ? reinterpret_cast<const float4 *>(x + (size_t)(r) * d)[idx] \
+                                          : make_float4(0.f, 0.f, 0.f, 0.f);                         \
+    }
+    L2_LOAD(nx, row0)
+#pragma unroll
+    for (int rr = 0; rr < LN_RPW; ++rr) {
+        const int row = row0 + 4 * rr;
+        if (row >= rows) break;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) v[i] = nx[i];
+        if (rr + 1 < LN_RPW) { L2_LOAD(nx, row + 4) }
+        float q = 0.f, big = 0.f;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {                      // (lanes past nv hold zeros)
+            q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+            const float a = __builtin_fabsf(v[i].x), b = __builtin_fabsf(v[i].y), c = __builtin_fabsf(v[i].z),
+                        e = __builtin_fabsf(v[i].w);
+            big = (a <= 3.402823466e38f && b <= 3.402823466e38f && c <= 3.402823466e38f && e <= 3.402823466e38f) ? big : 1.f;
+        }
+        const bool bad = wave_max(big) != 0.f;                   // (uniform: a NaN or an inf somewhere in the row)
+        const float den = fmaxf(sqrtf(wave_sum(q)), 1e-12f);
+        if (lane == 0) {
+            if (row_bad) row_bad[row] = bad ? 1 : 0;
+            if (bad && any_bad) atomicOr(any_bad, 1);
+        }
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            const int idx = lane + 64 * i;
+            if (idx < nv) {
+                const float4 o = bad ? make_float4(0.f, 0.f, 0.f, 0.f)
+                                     : make_float4(v[i].x / den, v[i].y / den, v[i].z / den, v[i].w / den);
+                if (packed) x3_store_quad(packed, nk, row, idx >> 2, idx & 3, o, fmt);
+                else reinterpret_cast<float4 *>(y + (size_t)row * d)[idx] = o;
+            }
+        }
+    }
+#undef L2_LOAD
+}
+
+int launch_l2norm_rows(hipStream_t st, const float *x, void *packed, float *y, int rows, int d, int fmt, int *row_bad,
+                       int *any_bad) {
+    CAPDEC_CHECK(d % 4 == 0 && d <= 256 * LN_MAXV && (!packed || d % 16 == 0), "l2norm_rows: unsupported width");
+    CAPDEC_CHECK((packed != nullptr) != (y != nullptr), "l2norm_rows: exactly one output form");
+    if (rows <= 0) return 0;
+    if (rows >= 16384)      // (the block sizes of launch_layernorm_packed)
+        hipLaunchKernelGGL(l2norm_rows_kernel<4>, dim3((rows + 15) / 16), dim3(256), 0, st, x, (char *)packed, y, rows, d, fmt,
+                           row_bad, any_bad);
+    else
+        hipLaunchKernelGGL(l2norm_rows_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, st, x, (char *)packed, y, rows, d, fmt,
+                           row_bad, any_bad);
+    CAPDEC_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- embeddings
 // h[row] = wte[tok[row]] + wpe_row   (all rows of a decode step share one position)
 // (cmap: compact activation row -> the original caption whose token it carries, see launch_attn_decode)

@@ -255,6 +255,37 @@ int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_d
     return launch_gemm_h2w_topk_dev(c->stream, Apk, pl, m_dev, N, K, inv_temp, o);
 }
 
+// gemm()'s rule for fp32 activations: the packed two-fp16-plane path in the f16x2 and the one-plane modes when K % 64 == 0
+bool topk_packed_a(const capdec_ctx *c, int K) { return (c->gemm_mode == GEMM_F16X2 || mode_single(c)) && K % 64 == 0; }
+
+int gemm_topk(capdec_ctx *c, const void *A, const float *Bt, bool cache, bool b_small, int M, int N, int K, int k,
+              const TopkOut &o, float *lse, float *top_val, int *top_idx) {
+    const double flops = 2.0 * M * (double)N * K;
+    if (topk_packed_a(c, K)) {
+        const void *pl = nullptr;
+        bool wide_ok = false;
+        CAPDEC_TRY(planes_of(c, Bt, N, K, cache, &pl, PK_F16X2, &wide_ok));
+        wide_ok = wide_ok || b_small;
+        ProfScope ps(c, F_NEAREST, flops);
+        const int h2w = c->tune.h2w;      // (the tile rule of ln_gemm_topk)
+        if (wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2))
+            CAPDEC_TRY(launch_gemm_h2w_topk(c->stream, A, pl, M, N, K, k, 1.0f, o));
+        else
+            CAPDEC_TRY(launch_gemm_f16x2p_topk(c->stream, A, pl, M, N, K, k, 1.0f, o));
+    } else if (c->gemm_mode != GEMM_F32 && K % 64 == 0) {
+        const void *pl = nullptr;
+        CAPDEC_TRY(planes_of(c, Bt, N, K, cache, &pl, PK_BF16X3));
+        ProfScope ps(c, F_NEAREST, flops);
+        CAPDEC_TRY(launch_gemm_bf16x3_topk(c->stream, (const float *)A, K, pl, M, N, K, k, 1.0f, o));
+    } else {
+        ProfScope ps(c, F_NEAREST, flops);
+        CAPDEC_TRY(launch_gemm_f32_topk(c->stream, (const float *)A, K, Bt, K, M, N, K, k, 1.0f, o));
+    }
+    ProfScope ps(c, F_SELECT);
+    return launch_topk_merge(c->stream, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx, M, gemm_tiles_n(N), k, lse, top_val,
+                             top_idx);
+}
+
 }  // namespace capdec
 
 using namespace capdec;

@@ -179,7 +179,10 @@ int train_apply_update(capdec_ctx *c, TrainState &t, float lr, float b1, float b
                        t.G.as<float>(), t.Mo.as<float>(), t.Vo.as<float>(), sc, b1, b2, eps, lr * weight_decay);
     CAPDEC_HIP(hipGetLastError());
     t.step += 1;
-    for (const Slot &sl : t.slots) drop_planes_of(c, sl.p);      // inference must never see planes packed from old values
+    for (const Slot &sl : t.slots) {
+        drop_planes_of(c, sl.p);      // inference must never see planes packed from old values
+        if (sl.p == c->gpt.wte) drop_wte_norm(c);      // ... nor capdec_nearest_tokens the unit rows of the old wte
+    }
     if (t.train_gpt) CAPDEC_TRY(refresh_backward_weights(c, t));
     return 0;
 }

@@ -147,6 +147,7 @@ int capdec_load_gpt2(capdec_ctx *c, const capdec_gpt2_weights *w) {
     Gpt2 &g = c->gpt;
     free_all(g.owned);
     drop_planes(c);
+    drop_wte_norm(c);
     train_release(c);
     g = Gpt2();
     g.n_layer = w->n_layer; g.n_head = w->n_head; g.d = w->n_embd; g.vocab = w->vocab; g.n_pos = w->n_pos;

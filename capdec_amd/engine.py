@@ -594,6 +594,37 @@ class Engine:
         self._chk(self.lib.capdec_score_chunks(self._h, C.byref(n)), "score_chunks")
         return n.value
 
+    # ------------------------------------------------------------------ prefix interpretation
+    def nearest_tokens(self, x: torch.Tensor, k: int = 1, table: Optional[torch.Tensor] = None, return_sims: bool = False):
+        """the ``k`` rows of ``table`` [V, d] (None: the loaded GPT-2's wte, whose normalised copy the library caches)
+        nearest to every row of ``x`` [..., d] under cosine similarity (capdec_nearest_tokens; the contract: include/capdec.h)
+        -> ids int32 [..., k], descending similarity, equal similarities in ascending id order, and with ``return_sims`` the
+        similarities fp32 [..., k].  A row of ``x`` holding a NaN or an inf gets ids -1 and sims NaN."""
+        if x.dim() < 1:
+            raise CapdecError("nearest_tokens: x must be [..., d]")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise CapdecError(f"nearest_tokens: k must be an integer, got {k!r}")
+        lead, d = tuple(x.shape[:-1]), int(x.shape[-1])
+        t = None
+        if table is not None:
+            if table.dim() != 2 or int(table.shape[1]) != d:
+                raise CapdecError(f"nearest_tokens: table must be [V, {d}], got {tuple(table.shape)}")
+            t = self._dev(table)
+        xs = self._dev(x).reshape(-1, d)
+        rows = int(xs.shape[0])
+        k = int(k)
+        if not 1 <= k <= 8:
+            raise CapdecError(f"nearest_tokens: k must be in 1..8, got {k}")
+        ids = torch.empty(rows, k, device=self.device, dtype=torch.int32)
+        sims = torch.empty(rows, k, device=self.device, dtype=torch.float32) if return_sims else None
+        self._sync_stream()
+        self._chk(self.lib.capdec_nearest_tokens(self._h, xs.data_ptr() if rows else None, rows, d,
+                                                 t.data_ptr() if t is not None else None, int(t.shape[0]) if t is not None else 0,
+                                                 int(k), ids.data_ptr() if rows else None,
+                                                 sims.data_ptr() if sims is not None and rows else None), "capdec_nearest_tokens")
+        ids = ids.view(*lead, int(k))
+        return (ids, sims.view(*lead, int(k))) if return_sims else ids
+
     # ------------------------------------------------------------------ caption-shard communicator (RCCL through the C ABI)
     def comm_unique_id(self) -> bytes:
         """rank 0: the 128-byte communicator id every rank passes to :meth:`comm_init`"""

@@ -195,6 +195,11 @@ class ClipCaptionModel(_HipModule):
     def get_dummy_token(self, batch_size: int, device) -> torch.Tensor:
         return torch.zeros(batch_size, self.prefix_length, dtype=torch.int64, device=device)
 
+    def get_embedding(self, tokens: torch.Tensor) -> torch.Tensor:
+        """the embedding rows of ``tokens`` -- what reference gpt2_prefix_eval.py:204 calls (and the reference's model does
+        not define): ``self.gpt.transformer.wte(tokens)``"""
+        return self.gpt.transformer.wte(tokens)
+
     # ---- train steps update the mapper ON THE DEVICE (capdec_amd.train.train_step): the host copy follows lazily
     _device_ahead = False
 

@@ -9,7 +9,13 @@ into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``
 Logits processors (``engine.LogitsProcessors``; the contract: include/capdec.h).  The batched functions take them as
 keyword-only arguments (None: not given); ``generate2`` / ``generate_beam`` keep the reference's signatures and read
 ``model.logits_processors`` instead, which is also what a batched function starts from before its own keywords go on top.
-Whatever is switched on is set on the engine for the one decode call and cleared after it."""
+Whatever is switched on is set on the engine for the one decode call and cleared after it.
+
+Prefix interpretation and editing (reference :201-251): ``get_prefix_tokens`` reads each prefix vector as its nearest
+vocabulary token under cosine similarity (``capdec_nearest_tokens``: the [rows, vocab] similarity matrix never exists);
+``add_embedding_from_text`` / ``generate_text`` / ``re_caption`` / ``remove_token`` / ``try_all_places`` are the probes built
+on it, with the reference's names and signatures.  ``prefix_token_ids`` / ``get_prefix_tokens_batch`` are the batched forms;
+``try_all_places`` decodes its P edited prefixes as one batch."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -18,7 +24,7 @@ import numpy as np
 import torch
 
 from ._capi import CapdecError
-from .engine import LogitsProcessors
+from .engine import LogitsProcessors, get_engine
 from .gpt2_prefix import ClipCaptionModel
 from .train import _next_seed
 
@@ -226,3 +232,98 @@ def generate_samples(model, tokenizer, tokens=None, prompt=None, embed=None, ent
                            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias, top_k=top_k)
     ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
     return [tokenizer.decode((prompt_ids or []) + [int(t) for t in ids[e, :lens[e]]]) for e in range(entry_count)]
+
+
+# --------------------------------------------------------------------------- prefix interpretation and editing
+def _nearest(embeddings, x: torch.Tensor, k: int = 1, model=None):
+    """(ids, sims) of the rows of ``x`` [..., d] against ``embeddings``: a ClipCaptionModel (its wte, normalised once and
+    cached by the library) or a [V, d] tensor as the reference passes it (given to the library as ``table``; normalising an
+    already normalised table again is harmless)"""
+    if isinstance(embeddings, torch.Tensor):
+        if model is not None:
+            eng = model.engine
+        else:
+            dev = x.device if x.device.type == "cuda" else embeddings.device
+            eng = get_engine(dev.index or 0)
+        return eng.nearest_tokens(x, k, table=embeddings, return_sims=True)
+    return embeddings.engine.nearest_tokens(x, k, return_sims=True)
+
+
+def prefix_token_ids(model: ClipCaptionModel, embed: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """embed [N, P, d] -> (ids int32 [N, P, k], sims fp32 [N, P, k]): the ``k`` vocabulary tokens nearest to every prefix
+    vector, best first -- device tensors"""
+    return _nearest(model, embed, k)
+
+
+def get_prefix_tokens_batch(model: ClipCaptionModel, tokenizer, embed: torch.Tensor) -> List[str]:
+    """embed [N, P, d] -> one "prefix sentence" per caption (``get_prefix_tokens`` of each row, one device call)"""
+    ids, _ = prefix_token_ids(model, embed, 1)
+    ids = ids[..., 0].to(torch.int64).cpu()
+    return [tokenizer.decode(ids[r]) for r in range(ids.shape[0])]
+
+
+def get_prefix_tokens(prefix_embed, embeddings, tokenizer) -> str:
+    """reference gpt2_prefix_eval.py:247-251.  ``embeddings``: the ClipCaptionModel, or the (normalised) embedding table
+    [V, d] the reference passes"""
+    ids, _ = _nearest(embeddings, prefix_embed[0], 1)
+    return tokenizer.decode(ids[:, 0].to(torch.int64).cpu())
+
+
+def add_embedding_from_text(add_in: str, prefix_embed: torch.Tensor, tokenizer, model: ClipCaptionModel, where: int):
+    """the prefix [1, P, d] with the embedding rows of ``add_in``'s tokens spliced in before position ``where`` (0: in
+    front; P or -1: appended) -> [1, P + m, d].  Name, signature and ``where`` rules of reference :201-212."""
+    ids = torch.as_tensor(tokenizer.encode(add_in), device=prefix_embed.device)
+    rows = model.get_embedding(ids).to(prefix_embed.device)[None]
+    at = prefix_embed.shape[1] if where == -1 else where
+    return torch.cat((prefix_embed[:, :at], rows, prefix_embed[:, at:]), 1)
+
+
+def _decode_texts(embed: torch.Tensor, tokenizer, model: ClipCaptionModel, use_beam: bool) -> List[str]:
+    """embed [N, P, d] -> one text per row from ONE decode call, as ``generate_beam(..., beam_size=5)[0]`` /
+    ``generate2`` give it with their defaults (entry_length 67, stop token '.', the model's logits processors)"""
+    model.eval()
+    stop = tokenizer.encode('.')[0]
+    if use_beam:
+        ids, lens, _, _ = decode_beam_ids(model, embed, stop, 5)
+        ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+        return [tokenizer.decode(ids[r, 0, :int(lens[r, 0])]) for r in range(ids.shape[0])]
+    ids, lens = decode_greedy_ids(model, embed, stop)
+    ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+    first = [r for r in range(ids.shape[0]) if lens[r] == 1]
+    if first:      # generate2 raises a TypeError for such a caption (the reference's squeeze() to a 0-d array, :191)
+        raise TypeError(f"iteration over a 0-d array: the first token stops the greedy decode of row(s) {first}")
+    return [tokenizer.decode([int(t) for t in ids[r, :lens[r]]]) for r in range(ids.shape[0])]
+
+
+def generate_text(prefix_embed: torch.Tensor, tokenizer, model: ClipCaptionModel, use_beam: bool) -> str:
+    """the caption of one prefix [1, P, d]: the best of 5 beams, or the greedy text (reference :215-220)"""
+    if prefix_embed.shape[0] != 1:
+        raise CapdecError("generate_text takes one caption ([1, P, d])")
+    return _decode_texts(prefix_embed, tokenizer, model, use_beam)[0]
+
+
+def re_caption(add_in: str, prefix_embed: torch.Tensor, tokenizer, model: ClipCaptionModel, where: int,
+               use_beam: bool = True) -> str:
+    """the caption after ``add_in`` was spliced into the prefix at ``where`` (reference :223-226)"""
+    return generate_text(add_embedding_from_text(add_in, prefix_embed, tokenizer, model, where), tokenizer, model, use_beam)
+
+
+def remove_token(prefix_embed: torch.Tensor, tokenizer, model: ClipCaptionModel, embeddings, where: List[int],
+                 use_beam: bool = True):
+    """reference :229-237 -> (text generated from the prefix without the positions ``where``, its prefix sentence)"""
+    keep = [i for i in range(prefix_embed.shape[1]) if i not in where]
+    shorter = prefix_embed[:, keep]
+    ids, _ = _nearest(embeddings, shorter[0], 1, model)
+    return generate_text(shorter, tokenizer, model, use_beam), tokenizer.decode(ids[:, 0].to(torch.int64).cpu())
+
+
+def try_all_places(add_in: str, prefix_embed: torch.Tensor, tokenizer, model: ClipCaptionModel,
+                   use_beam: bool = True) -> List[str]:
+    """``re_caption`` at every position 0..P-1 (reference :240-244): the P edited prefixes form one [P, P + m, d] batch
+    that ONE decode call serves.  Greedy: a TypeError naming the places whose first token stops, where ``re_caption``
+    would raise for that place alone."""
+    P = int(prefix_embed.shape[1])
+    if P == 0:
+        return []
+    batch = torch.cat([add_embedding_from_text(add_in, prefix_embed, tokenizer, model, i) for i in range(P)], 0)
+    return _decode_texts(batch, tokenizer, model, use_beam)

@@ -433,6 +433,35 @@ int capdec_score(capdec_ctx *ctx, const float *d_prefix /* [n, P, d] */, const i
                  int32_t *d_count /* [n] or NULL */, int32_t *d_top1 /* [n, L] or NULL */);
 /* *chunks = how many chunks the last capdec_score call split its captions into; 0 for an empty call. */
 int capdec_score_chunks(capdec_ctx *ctx, int *chunks);
+
+/* ---- prefix interpretation ----------------------------------------------------------- */
+/* Nearest rows of a table under cosine similarity; the [rows, table_rows] similarity matrix never exists in HBM.
+ * xn = x / max(||x||_2, 1e-12), tn likewise (torch's nnf.normalize); sim[r, j] = <xn[r], tn[j]>.
+ * d_ids[r, 0..k) = the k table rows with the largest sim, descending; EQUAL sims in ascending id order; d_sims (may be NULL)
+ * their values.  d_table == NULL: the loaded GPT-2's wte [vocab, n_embd] (reference gpt2_prefix_eval.py:248-249, :233-234,
+ * with the normalisation of :259-260); table_rows is then ignored.
+ *   - Both operands are normalised BEFORE the product, so every GEMM operand lies in [-1, 1]: the norms of trained prefixes
+ *     never meet the +-65504 clamp of the fp16-plane operand formats.
+ *   - fp32-accurate in every GEMM mode, as the mapper's GEMMs are: modes f16x2, bf16 and f16 run the two-fp16-plane
+ *     kernels (d % 64 == 0; other d the native fp32 kernel), mode bf16x3 its own top-k kernel, mode f32 the native one.
+ *   - Limits, each refused with capdec_last_error and the context left usable: d a multiple of 32, at most 1024;
+ *     1 <= k <= 8 and k <= table_rows; rows >= 0 (rows == 0 succeeds and touches nothing); with d_table == NULL, GPT-2
+ *     must be loaded and d == n_embd.  d_x and d_table are 16-byte aligned.
+ *   - An all-zero query row has every sim 0 and ids 0..k-1.  A query row holding a NaN or an inf gets d_sims NaN and d_ids
+ *     -1 for that row only; no id outside [0, table_rows) is ever written otherwise.  A zero table row has sim 0.  A table
+ *     row holding a NaN or an inf makes the call FAIL and write nothing (the normalising pass reads every row anyway).
+ *     Defined for norms whose square is a normal fp32 number; beyond that the behaviour is that of fp32 nnf.normalize.
+ *   - Rows are processed in blocks of a fixed 16 384 rows (the per-tile candidate lists of 50 257 columns at k = 8 are
+ *     28 KB per row).  A row's result does not depend on the other rows beyond what capdec_set_batch_invariant documents
+ *     (from 2048 rows a block takes a 256-row tile); with that mode on a row's ids and sims are bit-identical whatever the
+ *     batch and the block (the 128-row tile is pinned, as for the lm_head).
+ *   - The normalised wte is cached on first use (an fp32 copy plus its operand planes) and dropped by capdec_load_gpt2,
+ *     capdec_destroy and every train step that updates wte.  A caller's d_table is normalised on every call, never cached.
+ *   - The call enqueues on the context's stream and synchronises before it returns, like the decode calls.
+ * (Added without a new ABI number, like capdec_score.) */
+int capdec_nearest_tokens(capdec_ctx *ctx, const float *d_x /* [rows, d] */, int rows, int d,
+                          const float *d_table /* [table_rows, d] or NULL = wte */, int table_rows,
+                          int k, int32_t *d_ids /* [rows, k] */, float *d_sims /* [rows, k] or NULL */);
 /* Image preprocessing in front of capdec_clip_encode_image: the `preprocess` transform clip.load returns
  * (reference predictions_runner.py:212, embeddings_generator.py:72) = Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
  * ToTensor -> Normalize(mean, std); stretch != 0 = clip_transform_full (predictions_runner.py:116-122): Resize((n_px,

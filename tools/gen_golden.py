@@ -416,6 +416,94 @@ def gen_decode_p40(refs, dims, tag):
     print(f"decode_p40_{tag}.npz written")
 
 
+class IdTok(FakeTok):
+    """the prefix-editing functions also encode the text they splice in and decode argmax ids: ``encode`` reads a string
+    of ids ('.' stays the stop token), ``decode`` returns the id list"""
+
+    def encode(self, s):
+        return [self.stop] if s == "." else [int(w) for w in s.split()]
+
+    def decode(self, ids):
+        return [int(i) for i in ids]
+
+
+def gen_prefix_tokens(refs, dims, tag):
+    """Prefix interpretation and editing (reference gpt2_prefix_eval.py:201-251) on the tiny geometry: the reference's own
+    get_prefix_tokens, remove_token, re_caption and try_all_places, MLP mapper 512 -> P 10, 8 captions.  ``get_embedding``
+    (which :204 calls and the reference's model lacks) is attached to the instance here.  Written: the inputs, the
+    prefix-token ids, and the greedy ids / the beam state of every edited prefix."""
+    import torch.nn.functional as nnf
+    gpt2_prefix, E = refs[0], refs[1]
+    P, n, T, add_in, removed = 10, 8, 67, "17 905", [2, 7]
+    model, sd = build_ref_model(gpt2_prefix, dims, "mlp", 512, P)
+    model.get_embedding = lambda tokens: model.gpt.transformer.wte(tokens)
+    out = {"sd_crc": np.uint32(synth.state_dict_checksum(sd)), "add_in": np.array(IdTok().encode(add_in), np.int64),
+           "removed": np.array(removed, np.int64)}
+    x = synth.synthetic_clip_embeddings(n, 512, seed=0)
+    recap_rows, recap_where, places_rows = (0, 1, 2, 3), (0, 3, -1, P), (0, 5)
+    out["x"], out["recap_rows"], out["recap_where"] = x.numpy(), np.array(recap_rows), np.array(recap_where)
+    out["places_rows"] = np.array(places_rows)
+    beams = []
+
+    def prof(frame, event, arg):
+        if event == "return" and frame.f_code.co_name == "generate_beam":
+            loc = frame.f_locals
+            beams.append((pad_tokens(loc["tokens"].cpu().numpy().astype(np.int64), T),
+                          loc["seq_lengths"].cpu().numpy().astype(np.float32), loc["scores"].cpu().numpy().astype(np.float32),
+                          loc["order"].cpu().numpy().astype(np.int64)))
+
+    def greedy_row(ids):
+        row = np.zeros(T, np.int64)
+        row[:len(ids)] = ids
+        return row, len(ids)
+
+    def run(stop):
+        """every edited decode with this stop id; TypeError when a first token stops (the reference's own squeeze())"""
+        tok, res = IdTok(stop), {}
+        del beams[:]
+        sys.setprofile(prof)
+        try:
+            res["remove_sent"] = np.array([E.remove_token(pe[r:r + 1], tok, model, emb, removed, False)[1] for r in range(n)])
+            g = [greedy_row(E.remove_token(pe[r:r + 1], tok, model, emb, removed, False)[0]) for r in range(n)]
+            res["remove_greedy_ids"], res["remove_greedy_lens"] = np.stack([a for a, _ in g]), np.array([b for _, b in g])
+            texts = [E.remove_token(pe[r:r + 1], tok, model, emb, removed, True)[0] for r in range(n)]
+            g = [greedy_row(E.re_caption(add_in, pe[r:r + 1], tok, model, w, False)) for r in recap_rows for w in recap_where]
+            res["recap_greedy_ids"], res["recap_greedy_lens"] = np.stack([a for a, _ in g]), np.array([b for _, b in g])
+            texts += [E.re_caption(add_in, pe[r:r + 1], tok, model, w, True) for r in recap_rows for w in recap_where]
+            g = [greedy_row(t) for r in places_rows for t in E.try_all_places(add_in, pe[r:r + 1], tok, model, False)]
+            res["places_greedy_ids"], res["places_greedy_lens"] = np.stack([a for a, _ in g]), np.array([b for _, b in g])
+            for r in places_rows:
+                texts += E.try_all_places(add_in, pe[r:r + 1], tok, model, True)
+        finally:
+            sys.setprofile(None)
+        assert len(beams) == len(texts) == n + len(recap_rows) * len(recap_where) + len(places_rows) * P
+        for (toks, seql, _, order), text in zip(beams, texts):      # the text returned is the best beam's tokens
+            assert list(toks[order[0], :int(seql[order[0]])]) == text, (toks, text)
+        cuts = np.cumsum([0, n, len(recap_rows) * len(recap_where), len(places_rows) * P])
+        for name, a, b in zip(("remove", "recap", "places"), cuts[:-1], cuts[1:]):
+            for j, field in enumerate(("tokens", "seqlen", "scores", "order")):
+                res[f"{name}_beam_{field}"] = np.stack([bm[j] for bm in beams[a:b]])
+        return res
+
+    with torch.no_grad():
+        pe = model.clip_project(x).reshape(n, P, -1)
+        emb = nnf.normalize(model.gpt.get_input_embeddings().weight.data, 2, 1)      # reference :259-260
+        out["prefix_embed"] = pe.numpy()
+        out["prefix_ids"] = np.array([E.get_prefix_tokens(pe[r:r + 1], emb, IdTok()) for r in range(n)], np.int64)
+        free = run(dims.vocab + 5)                               # a stop id that never fires: full-length sequences
+        vals, counts = np.unique(free["remove_greedy_ids"][:, 2:], return_counts=True)
+        for stop in vals[np.argsort(-counts, kind="stable")]:    # the commonest id that stops no decode at its first token
+            try:
+                out.update(run(int(stop)))
+            except TypeError:
+                continue
+            out["stop_id"] = np.int64(stop)
+            break
+    assert "stop_id" in out
+    np.savez_compressed(os.path.join(OUT, f"prefix_tokens_{tag}.npz"), **out)
+    print(f"prefix_tokens_{tag}.npz written; stop {out['stop_id']}, greedy lens {out['places_greedy_lens'].tolist()}")
+
+
 class PromptTok(FakeTok):
     """tokenizer stand-in for the prompt / tokens entry of generate2 / generate_beam: a prompt is a string of ids."""
 
@@ -913,6 +1001,7 @@ def main():
         "train_full_tiny": lambda: gen_train_full(refs, synth.GPT2_TINY, "tiny"),
         "train_full_dropout_tiny": lambda: gen_train_full_dropout(refs, synth.GPT2_TINY, "tiny"),
         "train_step_tm_tiny": lambda: gen_train_step(refs, synth.GPT2_TINY, "tm_tiny", "transformer_encoder"),
+        "prefix_tokens_tiny": lambda: gen_prefix_tokens(refs, synth.GPT2_TINY, "tiny"),
         "prompt_tiny": lambda: gen_prompt(refs, synth.GPT2_TINY, "tiny"),
         "prompt_small": lambda: gen_prompt(refs, synth.GPT2_SMALL, "small"),
         "clip_tiny": lambda: gen_clip(synth.CLIP_TINY, "tiny", 6, 3),
