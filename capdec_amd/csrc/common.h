@@ -357,16 +357,36 @@ int launch_beam_step(hipStream_t st, const BeamState &s, const float *lse, const
                      const int *cmap = nullptr);
 int launch_beam_finalize(hipStream_t st, const BeamState &s, int ncap, int beam, int T, int *ids, int *lens,
                          float *scores, int *order);
-int launch_greedy_step(hipStream_t st, const int *top_idx, int rows, int step, int T, int stop_id, int alt_stop_id,
-                       int *ids, int *lens, uint8_t *done, int *next_tok, int *alive_count,
-                       const int *cmap = nullptr, int k = 1, const int *forced = nullptr, const float *top_val = nullptr,
-                       const float *lse = nullptr, float *stats = nullptr);
+// The state the greedy family of decodes (arg-max, teacher-forced, sampling) keeps per caption, and the constants of the
+// call that its step kernels need
+struct GreedyState {
+    int *ids = nullptr;         // [ncap, T]
+    int *lens = nullptr;        // [ncap]
+    uint8_t *done = nullptr;    // [ncap]
+    int *next_tok = nullptr;    // [ncap]
+    int *alive_count = nullptr; // [1] captions still running (device counter, polled by the host)
+    float *logp = nullptr;      // [ncap, T] optional: log-probability of every emitted token (sampling)
+    int T = 0, stop_id = -1, alt_stop_id = -1;
+    const int *cmap = nullptr;  // after compaction: activation row r -> caption cmap[r] (nullptr: identity)
+};
+// caption `row` (not done) emits `tok` at `step`
+__device__ __forceinline__ void greedy_emit(const GreedyState &s, int row, int step, int tok, float lp) {
+    s.next_tok[row] = tok;
+    s.ids[(size_t)row * s.T + step] = tok;
+    s.lens[row] = step + 1;
+    if (s.logp) s.logp[(size_t)row * s.T + step] = lp;
+    if (tok == s.stop_id || tok == s.alt_stop_id) s.done[row] = 1;
+    else atomicAdd(s.alive_count, 1);
+}
+// top_idx / top_val [rows, k], lse [rows]: k = 1 normally; forced [ncap, T] (teacher forcing) and stats [ncap, T, 3] may be nullptr
+int launch_greedy_step(hipStream_t st, const GreedyState &s, const int *top_idx, int rows, int step, int k = 1,
+                       const int *forced = nullptr, const float *top_val = nullptr, const float *lse = nullptr,
+                       float *stats = nullptr);
 // sample.hip: one nucleus-sampling decode step over materialised logits [rows, ld], the activation rows row0 .. row0 + rows
-// of the step -- writes what greedy_step_kernel writes (plus logp [captions, T], may be nullptr).  u [captions, T]
-// (nullptr: Philox keyed by (seed, cap_off + caption, step)).
-int launch_sample_top_p(hipStream_t st, const float *logits, int ld, int rows, int row0, int V, float inv_temp, float top_p,
-                        uint64_t seed, const float *u, int cap_off, int step, int T, int stop_id, int alt_stop_id, int *ids,
-                        int *lens, uint8_t *done, int *next_tok, int *alive_count, float *logp, const int *cmap);
+// of the step -- writes what greedy_step_kernel writes (plus s.logp).  u [captions, T] (nullptr: Philox keyed by (seed,
+// cap_off + caption, step)).
+int launch_sample_top_p(hipStream_t st, const GreedyState &s, const float *logits, int ld, int rows, int row0, int V,
+                        float inv_temp, float top_p, uint64_t seed, const float *u, int cap_off, int step);
 // process.hip: the logits processors (capdec_set_logits_processors) over materialised logits [rows, ld], in place; logits
 // row r is activation row row0 + r of the step and finds its history -- hist [captions, beam, T], the first `step` entries
 // -- through cmap and beam as the greedy / beam step kernels find their rows.  bias [V] or nullptr.

@@ -182,7 +182,7 @@ struct capdec_ctx {
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
     unsigned long long train_drop_seed = 0;  // ... key of the Philox keep-mask stream (counter = element, train step)
     DBuf slogits;          // sampling decode, logits processors: fp32 logits of one row block, [min(rows, tune.sample_rows), ld]
-                           // (decode.hip: lm_head_sample, lm_head_process)
+                           // (decode.hip: lm_head_rows)
     DBuf s_plan, s_rows, s_logit, s_bad;   // capdec_score (score.hip): the call's plan [lens | row offsets | h rows | targets], a
                                            // chunk's scored rows of h [R, d], their label logits [R], first tainted position [nc]
     int stat_score_chunks = 0;             // chunks of the last capdec_score call (capdec_score_chunks)
@@ -192,7 +192,7 @@ struct capdec_ctx {
     DBuf n_tab, n_bad;                     // ... a caller's table normalised for one call; [table flag | one flag per row of a block]
     capdec::LogitsProc proc;               // capdec_set_logits_processors (defaults: every processor off)
     int proc_bias_n = 0;                   // capdec_set_logit_bias: entries of `pbias` (0 = no bias)
-    DBuf pbias, pcorr;     // the logit bias [vocab]; a row block's logp shift under top_k (decode.hip: lm_head_process)
+    DBuf pbias, pcorr;     // the logit bias [vocab]; a row block's logp shift under top_k (decode.hip: lm_head_rows)
     DBuf lmflag, xpk2;     // fused lm_head with 3 candidates per tile: [count, total, rows...] of the rows whose top 5 need
                            // the exact second pass; their compacted packed A operand (decode.hip: lm_head_select)
     DBuf m_hid, m_lin, m_seq, m_x, m_qkv, m_att, m_ff;
@@ -284,6 +284,10 @@ int ln_gemm_packed(capdec_ctx *c, const float *h, int ldh, const float *lnw, con
                    float *C, int ldc, int M, int N, int K, const float *bias, int act, void *packed_out = nullptr,
                    bool ln_ready = false, const QkvScatter *qkv_scatter = nullptr);
 
+// The workspace of a fused top-k launch over `rows` rows, `ntiles` column tiles and k candidates per tile: the per-tile
+// lists (c->tmax / tsum / cval / cidx) -> *o, and c->lse [rows].  (c->topv / c->topi belong to the caller: not every one
+// of them merges into these.)
+int topk_workspace(capdec_ctx *c, int rows, int ntiles, int k, TopkOut *o);
 // The fused lm_head: LayerNorm of the M rows of h, then LN(h) . W^T (W [N, K]) fused with the per-(row, 128-column tile)
 // top-k of the logits * inv_temp into o.  k3_ok: a k = 5 selection may keep three candidates per tile where the kernel
 // allows it (the wide two-plane tile; the one-plane kernel from 2048 rows); *k3 reports whether it did -- the rows the

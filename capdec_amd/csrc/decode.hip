@@ -1,6 +1,9 @@
 // The KV-cached batched decode: the pre-LN block stack (GPT-2, and the CLIP towers that run on the same stack), the fused
 // lm_head + candidate selection, the greedy / beam / sampling drivers with finished-caption compaction -- host-side orchestration
 // only: every operation is a launcher of common.h enqueued on the context's stream.  (The mapping networks: mapper.hip.)
+// A call's constants travel in one DecodeCall; every step, the prefill's included, ends in select_and_advance, which picks
+// the lm_head route (lm_head_select: fused, logits never in HBM; lm_head_rows: materialised, for the logits processors and
+// the sampling decode) and then advances the greedy or the beam state.
 #include "context.h"
 
 namespace capdec {
@@ -112,14 +115,10 @@ int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv) {
 int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp) {
     const Gpt2 &g = c->gpt;
     const int d = g.d, nt = gemm_tiles_n(g.vocab);
-    CAPDEC_TRY(c->tmax.ensure((size_t)R * nt * 4));
-    CAPDEC_TRY(c->tsum.ensure((size_t)R * nt * 4));
-    CAPDEC_TRY(c->cval.ensure((size_t)R * nt * k * 4));
-    CAPDEC_TRY(c->cidx.ensure((size_t)R * nt * k * 4));
-    CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
+    TopkOut o;
+    CAPDEC_TRY(topk_workspace(c, R, nt, k, &o));
     CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
     CAPDEC_TRY(c->topi.ensure((size_t)R * k * 4));
-    const TopkOut o{c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()};
     // Beam search (k = 5) may keep THREE candidates per (row, 128-column tile) -- two selection rounds fewer in every tile's
     // epilogue.  The merge then knows exactly which rows that can have been too few for (some tile's third candidate is
     // still strictly better than the row's fifth: with 393 tiles a rare event) and those rows alone go through the k = 5
@@ -165,33 +164,28 @@ static int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float 
     return gemm(c, c->xl.as<float>(), d, g.wte, d, logits, ld, R, g.vocab, d, nullptr, CAPDEC_ACT_NONE);
 }
 
-// The sampling decode's arguments (capdec_decode_sample); u / logp point at the chunk's first caption, cap_off is its
-// index within the call -- the Philox counter is (cap_off + caption, step) and nothing else, so a caption's draws do not
-// depend on the chunking, on the compaction or on the rest of the batch.
-struct SampleArgs {
-    float top_p;
-    uint64_t seed;
-    const float *u;     // [n, T] or nullptr (Philox)
-    float *logp;        // [n, T] or nullptr
-    int cap_off;
+// The constants of one decode call; the extern "C" entry points fill it, decode_common offsets the pointers per chunk.
+struct DecodeCall {
+    int P = 0, beam = 1;
+    bool greedy = true;         // the greedy family (arg-max, teacher-forced, sampling): beam == 1
+    int stop_id = -1, alt_stop_id = -1, T = 0;
+    float temperature = 1.0f;
+    int *ids = nullptr, *lens = nullptr;        // [n, beam, T], [n, beam]
+    float *scores = nullptr;    // [n, beam] (beam)
+    int *order = nullptr;       // [n, beam] or nullptr (beam)
+    const int *forced = nullptr;    // [n, T] teacher forcing: fed instead of the arg-max (greedy)
+    float *stats = nullptr;     // [n, T, 3] or nullptr (teacher forcing)
+    // the sampling decode (capdec_decode_sample): the greedy loop with the arg-max replaced by a draw.  The Philox counter
+    // is (cap_off + caption, step) and nothing else, so a caption's draws do not depend on the chunking, on the compaction or
+    // on the rest of the batch.
+    bool sample = false;
+    float top_p = 0.f;
+    uint64_t seed = 0;
+    const float *u = nullptr;   // [n, T] or nullptr (Philox)
+    float *logp = nullptr;      // [n, T] or nullptr
+    int cap_off = 0;            // index of the chunk's first caption within the call: the Philox counter's caption offset, and
+                                // the offset of the chunk's slice of the per-call K/V-slot statistic (BeamState::kv_stat)
 };
-
-// One sampling step over `R` activation rows: lm_head_logits + the nucleus-sampling kernel, tune.sample_rows rows at a time
-// (the fp32 logits of 5000 rows of GPT-2's vocabulary are 1 GB).  Writes what lm_head_select + launch_greedy_step write.
-static int lm_head_sample(capdec_ctx *c, const float *h0, int ldh, int R, float inv_temp, const SampleArgs &a, int step,
-                          int T, int stop_id, int alt_stop_id, int *ids, int *lens, const int *cmap) {
-    const int V = c->gpt.vocab, ld = (V + 63) / 64 * 64, blk = std::min(R, std::max(1, c->tune.sample_rows));
-    CAPDEC_TRY(c->slogits.ensure((size_t)blk * ld * 4));
-    for (int r0 = 0; r0 < R; r0 += blk) {
-        const int nr = std::min(blk, R - r0);
-        CAPDEC_TRY(lm_head_logits(c, h0 + (size_t)r0 * ldh, ldh, nr, c->slogits.as<float>(), ld));
-        ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_sample_top_p(c->stream, c->slogits.as<float>(), ld, nr, r0, V, inv_temp, a.top_p, a.seed, a.u, a.cap_off,
-                                       step, T, stop_id, alt_stop_id, ids, lens, c->done.as<uint8_t>(), c->next_tok.as<int>(),
-                                       c->alive.as<int>(), a.logp, cmap));
-    }
-    return 0;
-}
 
 // Does this call run the logits processors (capdec_set_logits_processors / capdec_set_logit_bias)?  top_k counts in the
 // sampling decode only.
@@ -200,43 +194,44 @@ static bool processors_on(const capdec_ctx *c, bool sampling) {
     return p.theta != 1.0f || p.ngram > 0 || p.min_len > 0 || c->proc_bias_n > 0 || (sampling && p.top_k > 0);
 }
 
-// One step over `R` activation rows with the logits processors: per block of tune.sample_rows rows, lm_head_logits, the
-// processors in place (process.hip), then the one-pass selection at the block's offset into c->lse / c->topv / c->topi
-// (greedy, beam: what lm_head_select leaves, the step kernels follow unchanged) or, with `smp`, top_k and the
-// nucleus-sampling kernel (what lm_head_sample does).  hist: the rows' histories [captions, beam, T] -- `ids` or
-// BeamState::tokens; `step` entries of each are read.
-static int lm_head_process(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const SampleArgs *smp,
-                           int step, int T, int beam, int stop_id, int alt_stop_id, const int *hist, int *ids, int *lens,
-                           const int *cmap) {
+// One step over `R` activation rows through materialised logits, tune.sample_rows rows at a time (the fp32 logits of 5000
+// rows of GPT-2's vocabulary are 1 GB): lm_head_logits, with `proc` the processors in place (process.hip), then
+//   greedy, beam  the one-pass selection at the block's offset into c->lse / c->topv / c->topi: what lm_head_select
+//                 leaves, the step kernels follow unchanged
+//   sampling      top_k where it removes something, the nucleus-sampling kernel (it writes what launch_greedy_step
+//                 writes, into gs), the logp shift under top_k.
+// hist: the rows' histories [captions, beam, T] -- `ids` or BeamState::tokens; `step` entries of each are read.
+static int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const DecodeCall &a,
+                        const GreedyState &gs, bool proc, int step, int beam, const int *hist) {
     const int V = c->gpt.vocab, ld = (V + 63) / 64 * 64, blk = std::min(R, std::max(1, c->tune.sample_rows));
     const LogitsProc &p = c->proc;
     const float *bias = c->proc_bias_n > 0 ? c->pbias.as<float>() : nullptr;
-    const bool cut = smp && p.top_k > 0 && p.top_k < V;
+    const bool cut = proc && a.sample && p.top_k > 0 && p.top_k < V;
     CAPDEC_TRY(c->slogits.ensure((size_t)blk * ld * 4));
-    if (!smp) {
+    if (!a.sample) {
         CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
         CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
         CAPDEC_TRY(c->topi.ensure((size_t)R * k * 4));
-    } else if (cut && smp->logp) {
+    } else if (cut && a.logp) {
         CAPDEC_TRY(c->pcorr.ensure((size_t)blk * 4));
     }
     float *lg = c->slogits.as<float>();
+    float *corr = cut && a.logp ? c->pcorr.as<float>() : nullptr;
     for (int r0 = 0; r0 < R; r0 += blk) {
         const int nr = std::min(blk, R - r0);
         CAPDEC_TRY(lm_head_logits(c, h0 + (size_t)r0 * ldh, ldh, nr, lg, ld));
         ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_logits_process(c->stream, lg, ld, nr, r0, V, cmap, beam, hist, T, step, p, bias, stop_id, alt_stop_id));
-        if (!smp) {
+        if (proc)
+            CAPDEC_TRY(launch_logits_process(c->stream, lg, ld, nr, r0, V, gs.cmap, beam, hist, a.T, step, p, bias, a.stop_id,
+                                             a.alt_stop_id));
+        if (!a.sample) {
             CAPDEC_TRY(launch_logits_select(c->stream, lg, ld, nr, V, k, inv_temp, c->lse.as<float>() + r0,
                                             c->topv.as<float>() + (size_t)r0 * k, c->topi.as<int>() + (size_t)r0 * k));
             continue;
         }
-        float *corr = cut && smp->logp ? c->pcorr.as<float>() : nullptr;
         if (cut) CAPDEC_TRY(launch_logits_topk(c->stream, lg, ld, nr, V, p.top_k, inv_temp, corr));
-        CAPDEC_TRY(launch_sample_top_p(c->stream, lg, ld, nr, r0, V, inv_temp, smp->top_p, smp->seed, smp->u, smp->cap_off, step, T,
-                                       stop_id, alt_stop_id, ids, lens, c->done.as<uint8_t>(), c->next_tok.as<int>(),
-                                       c->alive.as<int>(), smp->logp, cmap));
-        if (corr) CAPDEC_TRY(launch_logp_shift(c->stream, corr, nr, r0, cmap, lens, step, T, smp->logp));
+        CAPDEC_TRY(launch_sample_top_p(c->stream, gs, lg, ld, nr, r0, V, inv_temp, a.top_p, a.seed, a.u, a.cap_off, step));
+        if (corr) CAPDEC_TRY(launch_logp_shift(c->stream, corr, nr, r0, gs.cmap, gs.lens, step, a.T, a.logp));
     }
     return 0;
 }
@@ -294,17 +289,15 @@ static int chunk_captions(capdec_ctx *c, int n, int beam, int ctx) {
 }
 
 // ---------------------------------------------------------------------------- decode drivers
-static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int beam, bool greedy, int stop_id,
-                        int alt_stop_id, int T, float temperature, int *ids, int *lens, float *scores, int *order,
-                        const int *forced = nullptr, float *stats = nullptr, int kv_stat_off = 0,
-                        const SampleArgs *smp = nullptr) {     // smp: the greedy loop with the arg-max replaced by a draw
+static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const DecodeCall &a) {
     const Gpt2 &g = c->gpt;
-    const int d = g.d;
+    const int d = g.d, P = a.P, T = a.T, beam = a.beam;
+    const bool greedy = a.greedy;
     const int ctx = P + T - 1;
     const int rows = nc * beam;
-    const int k = (greedy && stats) ? 2 : beam;   // candidates kept per row (teacher-forced statistics: top-2)
-    const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);
-    const bool proc = !forced && processors_on(c, smp != nullptr);      // (teacher forcing ignores the processors)
+    const int k = (greedy && a.stats) ? 2 : beam;   // candidates kept per row (teacher-forced statistics: top-2)
+    const float inv_temp = 1.0f / (a.temperature > 0.f ? a.temperature : 1.0f);
+    const bool proc = !a.forced && processors_on(c, a.sample);      // (teacher forcing ignores the processors)
     KvCache kv;
     CAPDEC_TRY(ensure_kv(c, kv, rows, ctx));
     kv.fixed_variant = c->batch_invariant;
@@ -314,6 +307,7 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     CAPDEC_TRY(c->alive.ensure(sizeof(int)));
     CAPDEC_TRY(c->done.ensure((size_t)rows));
     BeamState bs;
+    GreedyState gs;
     if (!greedy) {
         CAPDEC_TRY(c->tokens.ensure((size_t)rows * T * 4));
         CAPDEC_TRY(c->scores.ensure((size_t)rows * 4));
@@ -331,16 +325,42 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
         bs.diverge = c->diverge;
         // (distinct-K/V-slot statistic: this chunk's slice of the per-call array decode_common zeroed; nothing is read back
         //  here -- capdec_decode_counters sums it when somebody asks)
-        bs.kv_stat = c->kvstat.p ? c->kvstat.as<unsigned>() + (size_t)kv_stat_off * 2 : nullptr;
+        bs.kv_stat = c->kvstat.p ? c->kvstat.as<unsigned>() + (size_t)a.cap_off * 2 : nullptr;
         CAPDEC_HIP(hipMemsetAsync(bs.tokens, 0, (size_t)rows * T * 4, c->stream));
         CAPDEC_HIP(hipMemsetAsync(bs.anc, 0, (size_t)rows * ctx, c->stream));
     } else {
-        CAPDEC_HIP(hipMemsetAsync(ids, 0, (size_t)nc * T * 4, c->stream));
-        CAPDEC_HIP(hipMemsetAsync(lens, 0, (size_t)nc * 4, c->stream));
-        if (smp && smp->logp) CAPDEC_HIP(hipMemsetAsync(smp->logp, 0, (size_t)nc * T * 4, c->stream));
+        gs.ids = a.ids;
+        gs.lens = a.lens;
+        gs.done = c->done.as<uint8_t>();
+        gs.next_tok = c->next_tok.as<int>();
+        gs.alive_count = c->alive.as<int>();
+        gs.logp = a.logp;
+        gs.T = T;
+        gs.stop_id = a.stop_id;
+        gs.alt_stop_id = a.alt_stop_id;
+        CAPDEC_HIP(hipMemsetAsync(a.ids, 0, (size_t)nc * T * 4, c->stream));
+        CAPDEC_HIP(hipMemsetAsync(a.lens, 0, (size_t)nc * 4, c->stream));
+        if (a.logp) CAPDEC_HIP(hipMemsetAsync(a.logp, 0, (size_t)nc * T * 4, c->stream));
     }
     CAPDEC_HIP(hipMemsetAsync(c->done.p, 0, (size_t)rows, c->stream));
     CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
+    const int *hist = greedy ? a.ids : bs.tokens;       // the rows' own histories, for the logits processors
+
+    // Select and advance: the lm_head route of this call over the R rows of h at h0 (row stride ldh), then the step
+    // kernel of the decode.  hbeam: rows per caption for the history lookup; cmap: the compaction in force.
+    auto select_and_advance = [&](const float *h0, int ldh, int R, int step, int hbeam, const int *cmap) -> int {
+        gs.cmap = cmap;
+        if (proc || a.sample) CAPDEC_TRY(lm_head_rows(c, h0, ldh, R, k, inv_temp, a, gs, proc, step, hbeam, hist));
+        else CAPDEC_TRY(lm_head_select(c, h0, ldh, R, k, inv_temp));
+        if (a.sample) return 0;                         // (the sampling kernel has advanced the state)
+        ProfScope ps(c, F_SELECT);
+        const float *lse = c->lse.as<float>(), *topv = c->topv.as<float>();
+        const int *topi = c->topi.as<int>();
+        if (greedy) return launch_greedy_step(c->stream, gs, topi, R, step, k, a.forced, topv, lse, a.stats);
+        if (step == 0) return launch_beam_init(c->stream, bs, lse, topv, topi, R, beam, k, T, ctx, P, a.stop_id);
+        return launch_beam_step(c->stream, bs, lse, topv, topi, R / beam, beam, k, T, ctx, step, P + step - 1, g.vocab,
+                                a.stop_id, cmap);
+    };
 
     // ---- step 0: prefill the prefix (positions 0..P-1), logits of the last prefix row
     { ProfScope ps(c, F_EMBED); CAPDEC_TRY(launch_embed_prefix(c->stream, prefix, g.wpe, c->h.as<float>(), nc, P, 0, d)); }
@@ -350,25 +370,8 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
     sp.P = P;
     sp.beam = beam;
     CAPDEC_TRY(gpt2_body(c, sp, kv));
-    const int *hist = greedy ? ids : bs.tokens;       // the rows' own histories, for the logits processors
-    if (proc)       // (one row per caption and an empty history: nothing is read through `hist` yet)
-        CAPDEC_TRY(lm_head_process(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp, smp, 0, T, 1, stop_id,
-                                   alt_stop_id, hist, ids, lens, nullptr));
-    else if (!smp) CAPDEC_TRY(lm_head_select(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, k, inv_temp));
-    if (smp) {
-        if (!proc)
-            CAPDEC_TRY(lm_head_sample(c, c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, inv_temp, *smp, 0, T, stop_id,
-                                      alt_stop_id, ids, lens, nullptr));
-    } else if (greedy) {
-        ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_greedy_step(c->stream, c->topi.as<int>(), nc, 0, T, stop_id, alt_stop_id, ids, lens,
-                                      c->done.as<uint8_t>(), c->next_tok.as<int>(), c->alive.as<int>(), nullptr, k, forced,
-                                      c->topv.as<float>(), c->lse.as<float>(), stats));
-    } else {
-        ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_beam_init(c->stream, bs, c->lse.as<float>(), c->topv.as<float>(), c->topi.as<int>(), nc,
-                                    beam, k, T, ctx, P, stop_id));
-    }
+    // (one row per caption and an empty history: nothing is read through `hist` yet)
+    CAPDEC_TRY(select_and_advance(c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, 0, 1, nullptr));
     // ---- steps 1..T-1: one token per row per step.  Finished captions (stop token on every beam) are dropped from
     // the batch at the poll points: `cmap` lists the captions still generating, the activations of a step are the
     // na * beam rows of those captions only, while KV cache / ancestor table / beam state keep their original rows.
@@ -422,36 +425,19 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, int P, int b
         sd.anc_stride = ctx;
         sd.cmap = cmap;
         CAPDEC_TRY(gpt2_body(c, sd, kv));
-        if (proc) {
-            CAPDEC_TRY(lm_head_process(c, c->h.as<float>(), d, arows, k, inv_temp, smp, i, T, beam, stop_id, alt_stop_id, hist,
-                                       ids, lens, cmap));
-            if (smp) continue;
-        } else if (smp) {
-            CAPDEC_TRY(lm_head_sample(c, c->h.as<float>(), d, arows, inv_temp, *smp, i, T, stop_id, alt_stop_id, ids, lens, cmap));
-            continue;
-        } else {
-            CAPDEC_TRY(lm_head_select(c, c->h.as<float>(), d, arows, k, inv_temp));
-        }
-        ProfScope ps(c, F_SELECT);
-        if (greedy) {
-            CAPDEC_TRY(launch_greedy_step(c->stream, c->topi.as<int>(), arows, i, T, stop_id, alt_stop_id, ids, lens,
-                                          c->done.as<uint8_t>(), c->next_tok.as<int>(), c->alive.as<int>(), cmap, k, forced,
-                                          c->topv.as<float>(), c->lse.as<float>(), stats));
-        } else {
-            CAPDEC_TRY(launch_beam_step(c->stream, bs, c->lse.as<float>(), c->topv.as<float>(), c->topi.as<int>(), na,
-                                        beam, k, T, ctx, i, pos, g.vocab, stop_id, cmap));
-        }
+        CAPDEC_TRY(select_and_advance(c->h.as<float>(), d, arows, i, beam, cmap));
     }
     if (!greedy) {
         ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_beam_finalize(c->stream, bs, nc, beam, T, ids, lens, scores, order));
+        CAPDEC_TRY(launch_beam_finalize(c->stream, bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
     }
     return 0;
 }
 
-static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int beam, bool greedy, int stop_id,
-                         int alt_stop_id, int T, float temperature, int *ids, int *lens, float *scores,
-                         int *order, const int *forced = nullptr, float *stats = nullptr, const SampleArgs *smp = nullptr) {
+static int decode_common(capdec_ctx *c, const float *prefix, int n, const DecodeCall &call) {
+    const int P = call.P, T = call.T, beam = call.beam;
+    const bool greedy = call.greedy;
+    const int *forced = call.forced;
     CAPDEC_CHECK(c && c->gpt.loaded, "decode: GPT-2 weights not loaded");
     CAPDEC_CHECK(n >= 0 && P >= 1 && T >= 1, "decode: bad sizes");
     CAPDEC_CHECK(P + T - 1 <= c->gpt.n_pos, "decode: prefix + entry_length exceeds n_positions");
@@ -485,15 +471,17 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, int P, int b
     c->k3_rows = 0;
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int nc = std::min(chunk, n - c0);
-        SampleArgs sa;
-        if (smp) sa = SampleArgs{smp->top_p, smp->seed, smp->u ? smp->u + (size_t)c0 * T : nullptr,
-                                 smp->logp ? smp->logp + (size_t)c0 * T : nullptr, c0};
-        CAPDEC_TRY(decode_chunk(c, prefix + (size_t)c0 * P * c->gpt.d, nc, P, beam, greedy, stop_id, alt_stop_id, T,
-                                temperature, ids + (size_t)c0 * beam * T, lens + (size_t)c0 * beam,
-                                scores ? scores + (size_t)c0 * beam : nullptr,
-                                order ? order + (size_t)c0 * beam : nullptr,
-                                forced ? forced + (size_t)c0 * T : nullptr, stats ? stats + (size_t)c0 * T * 3 : nullptr, c0,
-                                smp ? &sa : nullptr));
+        DecodeCall a = call;
+        a.ids += (size_t)c0 * beam * T;
+        a.lens += (size_t)c0 * beam;
+        if (a.scores) a.scores += (size_t)c0 * beam;
+        if (a.order) a.order += (size_t)c0 * beam;
+        if (a.forced) a.forced += (size_t)c0 * T;
+        if (a.stats) a.stats += (size_t)c0 * T * 3;
+        if (a.u) a.u += (size_t)c0 * T;
+        if (a.logp) a.logp += (size_t)c0 * T;
+        a.cap_off = c0;
+        CAPDEC_TRY(decode_chunk(c, prefix + (size_t)c0 * P * c->gpt.d, nc, a));
     }
     CAPDEC_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -549,8 +537,10 @@ int capdec_wte_lookup(capdec_ctx *c, const int32_t *ids, int n, float *out) {
 int capdec_decode_greedy(capdec_ctx *c, const float *prefix, int n, int P, int stop_id, int alt_stop_id,
                          int entry_length, int32_t *ids, int32_t *lens) {
     CAPDEC_CHECK(c && (n == 0 || (prefix && ids && lens)), "decode_greedy: null argument");
-    return decode_common(c, prefix, n, P, 1, true, stop_id, alt_stop_id, entry_length, 1.0f, ids, lens, nullptr,
-                         nullptr);
+    DecodeCall a;
+    a.P = P; a.stop_id = stop_id; a.alt_stop_id = alt_stop_id; a.T = entry_length;
+    a.ids = ids; a.lens = lens;
+    return decode_common(c, prefix, n, a);
 }
 
 int capdec_decode_greedy_forced(capdec_ctx *c, const float *prefix, int n, int P, int entry_length,
@@ -560,8 +550,11 @@ int capdec_decode_greedy_forced(capdec_ctx *c, const float *prefix, int n, int P
     CAPDEC_TRY(lens.ensure((size_t)std::max(n, 1) * 4));
     const bool compact = c->compact;
     c->compact = false;                       // every caption runs every step
-    const int rc = decode_common(c, prefix, n, P, 1, true, -1, -1, entry_length, 1.0f, ids, lens.as<int>(), nullptr, nullptr,
-                                 forced, stats);
+    DecodeCall a;
+    a.P = P; a.T = entry_length;
+    a.ids = ids; a.lens = lens.as<int>();
+    a.forced = forced; a.stats = stats;
+    const int rc = decode_common(c, prefix, n, a);
     c->compact = compact;
     lens.release();
     return rc;
@@ -572,17 +565,21 @@ int capdec_decode_sample(capdec_ctx *c, const float *prefix, int n, int P, int s
                          float *logp) {
     CAPDEC_CHECK(top_p == top_p && temperature == temperature, "decode_sample: top_p or temperature is NaN");
     CAPDEC_CHECK(c && (n == 0 || (prefix && ids && lens)), "decode_sample: null argument");
-    const SampleArgs smp{top_p, seed, u, logp, 0};
-    return decode_common(c, prefix, n, P, 1, true, stop_id, alt_stop_id, entry_length, temperature, ids, lens, nullptr,
-                         nullptr, nullptr, nullptr, &smp);
+    DecodeCall a;
+    a.P = P; a.stop_id = stop_id; a.alt_stop_id = alt_stop_id; a.T = entry_length; a.temperature = temperature;
+    a.ids = ids; a.lens = lens;
+    a.sample = true; a.top_p = top_p; a.seed = seed; a.u = u; a.logp = logp;
+    return decode_common(c, prefix, n, a);
 }
 
 int capdec_decode_beam(capdec_ctx *c, const float *prefix, int n, int P, int beam, int stop_id, int entry_length,
                        float temperature, int32_t *ids, int32_t *lens, float *scores, int32_t *order) {
     CAPDEC_CHECK(c && (n == 0 || (prefix && ids && lens && scores)), "decode_beam: null argument");
     CAPDEC_CHECK(c->gpt.loaded && c->gpt.vocab >= beam, "decode_beam: vocabulary smaller than the beam");
-    return decode_common(c, prefix, n, P, beam, false, stop_id, -1, entry_length, temperature, ids, lens, scores,
-                         order);
+    DecodeCall a;
+    a.P = P; a.beam = beam; a.greedy = false; a.stop_id = stop_id; a.T = entry_length; a.temperature = temperature;
+    a.ids = ids; a.lens = lens; a.scores = scores; a.order = order;
+    return decode_common(c, prefix, n, a);
 }
 
 

@@ -205,6 +205,24 @@ int ln_gemm_packed(capdec_ctx *c, const float *h, int ldh, const float *lnw, con
     return gemm_packed(c, c->xpk.p, W, C, ldc, M, N, K, bias, act, nullptr, 0, packed_out, nullptr, nullptr, qkv_scatter);
 }
 
+int topk_workspace(capdec_ctx *c, int rows, int ntiles, int k, TopkOut *o) {
+    CAPDEC_TRY(c->tmax.ensure((size_t)rows * ntiles * 4));
+    CAPDEC_TRY(c->tsum.ensure((size_t)rows * ntiles * 4));
+    CAPDEC_TRY(c->cval.ensure((size_t)rows * ntiles * k * 4));
+    CAPDEC_TRY(c->cidx.ensure((size_t)rows * ntiles * k * 4));
+    CAPDEC_TRY(c->lse.ensure((size_t)rows * 4));
+    *o = TopkOut{c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()};
+    return 0;
+}
+
+// The tile of a fused top-k launch on two fp16 planes: 256 x 128 with one accumulator set once the grid is many rounds deep
+// (each W panel is then fetched by half as many row tiles); small row counts keep the 128-row tile (more blocks, the same
+// partial lists).  wide_ok: max |w| < 16 (GemmEpilogue::wide_ok).  (CAPDEC_H2W >= 2: forced, tests)
+static bool topk_wide_tile(const capdec_ctx *c, bool wide_ok, int M) {
+    const int h2w = c->tune.h2w;
+    return wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2);
+}
+
 int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const float *lnb, float eps, const float *W,
                  int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3) {
     const double flops = 2.0 * M * (double)N * K;
@@ -229,10 +247,7 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
     CAPDEC_TRY(planes_of(c, W, N, K, true, &pl, -1, &wide_ok));
     if (c->gemm_mode == GEMM_F16X2) {
         ProfScope ps(c, F_LMHEAD_H2, flops);
-        // 256 x 128 tiles with one accumulator set once the grid is many rounds deep (each W panel is then fetched by half
-        // as many row tiles); small row counts keep the 128-row tile (more blocks, the same partial lists)
-        const int h2w = c->tune.h2w;
-        if (wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2)) {   // (CAPDEC_H2W >= 2: forced, tests)
+        if (topk_wide_tile(c, wide_ok, M)) {
             *k3 = k3_ok;
             return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o);
         }
@@ -265,10 +280,8 @@ int gemm_topk(capdec_ctx *c, const void *A, const float *Bt, bool cache, bool b_
         const void *pl = nullptr;
         bool wide_ok = false;
         CAPDEC_TRY(planes_of(c, Bt, N, K, cache, &pl, PK_F16X2, &wide_ok));
-        wide_ok = wide_ok || b_small;
         ProfScope ps(c, F_NEAREST, flops);
-        const int h2w = c->tune.h2w;      // (the tile rule of ln_gemm_topk)
-        if (wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2))
+        if (topk_wide_tile(c, wide_ok || b_small, M))
             CAPDEC_TRY(launch_gemm_h2w_topk(c->stream, A, pl, M, N, K, k, 1.0f, o));
         else
             CAPDEC_TRY(launch_gemm_f16x2p_topk(c->stream, A, pl, M, N, K, k, 1.0f, o));

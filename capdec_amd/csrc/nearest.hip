@@ -65,13 +65,9 @@ int nearest_run(capdec_ctx *c, const float *x, int rows, int d, const float *tab
     const int blk = std::min(rows, NEAREST_ROWS), nt = gemm_tiles_n(n);
     if (packed) CAPDEC_TRY(c->xpk.ensure(x3_packed_bytes(blk, d, PK_F16X2)));
     else CAPDEC_TRY(c->xl.ensure((size_t)blk * d * 4));
-    CAPDEC_TRY(c->tmax.ensure((size_t)blk * nt * 4));
-    CAPDEC_TRY(c->tsum.ensure((size_t)blk * nt * 4));
-    CAPDEC_TRY(c->cval.ensure((size_t)blk * nt * k * 4));
-    CAPDEC_TRY(c->cidx.ensure((size_t)blk * nt * k * 4));
-    CAPDEC_TRY(c->lse.ensure((size_t)blk * 4));
+    TopkOut o;
+    CAPDEC_TRY(topk_workspace(c, blk, nt, k, &o));
     if (!sims) CAPDEC_TRY(c->topv.ensure((size_t)blk * k * 4));
-    const TopkOut o{c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()};
     int *row_bad = c->n_bad.as<int>() + 1;
     for (int r0 = 0; r0 < rows; r0 += NEAREST_ROWS) {
         const int nr = std::min(NEAREST_ROWS, rows - r0);

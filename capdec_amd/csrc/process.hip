@@ -1,5 +1,5 @@
 // Logits processors over materialised logits (capdec_set_logits_processors / capdec_set_logit_bias): what the decode loop
-// runs between the plain lm_head GEMM and the selection when a processor or a bias is set (decode.hip: lm_head_process).
+// runs between the plain lm_head GEMM and the selection when a processor or a bias is set (decode.hip: lm_head_rows).
 //
 // At step i a row has raw logits l[0..V) (before the division by the temperature) and a history g = (g_0 .. g_{i-1}): the
 // tokens its own hypothesis has generated so far -- the caption's `ids` (greedy, sampling) or that beam's row of
@@ -20,7 +20,9 @@
 // Every sum has a fixed order (a lane's elements in index order, the wavefront's DPP tree, the wavefronts in order) and one
 // workgroup owns a row whatever the launch holds: a row's result does not depend on the launch size, the row blocks, the
 // chunking or the compaction of the batch.  The ld - V pad columns of a row are never read or written.
-#include "common.h"
+// The candidate lists, the winner-pops round, the tie rule, order_key and the workgroup reductions are row_select.h's: the
+// ones launch_topk_merge and the sampling kernel use.
+#include "row_select.h"
 
 namespace capdec {
 
@@ -29,8 +31,6 @@ namespace {
 constexpr int PRC_THREADS = 256, PRC_WAVES = PRC_THREADS / WAVE;
 constexpr int PRC_HIST_MAX = 1024;      // entry_length <= 1024 (decode_common)
 constexpr int TOPK_THREADS = 1024, TOPK_WAVES = TOPK_THREADS / WAVE;
-
-__device__ __forceinline__ bool better_than(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 // history row of logits row r of a block: activation row row0 + r of the step, exactly as greedy_step_kernel (beam == 1)
 // and beam_step_kernel find their rows
@@ -95,26 +95,6 @@ __global__ __launch_bounds__(PRC_THREADS) void logits_process_kernel(float *__re
     }
 }
 
-// one candidate into a lane's descending list of K (the insertion of topk_merge_kernel)
-template <int K>
-__device__ __forceinline__ void topk_push(float (&bv)[K], int (&bi)[K], float v, int i) {
-    if (!better_than(v, i, bv[K - 1], bi[K - 1])) return;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (better_than(v, i, bv[j], bi[j])) {
-            const float tv = bv[j]; const int ti = bi[j];
-            bv[j] = v; bi[j] = i; v = tv; i = ti;
-        }
-    }
-}
-// running (max, sum exp(x - max)) of a lane over one more group of values whose maximum is gm
-__device__ __forceinline__ void online_rescale(float &m, float &s, float gm) {
-    if (gm > m) {
-        s = m > -INFINITY ? s * expf(m - gm) : 0.f;
-        m = gm;
-    }
-}
-
 template <int K>
 __global__ __launch_bounds__(PRC_THREADS) void logits_select_kernel(const float *__restrict__ logits, int ld, int V,
                                                                     float inv_temp, float *__restrict__ lse,
@@ -125,26 +105,24 @@ __global__ __launch_bounds__(PRC_THREADS) void logits_select_kernel(const float 
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const float *x = logits + (size_t)r * ld;
     float m = -INFINITY, s = 0.f;
-    float bv[K];
-    int bi[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
+    LaneTopk<K> best;
+    best.clear();
     const int V4 = V & ~3;
     for (int j = tid * 4; j < V4; j += PRC_THREADS * 4) {
         const float4 q = *reinterpret_cast<const float4 *>(x + j);
         const float v0 = q.x * inv_temp, v1 = q.y * inv_temp, v2 = q.z * inv_temp, v3 = q.w * inv_temp;
         online_rescale(m, s, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
         if (m > -INFINITY) s += ((expf(v0 - m) + expf(v1 - m)) + expf(v2 - m)) + expf(v3 - m);
-        topk_push<K>(bv, bi, v0, j);
-        topk_push<K>(bv, bi, v1, j + 1);
-        topk_push<K>(bv, bi, v2, j + 2);
-        topk_push<K>(bv, bi, v3, j + 3);
+        best.push(v0, j);
+        best.push(v1, j + 1);
+        best.push(v2, j + 2);
+        best.push(v3, j + 3);
     }
     for (int j = V4 + tid; j < V; j += PRC_THREADS) {
         const float v = x[j] * inv_temp;
         online_rescale(m, s, v);
         if (m > -INFINITY) s += expf(v - m);
-        topk_push<K>(bv, bi, v, j);
+        best.push(v, j);
     }
     // logsumexp: lanes -> wavefront -> workgroup, each in a fixed order
     const float M = wave_max(m);
@@ -153,19 +131,9 @@ __global__ __launch_bounds__(PRC_THREADS) void logits_select_kernel(const float 
     // the wavefront's K best: K rounds of an arg-max butterfly, the lane that held the winner pops it
 #pragma unroll
     for (int q = 0; q < K; ++q) {
-        float gv = bv[0];
-        int gi = bi[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(gv, o, 64);
-            const int oi = __shfl_xor(gi, o, 64);
-            if (better_than(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-        }
-        if (gi == bi[0] && gv == bv[0]) {
-#pragma unroll
-            for (int j = 0; j + 1 < K; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
-            bv[K - 1] = -INFINITY; bi[K - 1] = 0x7fffffff;
-        }
+        float gv;
+        int gi;
+        best.pop_best(gv, gi);
         if (lane == 0) { cv[wave * K + q] = gv; ci[wave * K + q] = gi; }
     }
     __syncthreads();
@@ -177,50 +145,10 @@ __global__ __launch_bounds__(PRC_THREADS) void logits_select_kernel(const float 
 #pragma unroll
     for (int w = 0; w < PRC_WAVES; ++w) S += wm[w] > -INFINITY ? ws[w] * expf(wm[w] - Mb) : 0.f;
     lse[r] = Mb + logf(S);
+    best.clear();
+    for (int q = 0; q < PRC_WAVES * K; ++q) best.push(cv[q], ci[q]);
 #pragma unroll
-    for (int j = 0; j < K; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
-    for (int q = 0; q < PRC_WAVES * K; ++q) topk_push<K>(bv, bi, cv[q], ci[q]);
-#pragma unroll
-    for (int j = 0; j < K; ++j) { top_val[(size_t)r * K + j] = bv[j]; top_idx[(size_t)r * K + j] = bi[j]; }
-}
-
-// order-preserving integer image of a float (-0 counts as +0: the two compare equal)
-__device__ __forceinline__ uint32_t order_key(float f) {
-    if (f == 0.f) f = 0.f;
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-// sums over the workgroup, the same value in every thread; successive calls alternate `par` (one barrier per call)
-__device__ __forceinline__ int block_count(int v, int *red, int par) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    int *r = red + par * TOPK_WAVES;
-    if ((threadIdx.x & (WAVE - 1)) == 0) r[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < TOPK_WAVES; ++w) t += r[w];
-    return t;
-}
-__device__ __forceinline__ float block_sum_f(float v, float *red, int par) {
-    v = wave_sum(v);
-    float *r = red + par * TOPK_WAVES;
-    if ((threadIdx.x & (WAVE - 1)) == 0) r[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < TOPK_WAVES; ++w) t += r[w];
-    return t;
-}
-__device__ __forceinline__ float block_max_f(float v, float *red, int par) {
-    v = wave_max(v);
-    float *r = red + par * TOPK_WAVES;
-    if ((threadIdx.x & (WAVE - 1)) == 0) r[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    float t = r[0];
-#pragma unroll
-    for (int w = 1; w < TOPK_WAVES; ++w) t = fmaxf(t, r[w]);
-    return t;
+    for (int j = 0; j < K; ++j) { top_val[(size_t)r * K + j] = best.v[j]; top_idx[(size_t)r * K + j] = best.i[j]; }
 }
 
 // tau = the largest key with at least top_k keys >= tau: the top_k-th largest value, built bit by bit from the top (32
@@ -239,22 +167,22 @@ __global__ __launch_bounds__(TOPK_THREADS) void logits_topk_kernel(float *__rest
         const uint32_t cand = tau | (1u << bit);
         int cnt = 0;
         for (int j = tid; j < V; j += TOPK_THREADS) cnt += order_key(x[j]) >= cand ? 1 : 0;
-        cnt = block_count(cnt, cred, par);
+        cnt = block_count<TOPK_WAVES>(cnt, cred, par);
         par ^= 1;
         if (cnt >= top_k) tau = cand;
     }
     if (corr) {
         float m = -INFINITY;
         for (int j = tid; j < V; j += TOPK_THREADS) m = fmaxf(m, x[j] * inv_temp);
-        m = block_max_f(m, fred, 0);
+        m = block_max<TOPK_WAVES>(m, fred, 0);
         float all = 0.f, kept = 0.f;
         for (int j = tid; j < V; j += TOPK_THREADS) {
             const float v = x[j], e = expf(v * inv_temp - m);
             all += e;
             kept += order_key(v) >= tau ? e : 0.f;
         }
-        all = block_sum_f(all, fred, 1);
-        kept = block_sum_f(kept, fred, 0);
+        all = block_sum<TOPK_WAVES>(all, fred, 1);
+        kept = block_sum<TOPK_WAVES>(kept, fred, 0);
         if (tid == 0) corr[r] = logf(kept) - logf(all);
     }
     __syncthreads();                                             // every read of the row is behind us

@@ -13,10 +13,11 @@
 // 30 significant bits of k, one block reduction per step.  Rows whose arg-max alone carries more than top_p (and every
 // row at top_p <= 0) leave after the two opening reductions; rows at top_p >= 1 skip the bisection (tau = 0).
 //
-// Every sum has a fixed order -- a lane's registers in index order, the wavefront's DPP tree, the 16 wavefronts in order,
-// and for the pick the 64-token segments in id order -- and one workgroup owns a row whatever the launch holds, so a
-// row's result does not depend on the launch size, the chunking or the compaction of the batch.
-#include "common.h"
+// Every sum has a fixed order -- a lane's registers in index order, the wavefront's DPP tree, the 16 wavefronts in order
+// (row_select.h: block_sum / block_max), and for the pick the 64-token segments in id order -- and one workgroup owns a row
+// whatever the launch holds, so a row's result does not depend on the launch size, the chunking or the compaction of the
+// batch.  A pick is written by greedy_emit (common.h), as the arg-max of the greedy step is.
+#include "row_select.h"
 
 namespace capdec {
 
@@ -24,28 +25,6 @@ namespace {
 
 constexpr int SMP_THREADS = 1024, SMP_WAVES = SMP_THREADS / WAVE;
 
-// sum over the workgroup, the same value in every thread; `red` holds 2 x SMP_WAVES floats and successive calls alternate
-// `par` so that one barrier per call is enough
-__device__ __forceinline__ float block_sum(float v, float *red, int par) {
-    v = wave_sum(v);
-    float *r = red + par * SMP_WAVES;
-    if ((threadIdx.x & (WAVE - 1)) == 0) r[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < SMP_WAVES; ++w) t += r[w];
-    return t;
-}
-__device__ __forceinline__ float block_max(float v, float *red, int par) {
-    v = wave_max(v);
-    float *r = red + par * SMP_WAVES;
-    if ((threadIdx.x & (WAVE - 1)) == 0) r[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    float t = r[0];
-#pragma unroll
-    for (int w = 1; w < SMP_WAVES; ++w) t = fmaxf(t, r[w]);
-    return t;
-}
 // inclusive prefix sum over the 64 lanes of a wavefront, in lane order
 __device__ __forceinline__ float wave_scan(float v) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -77,37 +56,18 @@ __device__ __forceinline__ float exp_shifted(float s, float m) {
     return __expf(d);
 }
 
-struct SampleOut {
-    int *ids, *lens;
-    uint8_t *done;
-    int *next_tok, *alive_count;
-    float *logp;            // [captions, T] or nullptr
-};
-
-// what greedy_step_kernel writes, for the caption `row` (the caller has checked done[row] == 0)
-__device__ __forceinline__ void sample_emit(const SampleOut &o, int row, int step, int T, int tok, float lp, int stop_id,
-                                            int alt_stop_id) {
-    o.next_tok[row] = tok;
-    o.ids[(size_t)row * T + step] = tok;
-    o.lens[row] = step + 1;
-    if (o.logp) o.logp[(size_t)row * T + step] = lp;
-    if (tok == stop_id || tok == alt_stop_id) o.done[row] = 1;
-    else atomicAdd(o.alive_count, 1);
-}
-
 // NV > 0: the row (V <= 1024 NV) lives in registers; NV == 0: any V, every pass re-reads the row (from L2)
 template <int NV>
 __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *__restrict__ logits, int ld, int V,
                                                                    int row0, float inv_temp, float top_p, uint64_t seed,
                                                                    const float *__restrict__ u_in, int cap_off, int step,
-                                                                   int T, int stop_id, int alt_stop_id, SampleOut o,
-                                                                   const int *__restrict__ cmap) {
+                                                                   GreedyState o) {
     __shared__ float red[2 * SMP_WAVES];
     __shared__ float seg[(NV > 0 ? NV : 1) * SMP_WAVES];
     __shared__ float pick_rem;
     __shared__ int pick_seg;
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int row = cmap ? cmap[row0 + r] : row0 + r;            // caption (logits row r = activation row row0 + r of the step)
+    const int row = o.cmap ? o.cmap[row0 + r] : row0 + r;        // caption (logits row r = activation row row0 + r of the step)
     if (o.done[row]) return;                                     // (uniform over the workgroup: nothing below runs)
     const float *x = logits + (size_t)r * ld;
     const int nv = NV > 0 ? NV : (V + SMP_THREADS - 1) / SMP_THREADS;
@@ -124,7 +84,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *
     } else {
         for (int i = 0; i < nv; ++i) m = fmaxf(m, scaled(i));
     }
-    m = block_max(m, red, 0);
+    m = block_max<SMP_WAVES>(m, red, 0);
     auto val = [&](int i) {
         if constexpr (NV > 0) return e[i];
         else return exp_shifted(scaled(i), m);
@@ -140,15 +100,15 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *
         s += v;
         nmax += v == 1.0f ? 1.f : 0.f;
     }
-    const float S = block_sum(s, red, 1);
-    nmax = block_sum(nmax, red, 0);
+    const float S = block_sum<SMP_WAVES>(s, red, 1);
+    nmax = block_sum<SMP_WAVES>(nmax, red, 0);
     const float bound = top_p * S;                               // nucleus: mass strictly above the token <= bound
     const float lse = m + __logf(S);
 
     if (nmax == 1.f && !(nmax <= bound)) {                       // the arg-max alone is the nucleus: whatever u is
 #pragma unroll
         for (int i = 0; i < nv; ++i)
-            if (val(i) == 1.0f) sample_emit(o, row, step, T, tid + i * SMP_THREADS, m - lse, stop_id, alt_stop_id);
+            if (val(i) == 1.0f) greedy_emit(o, row, step, tid + i * SMP_THREADS, m - lse);
         return;
     }
 
@@ -166,7 +126,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *
             const float v = val(i);
             a += __float_as_uint(v) > mid ? v : 0.f;
         }
-        a = block_sum(a, red, par);
+        a = block_sum<SMP_WAVES>(a, red, par);
         par ^= 1;
         if (a <= bound) hi = mid;
         else lo = mid + 1;
@@ -175,7 +135,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *
 
     // ---- the pick: the nucleus mass of every 64-token segment (ids 1024 i + 64 wave + lane: segment 16 i + wave, in id
     // order), a scan over the segments by wavefront 0, then a scan inside the segment the target falls into
-    const float uu = u_in ? u_in[(size_t)row * T + step] : sample_uniform(seed, (uint32_t)(cap_off + row), (uint32_t)step);
+    const float uu = u_in ? u_in[(size_t)row * o.T + step] : sample_uniform(seed, (uint32_t)(cap_off + row), (uint32_t)step);
     auto nucleus = [&](int i) { const float v = val(i); return __float_as_uint(v) >= tau ? v : 0.f; };
     if constexpr (NV > 0) {
 #pragma unroll
@@ -226,7 +186,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *
         const int pl = hit ? __ffsll((long long)hit) - 1 : 63 - __clzll((long long)any);
         if (lane == pl) {
             const int tok = gi * SMP_THREADS + tid;
-            sample_emit(o, row, step, T, tok, scaled_logit(x[tok], inv_temp) - lse, stop_id, alt_stop_id);
+            greedy_emit(o, row, step, tok, scaled_logit(x[tok], inv_temp) - lse);
         }
     } else {
         // any vocabulary: wavefront 0 walks the row in id order, 64 tokens at a time
@@ -251,27 +211,22 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_top_p_kernel(const float *
             run += __shfl(incl, WAVE - 1, WAVE);
         }
         if (tok < 0) tok = last;
-        if (lane == 0 && tok >= 0) sample_emit(o, row, step, T, tok, scaled_logit(x[tok], inv_temp) - lse, stop_id, alt_stop_id);
+        if (lane == 0 && tok >= 0) greedy_emit(o, row, step, tok, scaled_logit(x[tok], inv_temp) - lse);
     }
 }
 
 }  // namespace
 
-int launch_sample_top_p(hipStream_t st, const float *logits, int ld, int rows, int row0, int V, float inv_temp, float top_p,
-                        uint64_t seed, const float *u, int cap_off, int step, int T, int stop_id, int alt_stop_id, int *ids,
-                        int *lens, uint8_t *done, int *next_tok, int *alive_count, float *logp, const int *cmap) {
+int launch_sample_top_p(hipStream_t st, const GreedyState &s, const float *logits, int ld, int rows, int row0, int V,
+                        float inv_temp, float top_p, uint64_t seed, const float *u, int cap_off, int step) {
     if (rows <= 0) return 0;
-    const SampleOut o{ids, lens, done, next_tok, alive_count, logp};
     const dim3 grid(rows), block(SMP_THREADS);
-    if (V <= 2 * SMP_THREADS)
-        hipLaunchKernelGGL(sample_top_p_kernel<2>, grid, block, 0, st, logits, ld, V, row0, inv_temp, top_p, seed, u, cap_off, step, T,
-                           stop_id, alt_stop_id, o, cmap);
-    else if (V <= 50 * SMP_THREADS)
-        hipLaunchKernelGGL(sample_top_p_kernel<50>, grid, block, 0, st, logits, ld, V, row0, inv_temp, top_p, seed, u, cap_off, step,
-                           T, stop_id, alt_stop_id, o, cmap);
-    else
-        hipLaunchKernelGGL(sample_top_p_kernel<0>, grid, block, 0, st, logits, ld, V, row0, inv_temp, top_p, seed, u, cap_off, step, T,
-                           stop_id, alt_stop_id, o, cmap);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, logits, ld, V, row0, inv_temp, top_p, seed, u, cap_off, step, s);
+    };
+    if (V <= 2 * SMP_THREADS) launch(sample_top_p_kernel<2>);
+    else if (V <= 50 * SMP_THREADS) launch(sample_top_p_kernel<50>);
+    else launch(sample_top_p_kernel<0>);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

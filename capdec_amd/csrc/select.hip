@@ -1,7 +1,9 @@
 // Token selection: merge of the lm_head per-tile candidates, greedy step, and the beam-search
 // bookkeeping of reference gpt2_prefix_eval.py:78-108 (one wavefront per caption; all
 // per-caption state lives in a few hundred bytes, so these kernels are launch-latency sized).
-#include "common.h"
+// The tie rule, the lane lists, the winner-pops round and the tile logsumexp come from row_select.h; the three merge
+// kernels are entry points over merge_tile_lists.
+#include "row_select.h"
 
 namespace capdec {
 
@@ -10,9 +12,39 @@ constexpr int SEL_CTX_MAX = 1024;  // max context (prefix + generated): GPT-2's 
                                    // (the beam step stages beam x (T ints + ctx bytes) of state in dynamic LDS: <= 40 KB)
 constexpr int SEL_BEAM_MAX = 8;
 
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+// ---- merge: one wavefront per row; the row's KOUT best of its tiles' KIN-entry lists [ntiles, KIN] -> out_val / out_idx
+// [KOUT].  Returns, for the callers that flag rows, the row's KOUT-th winner and the best LAST-kept candidate among this
+// lane's tiles (what bounds their hidden ones).  Only the k = 3 kernel reads them; they are register arithmetic without
+// side effects, so where the result is ignored the compiler drops the tracking.
+struct MergeTail {
+    float kth_v; int kth_i;
+    float last_v; int last_i;
+};
+template <int KIN, int KOUT>
+__device__ __forceinline__ MergeTail merge_tile_lists(const float *__restrict__ cand_val, const int *__restrict__ cand_idx,
+                                                      int ntiles, int lane, float *__restrict__ out_val,
+                                                      int *__restrict__ out_idx) {
+    LaneTopk<KOUT> best;
+    best.clear();
+    MergeTail t{-INFINITY, 0x7fffffff, -INFINITY, 0x7fffffff};
+    for (int tile = lane; tile < ntiles; tile += 64) {
+#pragma unroll
+        for (int kk = 0; kk < KIN; ++kk) {
+            const float v = cand_val[(size_t)tile * KIN + kk];
+            const int i = cand_idx[(size_t)tile * KIN + kk];
+            if (kk == KIN - 1 && better(v, i, t.last_v, t.last_i)) { t.last_v = v; t.last_i = i; }
+            best.push(v, i);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < KOUT; ++r) {
+        best.pop_best(t.kth_v, t.kth_i);
+        if (lane == 0) { out_val[r] = t.kth_v; out_idx[r] = t.kth_i; }
+    }
+    return t;
+}
 
-// ---- merge: per row, logsumexp over tiles and the global top-k of the per-tile top-k lists.
+// per row, logsumexp over tiles and the global top-k of the per-tile top-k lists
 template <int KSEL>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict__ tile_max,
                                                          const float *__restrict__ tile_sum,
@@ -24,49 +56,10 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const size_t base = (size_t)row * ntiles;
-    float m = -INFINITY;
-    for (int t = lane; t < ntiles; t += 64) m = fmaxf(m, tile_max[base + t]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int t = lane; t < ntiles; t += 64) s += tile_sum[base + t] * expf(tile_max[base + t] - m);
-    s = wave_sum(s);
-    if (lane == 0) lse[row] = m + logf(s);
-
-    float bv[KSEL];
-    int bi[KSEL];
-#pragma unroll
-    for (int j = 0; j < KSEL; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
-    for (int t = lane; t < ntiles; t += 64) {
-#pragma unroll
-        for (int kk = 0; kk < KSEL; ++kk) {
-            float v = cand_val[(base + t) * KSEL + kk];
-            int i = cand_idx[(base + t) * KSEL + kk];
-#pragma unroll
-            for (int j = 0; j < KSEL; ++j) {
-                if (better(v, i, bv[j], bi[j])) {
-                    const float tv = bv[j]; const int ti = bi[j];
-                    bv[j] = v; bi[j] = i; v = tv; i = ti;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < KSEL; ++r) {
-        float gv = bv[0];
-        int gi = bi[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(gv, o, 64);
-            const int oi = __shfl_xor(gi, o, 64);
-            if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-        }
-        if (gi == bi[0] && gv == bv[0]) {   // this lane held the winner: pop it
-#pragma unroll
-            for (int j = 0; j + 1 < KSEL; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
-            bv[KSEL - 1] = -INFINITY; bi[KSEL - 1] = 0x7fffffff;
-        }
-        if (lane == 0) { top_val[(size_t)row * KSEL + r] = gv; top_idx[(size_t)row * KSEL + r] = gi; }
-    }
+    const float l = tile_logsumexp(tile_max + base, tile_sum + base, ntiles, lane);
+    if (lane == 0) lse[row] = l;
+    merge_tile_lists<KSEL, KSEL>(cand_val + base * KSEL, cand_idx + base * KSEL, ntiles, lane, top_val + (size_t)row * KSEL,
+                                 top_idx + (size_t)row * KSEL);
 }
 
 // ---- k = 3 per tile in, top 5 out, with the "may hide a fourth" flag (common.h)
@@ -81,57 +74,13 @@ __global__ __launch_bounds__(256) void topk_merge_k3_kernel(const float *__restr
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const size_t base = (size_t)row * ntiles;
-    float m = -INFINITY;
-    for (int t = lane; t < ntiles; t += 64) m = fmaxf(m, tile_max[base + t]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int t = lane; t < ntiles; t += 64) s += tile_sum[base + t] * expf(tile_max[base + t] - m);
-    s = wave_sum(s);
-    if (lane == 0) lse[row] = m + logf(s);
-
-    float bv[KOUT];
-    int bi[KOUT];
-#pragma unroll
-    for (int j = 0; j < KOUT; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
-    float l3v = -INFINITY;                 // the best LAST-kept candidate among this lane's tiles: what bounds their hidden ones
-    int l3i = 0x7fffffff;
-    for (int t = lane; t < ntiles; t += 64) {
-#pragma unroll
-        for (int kk = 0; kk < KIN; ++kk) {
-            float v = cand_val[(base + t) * KIN + kk];
-            int i = cand_idx[(base + t) * KIN + kk];
-            if (kk == KIN - 1 && better(v, i, l3v, l3i)) { l3v = v; l3i = i; }
-#pragma unroll
-            for (int j = 0; j < KOUT; ++j) {
-                if (better(v, i, bv[j], bi[j])) {
-                    const float tv = bv[j]; const int ti = bi[j];
-                    bv[j] = v; bi[j] = i; v = tv; i = ti;
-                }
-            }
-        }
-    }
-    float gv = -INFINITY;
-    int gi = 0x7fffffff;
-#pragma unroll
-    for (int r = 0; r < KOUT; ++r) {
-        gv = bv[0];
-        gi = bi[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(gv, o, 64);
-            const int oi = __shfl_xor(gi, o, 64);
-            if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-        }
-        if (gi == bi[0] && gv == bv[0]) {   // this lane held the winner: pop it
-#pragma unroll
-            for (int j = 0; j + 1 < KOUT; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
-            bv[KOUT - 1] = -INFINITY; bi[KOUT - 1] = 0x7fffffff;
-        }
-        if (lane == 0) { top_val[(size_t)row * KOUT + r] = gv; top_idx[(size_t)row * KOUT + r] = gi; }
-    }
-    // (gv, gi) = the row's fifth.  A tile's hidden candidates are all worse than its third kept one, so they can only
-    // matter if that third one is STRICTLY better than the fifth (if it IS the fifth, or worse, nothing hidden can pass it)
-    const bool mine = better(l3v, l3i, gv, gi);
+    const float l = tile_logsumexp(tile_max + base, tile_sum + base, ntiles, lane);
+    if (lane == 0) lse[row] = l;
+    const MergeTail t = merge_tile_lists<KIN, KOUT>(cand_val + base * KIN, cand_idx + base * KIN, ntiles, lane,
+                                                    top_val + (size_t)row * KOUT, top_idx + (size_t)row * KOUT);
+    // A tile's hidden candidates are all worse than its third kept one, so they can only matter if that third one is
+    // STRICTLY better than the row's fifth (if it IS the fifth, or worse, nothing hidden can pass it)
+    const bool mine = better(t.last_v, t.last_i, t.kth_v, t.kth_i);
     if (__ballot(mine) != 0ull && lane == 0) {
         flag_rows[atomicAdd(flag_count, 1)] = row;
         atomicAdd(flag_total, 1);
@@ -157,42 +106,9 @@ __global__ __launch_bounds__(256) void topk_merge_rows_kernel(const float *__res
     const int n = *count_dev;
     for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += gridDim.x * 4) {
         const size_t base = (size_t)row * ntiles;
-        float bv[KSEL];
-        int bi[KSEL];
-#pragma unroll
-        for (int j = 0; j < KSEL; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
-        for (int t = lane; t < ntiles; t += 64) {
-#pragma unroll
-            for (int kk = 0; kk < KSEL; ++kk) {
-                float v = cand_val[(base + t) * KSEL + kk];
-                int i = cand_idx[(base + t) * KSEL + kk];
-#pragma unroll
-                for (int j = 0; j < KSEL; ++j) {
-                    if (better(v, i, bv[j], bi[j])) {
-                        const float tv = bv[j]; const int ti = bi[j];
-                        bv[j] = v; bi[j] = i; v = tv; i = ti;
-                    }
-                }
-            }
-        }
         const size_t orow = (size_t)out_rows[row];
-#pragma unroll
-        for (int r = 0; r < KSEL; ++r) {
-            float gv = bv[0];
-            int gi = bi[0];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(gv, o, 64);
-                const int oi = __shfl_xor(gi, o, 64);
-                if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-            }
-            if (gi == bi[0] && gv == bv[0]) {
-#pragma unroll
-                for (int j = 0; j + 1 < KSEL; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
-                bv[KSEL - 1] = -INFINITY; bi[KSEL - 1] = 0x7fffffff;
-            }
-            if (lane == 0) { top_val[orow * KSEL + r] = gv; top_idx[orow * KSEL + r] = gi; }
-        }
+        merge_tile_lists<KSEL, KSEL>(cand_val + base * KSEL, cand_idx + base * KSEL, ntiles, lane, top_val + orow * KSEL,
+                                     top_idx + orow * KSEL);
     }
 }
 
@@ -220,43 +136,39 @@ int launch_topk_merge(hipStream_t st, const float *tile_max, const float *tile_s
 // ---- greedy: reference gpt2_prefix_eval.py:177-188 (argmax; stop on '.' or id 764)
 // (k candidates per row: k = 1 normally; teacher forcing -- forced != nullptr -- feeds forced[row, step] as the next
 //  token instead of the arg-max and, with k = 2, records (top-1 logit, top-2 logit, logsumexp) of every step)
-__global__ void greedy_step_kernel(const int *__restrict__ top_idx, int rows, int step, int T, int stop_id,
-                                   int alt_stop_id, int *__restrict__ ids, int *__restrict__ lens,
-                                   uint8_t *__restrict__ done, int *__restrict__ next_tok,
-                                   int *__restrict__ alive_count, const int *__restrict__ cmap, int k,
+__global__ void greedy_step_kernel(GreedyState s, const int *__restrict__ top_idx, int rows, int step, int k,
                                    const int *__restrict__ forced, const float *__restrict__ top_val,
                                    const float *__restrict__ lse, float *__restrict__ stats) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;       // activation row (compact)
     if (r >= rows) return;
-    const int row = cmap ? cmap[r] : r;                        // caption
+    const int row = s.cmap ? s.cmap[r] : r;                    // caption
     const int tok = top_idx[(size_t)r * k];
     if (stats) {
-        float *o = stats + ((size_t)row * T + step) * 3;
+        float *o = stats + ((size_t)row * s.T + step) * 3;
         o[0] = top_val[(size_t)r * k];
         o[1] = k > 1 ? top_val[(size_t)r * k + 1] : -INFINITY;
         o[2] = lse[r];
     }
     if (forced) {                                              // teacher forcing: nothing stops, every step is recorded
-        next_tok[row] = forced[(size_t)row * T + step];
-        ids[(size_t)row * T + step] = tok;
-        lens[row] = step + 1;
-        atomicAdd(alive_count, 1);
+        s.next_tok[row] = forced[(size_t)row * s.T + step];
+        s.ids[(size_t)row * s.T + step] = tok;
+        s.lens[row] = step + 1;
+        atomicAdd(s.alive_count, 1);
         return;
     }
-    next_tok[row] = tok;
-    if (done[row]) return;
-    ids[(size_t)row * T + step] = tok;
-    lens[row] = step + 1;
-    if (tok == stop_id || tok == alt_stop_id) done[row] = 1;
-    else atomicAdd(alive_count, 1);
+    // The next step embeds next_tok of EVERY row that is still in the batch, finished captions included (until the next
+    // compaction), so it is written before `done` is looked at.  greedy_emit stores the same value again: redundant here,
+    // needed by the sampling kernel, which leaves before any store when the caption is done.  Keep this order.
+    s.next_tok[row] = tok;
+    if (s.done[row]) return;
+    greedy_emit(s, row, step, tok, 0.f);
 }
 
-int launch_greedy_step(hipStream_t st, const int *top_idx, int rows, int step, int T, int stop_id, int alt_stop_id,
-                       int *ids, int *lens, uint8_t *done, int *next_tok, int *alive_count, const int *cmap, int k,
+int launch_greedy_step(hipStream_t st, const GreedyState &s, const int *top_idx, int rows, int step, int k,
                        const int *forced, const float *top_val, const float *lse, float *stats) {
     if (rows <= 0) return 0;
-    hipLaunchKernelGGL(greedy_step_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, top_idx, rows, step, T,
-                       stop_id, alt_stop_id, ids, lens, done, next_tok, alive_count, cmap, k, forced, top_val, lse, stats);
+    hipLaunchKernelGGL(greedy_step_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, s, top_idx, rows, step, k, forced,
+                       top_val, lse, stats);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

@@ -73,9 +73,10 @@ int capdec_synchronize(capdec_ctx *ctx);
  *     the fp32 reference (teacher-forced tolerance tests, capdec_decode_greedy_forced);
  * 4 = "f16": fp16 GEMM operands, fp32 everything else (KV cache included): the precision class of the reference's
  *     CLIP towers on a GPU (clip.load converts to fp16).
- * In the two 16-bit modes the CLIP towers' attention (sequences of 24 .. 128 positions: the 77-token text tower, the
- * 50-token ViT) also takes fp16 operands for its two products -- q, k, v and the un-normalised softmax weights, fp32
- * accumulate, fp32 softmax; GPT-2's attention keeps fp32 operands (bf16 mode: the bf16-rounded K / V of its cache).
+ * In the two 16-bit modes the CLIP towers' attention (every tower sequence up to 128 positions -- the 77-token text tower,
+ * the 50-token ViT: the prefill rule `tower || P >= 24` sends them to the fp16 matrix-core kernel) also takes fp16 operands
+ * for its two products -- q, k, v and the un-normalised softmax weights, fp32 accumulate, fp32 softmax; GPT-2's attention
+ * keeps fp32 operands (bf16 mode: the bf16-rounded K / V of its cache).
  * The mapper, patch-embedding and projection GEMMs are fp32-accurate in every mode.
  * The environment variable CAPDEC_GEMM_MODE=f16x2|bf16x3|f32|bf16|f16 overrides the default at capdec_create (any
  * other value makes capdec_create fail: a typo must not silently select another precision). */
@@ -481,7 +482,9 @@ int capdec_decode_stats(capdec_ctx *ctx, int *steps, int *compactions, long long
 int capdec_set_compact(capdec_ctx *ctx, int on);
 /* rows[i] = activation rows the (i + 1)-th decode step of the last decode call pushed through the GPT-2 body (step 0 is the
  * prefill); *n = how many steps there were (<= entry_length - 1).  At most `cap` entries are written.  With compaction the
- * sequence steps down at the poll points (every 8 steps) as captions finish; without it it is constant. */
+ * sequence steps down at the poll points as captions finish; without it it is constant.  The poll cadence is adaptive: every
+ * step from 8192 rows, every 2 from 2048, every 4 from 512, every 8 below; a poll that finds no newly finished caption
+ * doubles the interval (up to 8), the next one that does resets it. */
 int capdec_decode_step_rows(capdec_ctx *ctx, int *rows, int cap, int *n);
 /* *chunks = how many chunks the KV budget (capdec_set_kv_budget, clamped to the free device memory) split the captions of
  * the last decode call into; 0 for an empty call.  (Added with capdec_decode_sample, again without a new ABI number.) */
