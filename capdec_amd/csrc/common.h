@@ -349,6 +349,7 @@ struct BeamState {
     unsigned *kv_stat = nullptr;   // [ncap, 2] optional: per caption, sum over the decode steps of (distinct K/V slots the
                                    // next step's attention reads, positions it attends to) -- what the attention roofline depends on
     int diverge = 0;               // measurement only: every beam continues ITSELF (worst-case K/V traffic; results differ)
+    float *logp = nullptr;      // [ncap, beam]  diverse beam search only (diverse.hip): running sum of the UNPENALISED log-probs
 };
 int launch_beam_init(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
                      int ncap, int beam, int k, int T, int ctx, int P, int stop_id);
@@ -357,6 +358,15 @@ int launch_beam_step(hipStream_t st, const BeamState &s, const float *lse, const
                      const int *cmap = nullptr);
 int launch_beam_finalize(hipStream_t st, const BeamState &s, int ncap, int beam, int T, int *ids, int *lens,
                          float *scores, int *order);
+// diverse.hip: diverse (group) beam search -- the beam step run per group of beam / groups slots, with the tokens that the
+// earlier groups of the caption took at this step penalised by `diversity` each (the contract: include/capdec.h)
+int launch_group_beam_init(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
+                           int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int P, int stop_id);
+int launch_group_beam_step(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
+                           int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int step, int pos_new,
+                           int vocab, int stop_id, const int *cmap = nullptr);
+// logp_out[cap, rank] = s.logp[cap, order[cap, rank]]: the unpenalised sums in the order launch_beam_finalize returned
+int launch_group_beam_logp(hipStream_t st, const BeamState &s, int ncap, int beam, const int *order, float *logp_out);
 // The state the greedy family of decodes (arg-max, teacher-forced, sampling) keeps per caption, and the constants of the
 // call that its step kernels need
 struct GreedyState {

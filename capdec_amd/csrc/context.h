@@ -177,6 +177,7 @@ struct capdec_ctx {
     // workspaces
     DBuf h, x, qkv, att, ff, xl, tmax, tsum, cval, cidx, lse, topv, topi, kc, vc;
     DBuf tokens, scores, seq, stopped, done, anc, next_tok, alive, gids, glens, cmap, kvstat;
+    DBuf glogp;            // diverse beam search (capdec_decode_beam_groups): the unpenalised log-prob sums [rows] (BeamState::logp)
     capdec::TrainState *train = nullptr;     // created by the first capdec_train_step, freed by train_release
     int train_scope = 0;                     // capdec_train_set_scope: survives capdec_train_reset and weight reloads
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)

@@ -183,6 +183,10 @@ struct DecodeCall {
     uint64_t seed = 0;
     const float *u = nullptr;   // [n, T] or nullptr (Philox)
     float *logp = nullptr;      // [n, T] or nullptr
+    // diverse beam search (capdec_decode_beam_groups): groups > 0 sends the beam bookkeeping to diverse.hip's group kernels
+    int groups = 0;
+    float diversity = 0.f;
+    float *glogp = nullptr;     // [n, beam] or nullptr: the unpenalised log-prob sums, in the returned order
     int cap_off = 0;            // index of the chunk's first caption within the call: the Philox counter's caption offset, and
                                 // the offset of the chunk's slice of the per-call K/V-slot statistic (BeamState::kv_stat)
 };
@@ -323,6 +327,10 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
         bs.next_tok = c->next_tok.as<int>();
         bs.alive_count = c->alive.as<int>();
         bs.diverge = c->diverge;
+        if (a.groups > 0) {
+            CAPDEC_TRY(c->glogp.ensure((size_t)rows * 4));
+            bs.logp = c->glogp.as<float>();
+        }
         // (distinct-K/V-slot statistic: this chunk's slice of the per-call array decode_common zeroed; nothing is read back
         //  here -- capdec_decode_counters sums it when somebody asks)
         bs.kv_stat = c->kvstat.p ? c->kvstat.as<unsigned>() + (size_t)a.cap_off * 2 : nullptr;
@@ -357,6 +365,13 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
         const float *lse = c->lse.as<float>(), *topv = c->topv.as<float>();
         const int *topi = c->topi.as<int>();
         if (greedy) return launch_greedy_step(c->stream, gs, topi, R, step, k, a.forced, topv, lse, a.stats);
+        if (a.groups > 0) {
+            if (step == 0)
+                return launch_group_beam_init(c->stream, bs, lse, topv, topi, R, beam, a.groups, a.diversity, k, T, ctx, P,
+                                              a.stop_id);
+            return launch_group_beam_step(c->stream, bs, lse, topv, topi, R / beam, beam, a.groups, a.diversity, k, T, ctx, step,
+                                          P + step - 1, g.vocab, a.stop_id, cmap);
+        }
         if (step == 0) return launch_beam_init(c->stream, bs, lse, topv, topi, R, beam, k, T, ctx, P, a.stop_id);
         return launch_beam_step(c->stream, bs, lse, topv, topi, R / beam, beam, k, T, ctx, step, P + step - 1, g.vocab,
                                 a.stop_id, cmap);
@@ -430,6 +445,7 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
     if (!greedy) {
         ProfScope ps(c, F_SELECT);
         CAPDEC_TRY(launch_beam_finalize(c->stream, bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
+        if (a.glogp) CAPDEC_TRY(launch_group_beam_logp(c->stream, bs, nc, beam, a.order, a.glogp));
     }
     return 0;
 }
@@ -480,6 +496,7 @@ static int decode_common(capdec_ctx *c, const float *prefix, int n, const Decode
         if (a.stats) a.stats += (size_t)c0 * T * 3;
         if (a.u) a.u += (size_t)c0 * T;
         if (a.logp) a.logp += (size_t)c0 * T;
+        if (a.glogp) a.glogp += (size_t)c0 * beam;
         a.cap_off = c0;
         CAPDEC_TRY(decode_chunk(c, prefix + (size_t)c0 * P * c->gpt.d, nc, a));
     }
@@ -580,6 +597,31 @@ int capdec_decode_beam(capdec_ctx *c, const float *prefix, int n, int P, int bea
     a.P = P; a.beam = beam; a.greedy = false; a.stop_id = stop_id; a.T = entry_length; a.temperature = temperature;
     a.ids = ids; a.lens = lens; a.scores = scores; a.order = order;
     return decode_common(c, prefix, n, a);
+}
+
+int capdec_decode_beam_groups(capdec_ctx *c, const float *prefix, int n, int P, int beam, int groups, float diversity_penalty,
+                              int stop_id, int entry_length, float temperature, int32_t *ids, int32_t *lens, float *scores,
+                              int32_t *order, float *logp) {
+    CAPDEC_CHECK(c && (n == 0 || (prefix && ids && lens && scores)), "decode_beam_groups: null argument");
+    CAPDEC_CHECK(beam >= 1 && beam <= 8, "decode_beam_groups: beam size must be in 1..8");
+    CAPDEC_CHECK(groups >= 1, "decode_beam_groups: groups must be >= 1");
+    CAPDEC_CHECK(groups <= beam, "decode_beam_groups: more groups than beams");
+    CAPDEC_CHECK(beam % groups == 0, "decode_beam_groups: groups must divide the beam size");
+    CAPDEC_CHECK(diversity_penalty >= 0.f && diversity_penalty <= 3.0e38f,
+                 "decode_beam_groups: the diversity penalty must be finite and >= 0");
+    CAPDEC_CHECK(c->gpt.loaded && c->gpt.vocab >= beam, "decode_beam_groups: vocabulary smaller than the beam");
+    DBuf own_order;             // the log-prob sums are gathered through the order: keep one when the caller wants none
+    if (logp && !order && n > 0) {
+        CAPDEC_TRY(own_order.ensure((size_t)n * beam * 4));
+        order = own_order.as<int32_t>();
+    }
+    DecodeCall a;
+    a.P = P; a.beam = beam; a.greedy = false; a.stop_id = stop_id; a.T = entry_length; a.temperature = temperature;
+    a.ids = ids; a.lens = lens; a.scores = scores; a.order = order;
+    a.groups = groups; a.diversity = diversity_penalty; a.glogp = logp;
+    const int rc = decode_common(c, prefix, n, a);
+    own_order.release();
+    return rc;
 }
 
 

@@ -554,6 +554,47 @@ class Engine:
                                           order.data_ptr()), "capdec_decode_beam")
         return ids, lens, scores, order
 
+    def decode_beam_groups(self, prefix_embed: torch.Tensor, stop_id: int, beam_size: int = 6, num_beam_groups: int = 3,
+                           diversity_penalty: float = 0.5, entry_length: int = 67, temperature: float = 1.0, *,
+                           repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                           min_length: Optional[int] = None, logit_bias=None):
+        """diverse (group) beam search (capdec_decode_beam_groups): the beam decode with its ``beam_size`` slots split into
+        ``num_beam_groups`` groups that are advanced in order, a token that earlier groups took at the same step costing
+        ``diversity_penalty`` per taker.  -> ids [n, beam, T], lens [n, beam], scores [n, beam] (the penalised mean
+        log-probs, sorted descending over all slots), order [n, beam] (the slot of each returned row: its group is
+        ``order // (beam_size // num_beam_groups)``) and logp [n, beam] (the unpenalised log-prob sums, same order).  One
+        group is :meth:`decode_beam`.  The keyword-only processors as in :meth:`decode_greedy`."""
+        for name, v in (("beam_size", beam_size), ("num_beam_groups", num_beam_groups)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise CapdecError(f"decode_beam_groups: {name} must be an integer, got {v!r}")
+        if not 1 <= beam_size <= 8:
+            raise CapdecError("decode_beam_groups: beam_size must be in 1..8")
+        if num_beam_groups < 1 or num_beam_groups > beam_size or beam_size % num_beam_groups:
+            raise CapdecError(f"decode_beam_groups: num_beam_groups must be >= 1 and divide beam_size, got {num_beam_groups} "
+                              f"groups for {beam_size} beams")
+        t = diversity_penalty
+        if isinstance(t, bool) or not isinstance(t, (int, float, np.floating)) or not (t >= 0 and math.isfinite(t)):
+            raise CapdecError(f"decode_beam_groups: diversity_penalty must be a finite number >= 0, got {t!r}")
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias):
+            return self._decode_beam_groups(prefix_embed, stop_id, beam_size, num_beam_groups, float(diversity_penalty),
+                                            entry_length, temperature)
+
+    def _decode_beam_groups(self, prefix_embed, stop_id, beam_size, groups, penalty, entry_length, temperature):
+        p = self._dev(prefix_embed)
+        n, P, _ = p.shape
+        ids = torch.empty(n, beam_size, entry_length, device=self.device, dtype=torch.int32)
+        lens = torch.empty(n, beam_size, device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, beam_size, device=self.device, dtype=torch.float32)
+        order = torch.empty(n, beam_size, device=self.device, dtype=torch.int32)
+        logp = torch.empty(n, beam_size, device=self.device, dtype=torch.float32)
+        self._sync_stream()
+        self._chk(self.lib.capdec_decode_beam_groups(self._h, p.data_ptr(), n, P, int(beam_size), int(groups), float(penalty),
+                                                     int(stop_id), int(entry_length), float(temperature), ids.data_ptr(),
+                                                     lens.data_ptr(), scores.data_ptr(), order.data_ptr(), logp.data_ptr()),
+                  "capdec_decode_beam_groups")
+        return ids, lens, scores, order, logp
+
     # ------------------------------------------------------------------ scoring
     def score(self, prefix_embed: torch.Tensor, tokens: torch.Tensor, lens=None, ignore_id: int = -1,
               temperature: float = 1.0, return_top1: bool = False):

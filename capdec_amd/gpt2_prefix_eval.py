@@ -2,7 +2,9 @@
 ``generate2`` (:118-198) with the reference signatures, plus batched variants
 (``embed`` [N, P, 768]) that the throughput path uses.  The per-token Python loop, the
 no-cache re-forward and the per-token host syncs of the reference are replaced by one call
-into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``).  ``generate_samples`` /
+into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``).  ``generate_diverse_beam`` /
+``generate_diverse_beam_batch`` are ``generate_beam`` with diverse (group) beam search (``capdec_decode_beam_groups``:
+``num_beam_groups`` / ``diversity_penalty``), for callers who want beams that differ.  ``generate_samples`` /
 ``generate_samples_batch`` make ``top_p``, ``temperature`` and ``entry_count`` live: nucleus sampling
 (``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178).
 
@@ -80,6 +82,18 @@ def decode_beam_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_ind
     beams sorted by mean log-prob descending (the order generate_beam returns)."""
     kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     return model.engine.decode_beam(embed, stop_token_index, beam_size, entry_length, temperature, **kw)
+
+
+def decode_diverse_beam_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, beam_size: int = 6,
+                            num_beam_groups: int = 3, diversity_penalty: float = 0.5, entry_length: int = 67,
+                            temperature: float = 1.0, *, repetition_penalty: Optional[float] = None,
+                            no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None, logit_bias=None):
+    """embed [N, P, d] -> (ids [N, beam, T], lens [N, beam], scores [N, beam], order [N, beam], logp [N, beam]) of the
+    diverse (group) beam search (``capdec_decode_beam_groups``): rows sorted by their penalised mean log-prob descending;
+    ``order // (beam_size // num_beam_groups)`` is a row's group, ``logp`` its unpenalised log-prob sum."""
+    kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    return model.engine.decode_beam_groups(embed, stop_token_index, beam_size, num_beam_groups, diversity_penalty, entry_length,
+                                           temperature, **kw)
 
 
 def sample_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, entry_length: int = 67,
@@ -169,6 +183,28 @@ def generate_beam_batch(model, tokenizer, embed: torch.Tensor, beam_size: int = 
     return [[tokenizer.decode(ids[r, b, :int(lens[r, b])]) for b in range(ids.shape[1])] for r in range(ids.shape[0])]
 
 
+def generate_diverse_beam_batch(model, tokenizer, embed: torch.Tensor, beam_size: int = 6, num_beam_groups: int = 3,
+                                diversity_penalty: float = 0.5, entry_length: int = 67, temperature: float = 1.,
+                                stop_token: str = '.', per_group: bool = False, *, repetition_penalty: Optional[float] = None,
+                                no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None,
+                                logit_bias=None) -> List[List[str]]:
+    """embed [N, P, d] -> per caption the ``beam_size`` texts of the diverse beam search, best first; with ``per_group`` the
+    best text of each group, in group order (``num_beam_groups`` texts)"""
+    stop = tokenizer.encode(stop_token)[0]
+    ids, lens, _, order, _ = decode_diverse_beam_ids(model, embed, stop, beam_size, num_beam_groups, diversity_penalty, entry_length,
+                                                     temperature, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                                     min_length=min_length, logit_bias=logit_bias)
+    ids, lens, order = ids.cpu().numpy(), lens.cpu().numpy(), order.cpu().numpy()
+    out = []
+    for r in range(ids.shape[0]):
+        rows = list(range(ids.shape[1]))
+        if per_group:       # rows are sorted best first: the first row of every group is its best
+            group = order[r] // (beam_size // num_beam_groups)
+            rows = [int(np.nonzero(group == g)[0][0]) for g in range(num_beam_groups)]
+        out.append([tokenizer.decode(ids[r, b, :int(lens[r, b])]) for b in rows])
+    return out
+
+
 # --------------------------------------------------------------------------- reference signatures
 def generate_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 5, prompt=None, embed=None,
                   entry_length=67, temperature=1., stop_token: str = '.'):
@@ -186,6 +222,33 @@ def generate_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 5, prompt
         toks = ids[b, :int(lens[b])]
         if prompt_ids is not None:   # reference :86-87: prompt tokens stay in the output
             # seq_lengths counts generated tokens only (+ the reference slices the concatenated row)
+            toks = np.concatenate([np.asarray(prompt_ids, dtype=toks.dtype), ids[b]])[:int(lens[b])]
+        out.append(tokenizer.decode(toks))
+    return out
+
+
+def generate_diverse_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 6, num_beam_groups: int = 3,
+                          diversity_penalty: float = 0.5, prompt=None, embed=None, entry_length=67, temperature=1.,
+                          stop_token: str = '.', per_group: bool = False):
+    """``generate_beam`` with diverse (group) beam search: one caption ([1, P, d], or a prompt) -> ``beam_size`` texts, best
+    first (``per_group``: the best text of each group, in group order).  Prompt tokens stay in front as in
+    ``generate_beam``.  (Logits processors: ``model.logits_processors``.)"""
+    model.eval()
+    prefix, prompt_ids = _prefix_from(model, tokenizer, None, prompt, embed)
+    if prefix.shape[0] != 1:
+        raise CapdecError("generate_diverse_beam takes one caption ([1, P, d]); use generate_diverse_beam_batch for [N, P, d]")
+    stop = tokenizer.encode(stop_token)[0]
+    ids, lens, _, order, _ = decode_diverse_beam_ids(model, prefix, stop, beam_size, num_beam_groups, diversity_penalty,
+                                                     entry_length, temperature)
+    ids, lens, order = ids.cpu().numpy()[0], lens.cpu().numpy()[0], order.cpu().numpy()[0]
+    rows = list(range(beam_size))
+    if per_group:
+        group = order // (beam_size // num_beam_groups)
+        rows = [int(np.nonzero(group == g)[0][0]) for g in range(num_beam_groups)]
+    out = []
+    for b in rows:
+        toks = ids[b, :int(lens[b])]
+        if prompt_ids is not None:   # as generate_beam: the prompt tokens stay in the output, the row is cut at seq_lengths
             toks = np.concatenate([np.asarray(prompt_ids, dtype=toks.dtype), ids[b]])[:int(lens[b])]
         out.append(tokenizer.decode(toks))
     return out

@@ -356,6 +356,37 @@ int capdec_decode_greedy_forced(capdec_ctx *ctx, const float *d_prefix, int n, i
 int capdec_decode_beam(capdec_ctx *ctx, const float *d_prefix, int n, int P, int beam, int stop_id,
                        int entry_length, float temperature, int32_t *d_ids, int32_t *d_lens,
                        float *d_scores, int32_t *d_order);
+/* Diverse (group) beam search (Vijayakumar et al. 2016; `num_beam_groups` / `diversity_penalty` of older transformers)
+ * on the beam decode: beam B in 1..8, G groups (1 <= G <= B, B % G == 0, Bg = B / G), diversity_penalty lambda >= 0
+ * (finite).  Beam slots g*Bg .. (g+1)*Bg-1 of a caption form group g.  Each group runs capdec_decode_beam's step over its
+ * own Bg rows only: its own Bg x vocab candidates, its own top Bg, sources from its own slots.  Within a step the groups of
+ * a caption are processed in order 0..G-1:
+ *   lp      = the log-softmax of the processed, temperature-scaled logits, exactly as in capdec_decode_beam;
+ *   lp_pen  = lp - lambda * (float)cnt[j] for token j of a row of group g that is not stopped, where cnt[j] is the number of
+ *             hypotheses that groups < g of the same caption selected AT THIS STEP with token j, counting only selections
+ *             whose source beam was not stopped; a stopped row keeps its single candidate (token 0, log-prob 0), which is
+ *             neither penalised nor counted;
+ *   key     = (scores[row] + lp_pen) / seq_new[row], fp32 in that operation order; the group's Bg winners by the tie rule
+ *             of capdec_decode_beam (larger key, then smaller flat index = caption-level slot * vocab + token);
+ *   scores[slot] = key * seq_new[src]: the scores accumulate the PENALISED values, as the classic algorithm does;
+ *   logp[slot]   = logp[src] + (stopped[src] ? 0 : lp): a second accumulator with the UNPENALISED sum.
+ * Step 0 has one logits row per caption: group g takes the best Bg tokens of lp - lambda * cnt, cnt holding what groups
+ * < g took at this step (with lambda = 0 all groups start identical).  tokens, seq, stopped, logp and the ancestor table
+ * follow the winners' permutation (sources are caption-level slots); a caption is done when every slot of every group is
+ * stopped; the end is capdec_decode_beam's: d_scores = scores / seq sorted descending over all B slots, d_order [n, beam]
+ * (may be NULL) the slot of each returned row, so a row's group is d_order / Bg; d_logp [n, beam] (may be NULL) the
+ * unpenalised sums in the returned order.  groups == 1 is capdec_decode_beam bit for bit, whatever the penalty.  The
+ * selection stays exact with `beam` candidates per row (the logits are still not materialised when no processor is set):
+ * at most B - Bg tokens are penalised for a group, so a row's unpenalised top-B list holds at least Bg unpenalised
+ * tokens, each >= every token outside the list.  Logits processors compose unchanged (they act before the selection; a
+ * row's history is its slot's tokens).  capdec_set_debug_diverge is not honoured here.  Errors (capdec_last_error):
+ * groups < 1, groups > beam, beam % groups != 0, a negative, infinite or NaN penalty. */
+int capdec_decode_beam_groups(capdec_ctx *ctx, const float *d_prefix, int n, int P,
+                              int beam, int groups, float diversity_penalty,
+                              int stop_id, int entry_length, float temperature,
+                              int32_t *d_ids, int32_t *d_lens, float *d_scores,
+                              int32_t *d_order,
+                              float *d_logp /* [n, beam] or NULL */);
 /* Nucleus-sampling decode: the greedy loop with the arg-max replaced by one draw per step.  For a row of logits l, with
  * s = l / (temperature > 0 ? temperature : 1) and p = softmax(s): token j is in the nucleus iff it is the arg-max or the
  * sum of p[i] over all p[i] > p[j] is <= top_p (the filter of reference gpt2_prefix_eval.py:166-175; exactly equal
