@@ -1,0 +1,584 @@
+"""The decode-attention kernel (``attn_decode_beams_kernel``, capdec_amd/csrc/attention.hip) in every form that the
+public entry points reach with a handful of captions, against the float64 teacher-forced definition of
+tests/decode_attn_def.py and the KV-cached oracle -- at every value of the prefix peel, across the 64-position ballot
+rounds, at GPT-2's last position, and where the launch needs more than 64 KB of LDS.
+
+CASES is a table: one row per case with the kernel form ``<BEAM, KV, OCC, NA, CUR, DMA>`` the row CLAIMS to launch,
+restated by hand from ``stack_body`` (decode.hip), ``gemm_splitk_slices`` and ``attn_decode_typed`` (attention.hip).
+``test_cases_launch_the_forms_they_claim`` runs this file as a script in a child process under ``rocprofv3
+--kernel-trace`` and checks each claim against the launches it observed, so a condition that moves in one of those three
+places turns a row red instead of silently re-routing it.
+
+Levers (at most 8 captions, so (caption, head) wavefronts <= 16384 and the qkv GEMM of a decode step is split-K):
+
+    default          <B, float, ., 4, false, false> for B <= 5, NA = 2 for B = 6..8
+    bi               set_batch_invariant(True): NA = 2; B in {1, 5} take the LDS-DMA form <B, float, ., 2, true, true>
+    bi_nodirect      ... in a context created under CAPDEC_KV_DIRECT=0: <B, float, ., 2, false, false> for B in {1, 5}
+    bf16 / bf16_bi / bf16_bi_nodirect   the same three on the bf16 cache (set_gemm_mode("bf16")); CUR without DMA
+
+OCC is 4 up to beam 5 and 2 above.  Of the 32 forms attention.hip instantiates these levers reach 30.  The other two are
+``<5, __bf16, 4, 4, true, false>`` (more than 1792 rows: test_bf16_kv_through_the_qkv_epilogue_matches_the_attention_append
+runs it) and ``<1, __bf16, 4, 4, true, false>``, which no launch reaches at 12 heads (unsplit qkv needs more than 1792
+greedy rows, NA = 4 at most 1365).
+
+Bounds (the project's existing ones).  fp32 cache: per-step (top-1, top-2, logsumexp) within 1e-4 of the fp64 definition,
+arg-max equal where the fp64 top-1 / top-2 gap exceeds 2e-4; beams by the rule of ``_beam_rows_vs_oracle`` (a caption whose
+oracle margin exceeds 1e-4 matches exactly, scores 1e-4; another one is finite and sorted), and EVERY returned beam's score
+within 1e-4 of the fp64 teacher-forced mean log-prob of its own tokens.  bf16 cache: the noise-derived tolerance of
+test_bf16_mode_logits_and_decode_vs_bf16_oracle, max(4 x oracle noise, 0.5 x class gap); free-running beams by that test's
+bar (best score within 0.05, finite, full length).  The CPU tests show, on the references alone, that a single hidden key
+moves the compared statistics by at least 3 x each tolerance and that at most one caption of a beam case is a near-tie.
+"""
+import collections
+import functools
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import numpy as np
+import pytest
+import torch
+
+import decode_attn_def as DD
+from capdec_amd import synth
+
+gpu = pytest.mark.gpu
+STAT_TOL = 1e-4               # per-step statistics and beam scores, fp32 cache (test_teacher_forced_decode_fp32_modes)
+ID_GAP = 2e-4                 # arg-max compared where the fp64 top-1 / top-2 gap exceeds this
+KEY_GAP = 1e-4                # a beam caption is clear when its oracle margin exceeds this (_beam_rows_vs_oracle)
+UNCLEAR_CAP = 1               # captions of a beam case that may be unclear
+BF16_BEST = 0.05              # free-running bf16 beam: best mean log-prob against the bf16 oracle
+STOP = 10 ** 6                # no token stops a caption: every beam runs its T steps
+KNOBS = ("CAPDEC_GEMM_MODE", "CAPDEC_KV_DIRECT", "CAPDEC_BATCH_INVARIANT")
+
+# ------------------------------------------------------------------------------------------------ the table
+Case = collections.namedtuple("Case", "id kind lever B P T n seed form")
+
+
+def form_of(lever, B):
+    """the one kernel form <BEAM, KV, OCC, NA, CUR, DMA> a lever launches at beam width B (at most 8 captions)"""
+    kv = "bf16" if lever.startswith("bf16") else "float"
+    occ = 4 if B <= 5 else 2
+    if lever in ("default", "bf16"):
+        return (B, kv, occ, 4 if B <= 5 else 2, 0, 0)
+    direct = not lever.endswith("nodirect") and B in (1, 5)          # K / V through the qkv epilogue: CUR
+    return (B, kv, occ, 2, int(direct), int(direct and kv == "float"))
+
+
+CASES = []
+
+
+def case(kind, lever, B, P, T, n, seed):
+    CASES.append(Case(f"{kind}-{lever}-b{B}-p{P}", kind, lever, B, P, T, n, seed, form_of(lever, B)))
+
+
+# seeds: chosen on the CPU so that the oracle alone meets the near-tie cap (test_beam_cases_keep_something_to_compare)
+SHORT_P = (1, 3, 5, 8, 13, 17)
+SEED = 2
+BEAM_SEEDS = {}               # (P, B) -> seed where SEED leaves more than UNCLEAR_CAP captions unclear
+LONG_SEEDS = {}
+
+# (a) greedy, teacher-forced, fp32 cache: every peel value of NA 2 and 4, the ballot rounds at 64 / 128 / 256, context 1024
+for _P, _T in [(p, 8) for p in (1, 3, 5, 8, 13, 17, 60, 125, 250)] + [(1000, 25)]:
+    for _lever in ("default", "bi", "bi_nodirect"):
+        case("forced", _lever, 1, _P, _T, 4, SEED)
+# (b) plain beam, short contexts
+for _P in SHORT_P:
+    for _B in range(1, 9):
+        for _lever in ("default", "bi") + (("bi_nodirect",) if _B == 5 else ()):      # (beam 5 also without the DMA form)
+            case("beam", _lever, _B, _P, 8, 6, BEAM_SEEDS.get((_P, _B), SEED))
+# (c) beam past 64 KB of LDS
+LONG = [(5, "bi", 400, 16), (5, "bi", 605, 16), (5, "bi", 800, 16), (5, "bi", 1000, 25), (5, "default", 812, 16),
+        (8, "default", 505, 16), (8, "default", 1000, 25)]
+for _B, _lever, _P, _T in LONG:
+    case("beam", _lever, _B, _P, _T, 4, LONG_SEEDS.get((_P, _B), SEED))
+# (d) bf16 cache
+for _P in (1, 5, 8, 17, 60):
+    for _lever in ("bf16", "bf16_bi"):
+        case("bf16_forced", _lever, 1, _P, 8, 4, SEED)
+case("bf16_forced", "bf16_bi_nodirect", 1, 8, 8, 4, SEED)
+case("bf16_beam", "bf16_bi", 5, 812, 16, 4, 3)          # (seed 2: the bf16 oracle's own best score moves by 0.26 under a 1e-7 perturbation)
+for _B in range(2, 9):        # the other widths of the bf16 cache: short, free-running
+    for _lever in ("bf16", "bf16_bi"):
+        case("bf16_beam", _lever, _B, 5, 8, 4, SEED)
+case("bf16_beam", "bf16_bi_nodirect", 5, 5, 8, 4, SEED)
+assert len({c.id for c in CASES}) == len(CASES)
+BY_KIND = {k: [c for c in CASES if c.kind == k] for k in ("forced", "beam", "bf16_forced", "bf16_beam")}
+IDS = lambda cs: [c.id for c in cs]
+
+# every form attention.hip instantiates and these levers can reach (module docstring)
+LIVE = sorted({form_of(lv, B) for B in range(1, 9) for lv in ("default", "bi", "bf16", "bf16_bi")} |
+              {form_of(lv, B) for B in (1, 5) for lv in ("bi_nodirect", "bf16_bi_nodirect")})
+assert len(LIVE) == 30 and {c.form for c in CASES} == set(LIVE)
+
+
+def slot_table_bytes(B, L):
+    """launch_attn_decode: 4 wavefronts x B beams x L positions of int, rounded up to 1 KB (the DMA ring follows it)"""
+    return (16 * B * L + 1023) & ~1023
+
+
+RING = 4 * 2 * (2 * 2 * 1024)                              # four wavefronts x double buffer x (2 K + 2 V pieces of 1 KB)
+
+
+# ------------------------------------------------------------------------------------------------ shared references
+@functools.lru_cache(maxsize=None)
+def _model():
+    dims = synth.GPT2Dims(n_layer=2, vocab=1531, n_pos=1024)
+    return dims, synth.hot_state_dict(5, "mlp", 512, 10, dims=dims)
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(P, T, n, seed):
+    """-> prefixes [n, P, 768], random forced tokens int32 [n, T]"""
+    g = torch.Generator().manual_seed(seed)
+    pe = torch.randn(n, P, 768, generator=g) * 0.5
+    return pe, torch.randint(0, _model()[0].vocab, (n, T), generator=g).to(torch.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _prefilled(P, n, seed):
+    dims, sd = _model()
+    return DD.Prefilled(sd, _inputs(P, 1, n, seed)[0], dims.n_head)
+
+
+@functools.lru_cache(maxsize=None)
+def _forced_def(P, T, n, seed, hide=None):
+    """fp64 definition on the random forced tokens -> (arg-max ids, stats [n, T, 3])"""
+    return DD.stats(DD.forced_logits(_prefilled(P, n, seed), _inputs(P, T, n, seed)[1], hide))
+
+
+@functools.lru_cache(maxsize=None)
+def _beam_oracle(B, P, T, n, seed):
+    """O.beam_cached -> tokens, lengths, scores in the returned order, and the per-caption margin"""
+    from oracle import capdec_oracle as O
+    dims, sd = _model()
+    mg = []
+    tok, seq, sc = O.beam_cached(sd, _inputs(P, 1, n, seed)[0], B, STOP, T, n_head=dims.n_head, margins=mg)
+    od = O.beam_output_order(sc)
+    take = lambda t: torch.stack([t[r][od[r]] for r in range(n)]).numpy()
+    return take(tok), take(seq), take(sc), od.numpy(), mg[0].numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _bf16_forced_ref(P, T, n, seed):
+    """test_bf16_mode_logits_and_decode_vs_bf16_oracle's reference: forced tokens = the fp32 oracle's greedy ids; the oracle
+    on bf16-rounded GEMM operands; its noise under 1e-7-relative input perturbations; the bf16-vs-fp32 class gap"""
+    from oracle import capdec_oracle as O
+    dims, sd = _model()
+    pe = _inputs(P, T, n, seed)[0]
+    forced, _ = O.greedy_cached(sd, pe, STOP, T, alt_stop_id=-1, n_head=dims.n_head)
+    with O.bf16_gemm_operands():
+        want_ids, want_st = O.greedy_forced(sd, pe, forced, n_head=dims.n_head)
+        noise = max(float((O.greedy_forced(sd, pe * (1 + eps), forced, n_head=dims.n_head)[1] - want_st).abs().max())
+                    for eps in (1e-7, -3e-7, 1e-6))
+    _, f32_st = O.greedy_forced(sd, pe, forced, n_head=dims.n_head)
+    cls_gap = float((f32_st - want_st).abs().max())
+    return dict(forced=forced, ids=want_ids, st=want_st, f32_st=f32_st, noise=noise, cls_gap=cls_gap,
+                tol=max(4 * noise, 0.5 * cls_gap))
+
+
+@functools.lru_cache(maxsize=None)
+def _bf16_beam_best(B, P, T, n, seed, eps=0.0):
+    """the bf16 oracle's best mean log-prob per caption (eps: relative perturbation of the prefixes)"""
+    from oracle import capdec_oracle as O
+    dims, sd = _model()
+    with O.bf16_gemm_operands():
+        _, _, sc = O.beam_cached(sd, _inputs(P, 1, n, seed)[0] * (1 + eps), B, STOP, T, n_head=dims.n_head)
+    return sc.max(dim=1).values.numpy()
+
+
+def _report(line):
+    """the parity tests' record line: printed and appended to their counts file (tests/test_hip_parity.py::_report)"""
+    import test_hip_parity
+    test_hip_parity._report(line)
+
+
+# ================================================================================================ CPU: the references
+@pytest.mark.parametrize("P,T", [(3, 8), (800, 30)])
+def test_definition_in_fp32_is_the_oracle(P, T):
+    """the full-sequence restatement run in fp32 equals O.greedy_forced (KV-cached, step by step) to fp32 round-off:
+    ids where the gap is clear, statistics within 1e-4; and the oracle sits within 1e-4 of the fp64 run"""
+    from oracle import capdec_oracle as O
+    dims, sd = _model()
+    pe, forced = _inputs(P, T, 4, SEED)
+    ids_o, st_o = O.greedy_forced(sd, pe, forced, n_head=dims.n_head)
+    ids32, st32 = DD.stats(DD.forced_logits(DD.Prefilled(sd, pe, dims.n_head, torch.float32), forced))
+    ids64, st64 = _forced_def(P, T, 4, SEED)
+    d32, d64 = float((st32 - st_o).abs().max()), float((st_o.double() - st64).abs().max())
+    print(f"[definition] P {P} T {T}: fp32 restatement vs oracle {d32:.2e}, oracle vs fp64 {d64:.2e}")
+    assert st32.dtype == torch.float32 and st64.dtype == torch.float64
+    assert d32 < 5e-5 and d64 < 5e-5                          # fp32 round-off of logits of magnitude ~10 (observed 1e-5, 2e-5)
+    clear = (st64[..., 0] - st64[..., 1]) > ID_GAP
+    assert bool((ids32[clear] == ids_o.long()[clear]).all()) and bool((ids64[clear] == ids_o.long()[clear]).all())
+
+
+def test_planted_fault_hides_exactly_one_key():
+    """the fault leaves step 0 (the prefill row) alone and changes every decode step of every caption"""
+    ids, st = _forced_def(5, 8, 4, SEED)
+    for hide in DD.HIDE:
+        _, s = _forced_def(5, 8, 4, SEED, hide)
+        assert float((s[:, 0] - st[:, 0]).abs().max()) == 0.0
+        assert bool(((s[:, 1:] - st[:, 1:]).abs().amax(dim=2) > 0).all()), hide
+
+
+FORCED_DATA = sorted({(c.P, c.T, c.n, c.seed) for c in BY_KIND["forced"]})
+BF16_DATA = sorted({(c.P, c.T, c.n, c.seed) for c in BY_KIND["bf16_forced"]})
+
+
+@pytest.mark.parametrize("P,T,n,seed", FORCED_DATA, ids=[f"p{d[0]}" for d in FORCED_DATA])
+def test_one_hidden_key_moves_the_fp32_statistics(P, T, n, seed):
+    """conditioning of the teacher-forced fp32 cases: each planted fault moves the compared statistics by at least
+    3 x 1e-4 at some step -- not only in the maximum over the captions but for EVERY caption (random forced tokens;
+    per-caption largest shift 1.2 .. 4.7 at P = 3, 0.07 .. 0.95 at P = 1000 and everything between)"""
+    _, st = _forced_def(P, T, n, seed)
+    for hide in DD.HIDE:
+        shift = (_forced_def(P, T, n, seed, hide)[1] - st).abs().amax(dim=(1, 2))
+        print(f"[conditioning] P {P} T {T} {hide}: per-caption largest shift {float(shift.min()):.4f} .. {float(shift.max()):.4f}")
+        assert float(shift.min()) >= 3 * STAT_TOL, (hide, shift)
+
+
+@pytest.mark.parametrize("P,T,n,seed", BF16_DATA, ids=[f"p{d[0]}" for d in BF16_DATA])
+def test_one_hidden_key_moves_the_bf16_statistics(P, T, n, seed):
+    """the same for the bf16 cases at their own, noise-derived tolerance (computed on the oracle alone), in the maximum
+    over the steps of all captions; and the arg-max comparison of the GPU test is not vacuous: at least a quarter of
+    the steps clear 2 x the tolerance.  The tolerance is 0.03 .. 0.25 depending on where the oracle's rounding chaos
+    lands (it differs between machines); up to 17 positions every caption alone clears 3 x that, at 60 positions only the
+    maximum over the captions does (per-caption smallest shift 0.2 .. 0.9, printed): there the case sees a fault in the
+    64-position ballot round, not one lost key of every caption."""
+    ref = _bf16_forced_ref(P, T, n, seed)
+    pf = _prefilled(P, n, seed)
+    st = DD.stats(DD.forced_logits(pf, ref["forced"]))[1]
+    print(f"[conditioning bf16] P {P}: tolerance {ref['tol']:.4f} (oracle noise {ref['noise']:.4f}, class gap {ref['cls_gap']:.4f})")
+    assert ref["cls_gap"] > 1e-3
+    for hide in DD.HIDE:
+        shift = (DD.stats(DD.forced_logits(pf, ref["forced"], hide))[1] - st).abs().amax(dim=(1, 2))
+        print(f"[conditioning bf16] P {P} {hide}: per-caption largest shift {float(shift.min()):.4f} .. {float(shift.max()):.4f}"
+              f" = {float(shift.min()) / ref['tol']:.1f} .. {float(shift.max()) / ref['tol']:.1f} x tolerance")
+        assert float(shift.max()) >= 3 * ref["tol"], (hide, shift, ref["tol"])
+    clear = (ref["st"][:, :, 0] - ref["st"][:, :, 1]) > 2 * ref["tol"]
+    assert int(clear.sum()) >= n * T // 4
+
+
+BEAM_DATA = sorted({(c.B, c.P, c.T, c.n, c.seed) for c in BY_KIND["beam"]}, key=lambda d: (d[1], d[0]))
+
+
+@pytest.mark.parametrize("B,P,T,n,seed", BEAM_DATA, ids=[f"b{d[0]}-p{d[1]}" for d in BEAM_DATA])
+def test_beam_cases_keep_something_to_compare(B, P, T, n, seed):
+    """the oracle alone: at most one caption of a free-running beam case has a margin below 1e-4 (the seeds of the table
+    were chosen for it), so the exact comparison of the GPU test covers all the others"""
+    margin = _beam_oracle(B, P, T, n, seed)[4]
+    unclear = int((margin <= KEY_GAP).sum())
+    print(f"[margins] beam {B} P {P} T {T} seed {seed}: {unclear} of {n} captions below {KEY_GAP:g} (smallest {margin.min():.2e})")
+    assert unclear <= UNCLEAR_CAP
+
+
+BF16_BEAM_DATA = sorted({(c.B, c.P, c.T, c.n, c.seed) for c in BY_KIND["bf16_beam"]}, key=lambda d: (d[1], d[0]))
+
+
+@pytest.mark.parametrize("B,P,T,n,seed", BF16_BEAM_DATA, ids=[f"b{d[0]}-p{d[1]}" for d in BF16_BEAM_DATA])
+def test_bf16_beam_oracle_holds_still(B, P, T, n, seed):
+    """a free-running bf16 beam is compared through its best score at 0.05; round-off-sized input perturbations (1e-7
+    relative, the size of the difference between two correct fp32 summation orders) must therefore move the ORACLE's own
+    best score by less than half of that, or the bar says nothing (at 812 positions four of seeds 2..9 fail this: the
+    rounding chaos flips which beam survives).  Measured: 0.0024 at P = 812 seed 3, at most 0.006 at P = 5."""
+    base = _bf16_beam_best(B, P, T, n, seed)
+    moved = max(float(np.abs(_bf16_beam_best(B, P, T, n, seed, eps) - base).max()) for eps in (1e-7, -3e-7))
+    print(f"[bf16 beam oracle] beam {B} P {P} T {T} seed {seed}: best score moves by {moved:.4f} under 1e-7 perturbations")
+    assert moved <= 0.5 * BF16_BEST, moved
+
+
+LDS_CROSSINGS = [      # (beam, lever, P, T, first context on the far side of the case's threshold)
+    (5, "bi", 400, 16, 410), (5, "bi", 800, 16, 807), (5, "default", 812, 16, 820), (8, "default", 505, 16, 513),
+    (8, "default", 1000, 25, 1017)]
+
+
+def test_long_cases_cross_the_lds_thresholds_they_name():
+    """the launcher's byte arithmetic restated.  The DMA ring is 32 KB (four wavefronts x two buffers x 2 K + 2 V pieces of
+    1 KB), so beam 5 with the ring passes 64 KB of launch LDS at 410 positions; its ring starts at or beyond byte 65536
+    from 807; without the ring beam 5 passes 64 KB at 820 and beam 8 at 513; the beam-8 table is the full 128 KB (the
+    launcher's lds + 32 KB <= 160 KB limit, which is also what table + ring may take) from 1017 to 1024.  A case's
+    contexts run from P + 1 to P + T - 1 and lie on both sides of its threshold; the 605 case sits between two of them
+    (81 KB launches, ring below byte 65536) and the beam-5 case at 1000 ends at GPT-2's last position."""
+    first = lambda pred: next(L for L in range(1, 1025) if pred(L))
+    assert RING == 32768
+    assert first(lambda L: slot_table_bytes(5, L) + RING > 65536) == 410
+    assert first(lambda L: slot_table_bytes(5, L) >= 65536) == 807
+    assert first(lambda L: slot_table_bytes(5, L) > 65536) == 820
+    assert first(lambda L: slot_table_bytes(8, L) > 65536) == 513
+    assert first(lambda L: slot_table_bytes(8, L) == 131072) == 1017 and slot_table_bytes(8, 1024) + 32768 == 160 * 1024
+    assert slot_table_bytes(5, 1024) + RING <= 160 * 1024
+    long_cases = {(c.B, c.lever, c.P, c.T) for c in BY_KIND["beam"] if c.P > 100}
+    assert {x[:4] for x in LDS_CROSSINGS} | {(5, "bi", 605, 16), (5, "bi", 1000, 25)} == long_cases
+    for B, lever, P, T, at in LDS_CROSSINGS:
+        assert P + 1 < at <= P + T - 1, (B, lever, P, T, at)
+    assert 410 < 606 and 620 < 807
+    assert all(c.P + c.T - 1 == 1024 for c in CASES if c.P == 1000)
+
+
+# ================================================================================================ GPU
+class _Engines:
+    """one context per (cache type, CAPDEC_KV_DIRECT): the switch is read when a context is created"""
+
+    def __init__(self):
+        self.made = {}
+
+    def get(self, lever):
+        key = (lever.startswith("bf16"), lever.endswith("nodirect"))
+        if key not in self.made:
+            from capdec_amd.engine import Engine
+            saved = {k: os.environ.pop(k, None) for k in KNOBS}
+            try:
+                if key[1]:
+                    os.environ["CAPDEC_KV_DIRECT"] = "0"
+                e = Engine(0)
+            finally:
+                os.environ.pop("CAPDEC_KV_DIRECT", None)
+                os.environ.update({k: v for k, v in saved.items() if v is not None})
+            if key[0]:
+                e.set_gemm_mode("bf16")
+            e.load_gpt2(_model()[1])
+            self.made[key] = e
+        return self.made[key]
+
+    def run(self, c, forced=None):
+        """case c through its lever -> decode_greedy_forced's or decode_beam's outputs on the host (+ the slot counter)"""
+        e = self.get(c.lever)
+        pe, rnd = _inputs(c.P, c.T, c.n, c.seed)
+        bi = "bi" in c.lever.split("_")
+        e.set_batch_invariant(bi)
+        try:
+            if c.kind.endswith("forced"):
+                ids, st = e.decode_greedy_forced(pe, rnd if forced is None else forced)
+                return ids.cpu(), st.cpu()
+            ids, lens, sc, od = e.decode_beam(pe, STOP, c.B, c.T)
+            return ids.cpu().numpy(), lens.cpu().numpy(), sc.cpu().numpy(), od.cpu().numpy(), \
+                e.decode_counters()["kv_slots_per_position"]
+        finally:
+            e.set_batch_invariant(False)
+
+    def close(self):
+        for e in self.made.values():
+            e.close()
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = _Engines()
+    yield e
+    e.close()
+
+
+@gpu
+@pytest.mark.parametrize("c", BY_KIND["forced"], ids=IDS(BY_KIND["forced"]))
+def test_greedy_teacher_forced_vs_fp64(eng, c):
+    """(a) decode_greedy_forced on random forced tokens against the fp64 definition: every step's (top-1, top-2,
+    logsumexp) within 1e-4, arg-max equal wherever the fp64 gap exceeds 2e-4.
+    observed: at most 1.8e-5 over the 30 cases (default 1.5e-5, batch-invariant 1.8e-5, without the direct K/V 1.7e-5); 1161 of 1164 steps clear"""
+    ids, st = eng.run(c)
+    ids64, st64 = _forced_def(c.P, c.T, c.n, c.seed)
+    err = float((st.double() - st64).abs().max())
+    clear = (st64[..., 0] - st64[..., 1]) > ID_GAP
+    _report(f"[decode attention] {c.id} {c.form}: max |stat - fp64| {err:.2e} (bound {STAT_TOL:g}), "
+            f"{int(clear.sum())} of {clear.numel()} steps with a clear arg-max")
+    assert err <= STAT_TOL, err
+    assert bool((ids.long()[clear] == ids64[clear]).all())
+
+
+def _beam_vs_oracle_and_fp64(eng, c):
+    ids, lens, sc, od, slots = eng.run(c)
+    tok_o, seq_o, sc_o, od_o, margin = _beam_oracle(c.B, c.P, c.T, c.n, c.seed)
+    same = tied = 0
+    for r in range(c.n):
+        eq = (np.array_equal(od[r], od_o[r]) and np.array_equal(ids[r], tok_o[r]) and np.array_equal(lens[r], seq_o[r])
+              and np.allclose(sc[r], sc_o[r], atol=KEY_GAP, rtol=0))
+        if eq:
+            same += 1
+        elif margin[r] <= KEY_GAP:
+            assert np.isfinite(sc[r]).all() and (np.diff(sc[r]) <= 0).all()      # a tie: any surviving beam set is valid
+            tied += 1
+        else:
+            np.testing.assert_array_equal(od[r], od_o[r])
+            np.testing.assert_array_equal(ids[r], tok_o[r])
+            np.testing.assert_array_equal(lens[r], seq_o[r])
+            np.testing.assert_allclose(sc[r], sc_o[r], atol=KEY_GAP, rtol=0)
+    # every returned beam, whichever side of a tie it came from: its score is the mean log-prob of its own tokens
+    assert (lens == c.T).all()
+    own = DD.token_logp(DD.forced_logits(_prefilled(c.P, c.n, c.seed), torch.from_numpy(ids.astype(np.int64))),
+                        torch.from_numpy(ids.astype(np.int64))).mean(-1).numpy()
+    err = float(np.abs(sc.astype(np.float64) - own).max())
+    _report(f"[decode attention] {c.id} {c.form}: {same} of {c.n} captions identical to the oracle, {tied} differ on a tie; "
+            f"max |score - fp64 mean log-prob of its tokens| {err:.2e} (bound {STAT_TOL:g}); {slots:.3f} slots per position")
+    assert same + tied == c.n
+    assert err <= STAT_TOL, err
+    assert c.B == 1 or slots > 1.0                            # the diverged phase B really ran
+
+
+SHORT_BEAMS = [c for c in BY_KIND["beam"] if c.P <= 100]
+LONG_BEAMS = [c for c in BY_KIND["beam"] if c.P > 100]
+
+
+@gpu
+@pytest.mark.parametrize("c", SHORT_BEAMS, ids=IDS(SHORT_BEAMS))
+def test_beam_short_contexts_vs_oracle_and_fp64(eng, c):
+    """(b) beam widths 1..8 at every peel value: clear captions identical to O.beam_cached (order, tokens, lengths, scores
+    1e-4), every returned beam's score within 1e-4 of the fp64 mean log-prob of its tokens, more than one K/V slot per
+    position from width 2.
+    observed: all 6 captions of all 102 cases identical to the oracle; score against fp64 at most 2.3e-6; 1.04 .. 1.81 slots per position"""
+    _beam_vs_oracle_and_fp64(eng, c)
+
+
+@gpu
+@pytest.mark.parametrize("c", LONG_BEAMS, ids=IDS(LONG_BEAMS))
+def test_beam_past_64_kb_of_lds_vs_oracle_and_fp64(eng, c):
+    """(c) beam 5 (LDS-DMA form and register-landed form) and beam 8 across the contexts where the launch passes 64 KB of
+    LDS, where the DMA ring starts beyond byte 65536, and up to position 1024 / the 128 KB table: the checks of (b).
+    observed: all 4 captions of all 7 cases identical to the oracle; score against fp64 at most 2.0e-6, contexts 401 .. 1024"""
+    _beam_vs_oracle_and_fp64(eng, c)
+
+
+@gpu
+@pytest.mark.parametrize("c", BY_KIND["bf16_forced"], ids=IDS(BY_KIND["bf16_forced"]))
+def test_bf16_cache_teacher_forced_vs_bf16_oracle(eng, c):
+    """(d) the bf16 cache under teacher forcing (the fp32 oracle's greedy ids) against the oracle on bf16-rounded operands:
+    within max(4 x oracle noise, 0.5 x class gap), really the bf16 path, arg-max equal where the margin clears 2 x that.
+    observed: 0.023 .. 0.047 against tolerances of 0.044 (P = 1) .. 0.22 (P = 60)"""
+    ref = _bf16_forced_ref(c.P, c.T, c.n, c.seed)
+    ids, st = eng.run(c, ref["forced"])
+    err = float((st - ref["st"]).abs().max())
+    _report(f"[decode attention] {c.id} {c.form}: max |stat - bf16 oracle| {err:.4f}, tolerance {ref['tol']:.4f} "
+            f"(oracle noise {ref['noise']:.4f}, bf16-vs-fp32 gap {ref['cls_gap']:.4f})")
+    assert err <= ref["tol"], (err, ref["tol"])
+    assert float((st - ref["f32_st"]).abs().max()) > 0.1 * ref["cls_gap"]          # really the bf16 path
+    clear = (ref["st"][:, :, 0] - ref["st"][:, :, 1]) > 2 * ref["tol"]
+    assert bool((ids[clear] == ref["ids"][clear]).all())
+
+
+@gpu
+@pytest.mark.parametrize("c", BY_KIND["bf16_beam"], ids=IDS(BY_KIND["bf16_beam"]))
+def test_bf16_cache_free_running_beam(eng, c):
+    """(d) free-running beams on the bf16 cache -- beam 5 at 813..827 positions, every other width at a short context --
+    by the bar of test_bf16_mode_logits_and_decode_vs_bf16_oracle: best mean log-prob within 0.05 of the bf16 oracle's,
+    finite, full length.
+    observed: 0.002 .. 0.005 at P = 5; 0.0045 at P = 812 (seed 3)"""
+    ids, lens, sc, od, slots = eng.run(c)
+    best = _bf16_beam_best(c.B, c.P, c.T, c.n, c.seed)
+    err = float(np.abs(sc[:, 0] - best).max())
+    _report(f"[decode attention] {c.id} {c.form}: max |best score - bf16 oracle's| {err:.4f} (bound {BF16_BEST}), "
+            f"{slots:.3f} slots per position")
+    assert np.isfinite(sc).all() and (lens == c.T).all() and (np.diff(sc, axis=1) <= 0).all()
+    assert err <= BF16_BEST, err
+    assert slots > 1.0
+
+
+# ------------------------------------------------------------------------------------------------ what was launched
+MARKER = "normalize_prefix_kernel"                        # one launch of it separates two cases in the trace
+
+
+def attn_form(name):
+    """<BEAM, KV, OCC, NA, CUR, DMA> of a traced attn_decode_beams_kernel launch, from the mangled or the demangled name;
+    None for every other kernel"""
+    m = re.search(r"attn_decode_beams_kernelILi(\d+)E(f|DF16b)Li(\d+)ELi(\d+)ELb([01])ELb([01])E", name)
+    if m:
+        g = m.groups()
+        return (int(g[0]), "float" if g[1] == "f" else "bf16", int(g[2]), int(g[3]), int(g[4]), int(g[5]))
+    m = re.search(r"attn_decode_beams_kernel<(\d+), *(float|__bf16), *(\d+), *(\d+), *(true|false), *(true|false)>", name)
+    if m:
+        g = m.groups()
+        return (int(g[0]), "float" if g[1] == "float" else "bf16", int(g[2]), int(g[3]), int(g[4] == "true"), int(g[5] == "true"))
+    assert "attn_decode_beams_kernel" not in name, f"unparsed decode-attention kernel name: {name}"
+    return None
+
+
+def test_attn_form_reads_both_name_forms():
+    assert attn_form("_ZN6capdec24attn_decode_beams_kernelILi5EfLi4ELi2ELb1ELb1EEEvPKfPT0_S4_iiiiiPKhiPfPcPKiiii") == (5, "float", 4, 2, 1, 1)
+    assert attn_form("_ZN6capdec24attn_decode_beams_kernelILi8EDF16bLi2ELi2ELb0ELb0EEEvPKfPT0_S4_iiiiiPKhiPfPcPKiiii") == (8, "bf16", 2, 2, 0, 0)
+    assert attn_form("void capdec::attn_decode_beams_kernel<1, float, 4, 4, false, false>") == (1, "float", 4, 4, 0, 0)
+    assert attn_form("void capdec::attn_decode_beams_kernel<5, __bf16, 4, 2, true, false>") == (5, "bf16", 4, 2, 1, 0)
+    assert attn_form("capdec::attn_prefill_rows_kernel<8, float>") is None
+
+
+def forms_by_case(rows):
+    """the traced launches cut at the marker kernel: one set of decode-attention forms per case, in order"""
+    groups = None
+    for _, _, name, _, _ in rows:
+        if MARKER in name:
+            groups = (groups or []) + [set()]
+        elif groups is not None:
+            f = attn_form(name)
+            if f is not None:
+                groups[-1].add(f)
+    return groups or []
+
+
+def _read_kernel_trace(src):
+    spec = importlib.util.spec_from_file_location("capdec_trace_summary", os.path.join(ROOT, "tools", "trace_summary.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.read_kernel_trace(src)
+
+
+def _script(argv):
+    return [sys.executable, os.path.abspath(__file__)] + argv
+
+
+@gpu
+def test_cases_launch_the_forms_they_claim(tmp_path):
+    """(e) this file as a script -- every case of the table once, in table order, no references -- in a fresh child process
+    under rocprofv3 --kernel-trace: the decode-attention forms launched by each case are exactly the one its row claims,
+    and every form of LIVE is reached.
+    observed: 166 cases, 3.6 s untraced, 3.8 s under rocprofv3; all 30 forms reached by 1 .. 16 cases each"""
+    exe = shutil.which("rocprofv3") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "rocprofv3")
+    assert os.path.exists(exe), "rocprofv3 not found: the launched kernels cannot be observed (this test does not skip)"
+    t0 = time.time()
+    r = subprocess.run(_script(["--run-all"]), capture_output=True, text=True, timeout=1200)
+    untraced = time.time() - t0
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    limit = int(120 + 5 * untraced)
+    t0 = time.time()
+    r = subprocess.run(["timeout", "-k", "10", str(limit), exe, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path),
+                        "--"] + _script(["--run-all"]), capture_output=True, text=True)
+    _report(f"[decode attention trace] {len(CASES)} cases: {untraced:.1f} s untraced, {time.time() - t0:.1f} s under rocprofv3")
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    groups = forms_by_case(_read_kernel_trace(str(tmp_path)))
+    assert len(groups) == len(CASES), f"{len(groups)} marked groups traced for {len(CASES)} cases"
+    bad, reached = [], collections.Counter()
+    for c, seen in zip(CASES, groups):
+        for f in seen:
+            reached[f] += 1
+        if seen != {c.form}:
+            bad.append(f"{c.id}: claimed {c.form}, observed {sorted(seen)}")
+    for f in sorted(set(LIVE) | set(reached)):
+        _report(f"[decode attention trace] {reached[f]:4d} cases reached <{', '.join(str(v) for v in f)}>")
+    assert not bad, "\n".join(bad)
+    assert set(reached) == set(LIVE)
+
+
+def _run_all():
+    """script mode: a marker launch, then every case once in table order (random forced tokens, no references)"""
+    e = _Engines()
+    x = torch.ones(4, 512)
+    for c in CASES:
+        e.get(c.lever).normalize_prefix(x)
+        e.run(c)
+        print("ran", c.id, flush=True)
+    torch.cuda.synchronize()
+    e.close()
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["--run-all"]:
+        _run_all()
+    elif sys.argv[1:] == ["--list"]:
+        for c in CASES:
+            print(c.id, c.form)
+    else:
+        sys.exit("usage: test_decode_attention.py --run-all | --list")
