@@ -57,13 +57,37 @@ template <int TJ, int Q> struct EpiWalk {
 
 // One wavefront: acc[i][j] (TR layout; WAVE_M / WAVE_N = the wavefront's block coordinates in units of its tile) ->
 // slab -> out.  MODE 0: fp32 C (+ bias, activation, residual); 1: packed output (+ packed residual); 2: qkv scatter.
-template <int TI, int TJ, int MODE, int ACT>
+// AHEAD (MODE 0 and 2, a lane's column the same in every pass): the lane's bias quad and, MODE 0, the residual quads of
+// all its TI x PASSES pieces are requested BEFORE the transposition instead of inside each store pass, where a pass's
+// residual load sat behind the previous pass's stores on the wavefront's memory counter -- TI x PASSES x 4 registers, so
+// only for the 2 x 2 tile, whose cross-term accumulators are dead by then.  Addresses of pieces past M or N are clamped
+// into the matrix (loaded, never used): no branch per load.  The arithmetic of a piece is unchanged.
+template <int TI, int TJ, int MODE, int ACT, bool AHEAD = false>
 __device__ __forceinline__ void epilogue_lds_wave(const f32x16 (&acc)[TI][TJ], float *slab, int row0, int col0,
                                                   const EpiArgs &a) {
     using S = EpiSlab<TJ>;
     const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
     constexpr int Q = MODE == 1 ? 2 : 1;                           // packed output: 8 columns (one 16-byte piece) per lane
     using Wk = EpiWalk<TJ, Q>;
+    constexpr bool PRE = AHEAD && MODE != 1;
+    static_assert(!PRE || (64 % Wk::LPR == 0 && Wk::PASSES * 64 == 32 * Wk::LPR), "AHEAD: one column per lane, whole passes");
+    float4 bq = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 rq[PRE && MODE == 0 ? TI * Wk::PASSES : 1];
+    if constexpr (PRE) {
+        const int colc = min(col0 + (lane % Wk::LPR) * 4, a.N - 4);
+        if (a.bias) bq = *reinterpret_cast<const float4 *>(a.bias + colc);
+        if constexpr (MODE == 0) {
+            if (a.resid) {
+#pragma unroll
+                for (int i = 0; i < TI; ++i)
+#pragma unroll
+                    for (int p = 0; p < Wk::PASSES; ++p) {
+                        const int rowc = min(row0 + i * 32 + (p * 64 + lane) / Wk::LPR, a.M - 1);
+                        rq[i * Wk::PASSES + p] = *reinterpret_cast<const float4 *>(a.resid + (size_t)rowc * a.ldr + colc);
+                    }
+            }
+        }
+    }
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
         // ---- accumulators -> slab (row l32, four consecutive columns per quad)
@@ -89,7 +113,9 @@ __device__ __forceinline__ void epilogue_lds_wave(const f32x16 (&acc)[TI][TJ], f
                 v[q] = *reinterpret_cast<const float4 *>(slab + rl * S::LD + cq * (4 * Q) + 4 * q);
                 v[q].x *= a.scale; v[q].y *= a.scale; v[q].z *= a.scale; v[q].w *= a.scale;
                 if (a.bias) {
-                    const float4 b = *reinterpret_cast<const float4 *>(a.bias + col + 4 * q);
+                    float4 b;
+                    if constexpr (PRE) b = bq;
+                    else b = *reinterpret_cast<const float4 *>(a.bias + col + 4 * q);
                     v[q].x += b.x; v[q].y += b.y; v[q].z += b.z; v[q].w += b.w;
                 }
                 v[q].x = act_const<ACT>(v[q].x); v[q].y = act_const<ACT>(v[q].y);
@@ -97,7 +123,9 @@ __device__ __forceinline__ void epilogue_lds_wave(const f32x16 (&acc)[TI][TJ], f
             }
             if constexpr (MODE == 0) {
                 if (a.resid) {
-                    const float4 r4 = *reinterpret_cast<const float4 *>(a.resid + (size_t)row * a.ldr + col);
+                    float4 r4;
+                    if constexpr (PRE) r4 = rq[i * Wk::PASSES + p];
+                    else r4 = *reinterpret_cast<const float4 *>(a.resid + (size_t)row * a.ldr + col);
                     v[0].x = post_resid_const<ACT>(v[0].x + r4.x); v[0].y = post_resid_const<ACT>(v[0].y + r4.y);
                     v[0].z = post_resid_const<ACT>(v[0].z + r4.z); v[0].w = post_resid_const<ACT>(v[0].w + r4.w);
                 }
@@ -156,30 +184,30 @@ __device__ __forceinline__ void epilogue_lds_wave(const f32x16 (&acc)[TI][TJ], f
 }
 
 // the activation code becomes a compile-time constant of the element loops (one switch per tile, not per element)
-template <int TI, int TJ, int MODE>
+template <int TI, int TJ, int MODE, bool AHEAD = false>
 __device__ __forceinline__ void epilogue_lds_dispatch(const f32x16 (&acc)[TI][TJ], float *slab, int row0, int col0,
                                                       const EpiArgs &a) {
     switch (a.act) {
-        case CAPDEC_ACT_GELU_NEW: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_GELU_NEW>(acc, slab, row0, col0, a); break;
-        case CAPDEC_ACT_QUICK_GELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_QUICK_GELU>(acc, slab, row0, col0, a); break;
-        case CAPDEC_ACT_RELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_RELU>(acc, slab, row0, col0, a); break;
-        case CAPDEC_ACT_TANH: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_TANH>(acc, slab, row0, col0, a); break;
-        case CAPDEC_ACT_RESID_RELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_RESID_RELU>(acc, slab, row0, col0, a); break;
-        default: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_NONE>(acc, slab, row0, col0, a); break;
+        case CAPDEC_ACT_GELU_NEW: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_GELU_NEW, AHEAD>(acc, slab, row0, col0, a); break;
+        case CAPDEC_ACT_QUICK_GELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_QUICK_GELU, AHEAD>(acc, slab, row0, col0, a); break;
+        case CAPDEC_ACT_RELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_RELU, AHEAD>(acc, slab, row0, col0, a); break;
+        case CAPDEC_ACT_TANH: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_TANH, AHEAD>(acc, slab, row0, col0, a); break;
+        case CAPDEC_ACT_RESID_RELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_RESID_RELU, AHEAD>(acc, slab, row0, col0, a); break;
+        default: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_NONE, AHEAD>(acc, slab, row0, col0, a); break;
     }
 }
 
 // block-level entry: G supplies WN, TI, TJ (wavefront w owns tile (w / WN, w % WN)); smem = the block's idle ring, at
 // least NW * EpiSlab<TJ>::BYTES
-template <class G>
+template <class G, bool AHEAD = false>
 __device__ __forceinline__ void epilogue_lds(const f32x16 (&acc)[G::TI][G::TJ], char *smem, const EpiArgs &a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / G::WN, wn = wave % G::WN;
     float *slab = reinterpret_cast<float *>(smem + wave * EpiSlab<G::TJ>::BYTES);
     const int row0 = a.m0 + wm * G::TI * 32, col0 = a.n0 + wn * G::TJ * 32;
     if (a.packed) epilogue_lds_dispatch<G::TI, G::TJ, 1>(acc, slab, row0, col0, a);
-    else if (a.sc && a.sc->kc) epilogue_lds_wave<G::TI, G::TJ, 2, CAPDEC_ACT_NONE>(acc, slab, row0, col0, a);
-    else epilogue_lds_dispatch<G::TI, G::TJ, 0>(acc, slab, row0, col0, a);
+    else if (a.sc && a.sc->kc) epilogue_lds_wave<G::TI, G::TJ, 2, CAPDEC_ACT_NONE, AHEAD>(acc, slab, row0, col0, a);
+    else epilogue_lds_dispatch<G::TI, G::TJ, 0, AHEAD>(acc, slab, row0, col0, a);
 }
 
 }  // namespace capdec

@@ -359,7 +359,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__r
         h2_join(am, ac);
         if constexpr (VEC4) {
             const EpiArgs ea = h2_epi_args(C, ldc, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, resid, ldr, act, packed_out, PK_F16X2, &sc);
-            epilogue_lds<H2Tile>(am, smem, ea);
+            // (<.., true>: the tile's bias and residual quads are requested before the transposition -- the cross-term
+            //  accumulators are dead after h2_join, their registers hold the 16 residual quads; gemm_epilogue_lds.h)
+            epilogue_lds<H2Tile, true>(am, smem, ea);
             h2_slab_release(tile + (int)gridDim.x < ntiles);
         } else if (packed_out) {
             epilogue_store_packed_t(am, packed_out, N >> 4, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, act, PK_F16X2,
