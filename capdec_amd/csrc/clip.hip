@@ -171,7 +171,6 @@ static int conv3x3_implicit(capdec_ctx *c, const ConvW &w, const void *in_pk, in
     e.bias = w.b;
     e.act = act;
     e.packed_out = packed_out;
-    CAPDEC_TRY(gemm_epilogue(c, e, n * H * W, w.cout_p, w.K, /*split=*/false, c->batch_invariant));
     ProfScope ps(c, gemm_family(fmt), 2.0 * n * H * W * (double)w.cout_p * w.K);
     return launch_conv3x3_packed(c->stream, in_pk, pl, out, w.cout_p, n, H, W, w.cin_p, w.cout_p, e, fmt, c->r_zero.p,
                                  c->r_zero.cap);

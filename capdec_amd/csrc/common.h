@@ -8,6 +8,7 @@
 
 #include "../../include/capdec.h"
 #include "config.h"
+#include "gemm_plan.h"
 
 namespace capdec {
 
@@ -112,24 +113,22 @@ struct QkvScatter {
     bool bf16 = false;                      // bf16 mode: the cache holds bf16 -- K / V are rounded (RNE) as they are written
 };
 
-// The epilogue and launch options of one GEMM.  Families: f32 (native fp32), bf16x3 (fp32 A), bf16x3p / f16x2p / x1
-// (packed A; f16x2p includes the wide-tile and ping-pong geometries its planner picks: gemm_h2w.hip, gemm_pp.hip) and the
-// implicit 3x3 convolution.  gemm_dispatch.hip fills the shared fields (gemm_epilogue).
+// The epilogue of one GEMM.  Families: f32 (native fp32), bf16x3 (fp32 A), the packed-A kernels (bf16x3p / f16x2p / x1 and
+// the wide-tile and ping-pong geometries of the two-plane format: gemm_h2w.hip, gemm_pp.hip) and the implicit 3x3
+// convolution.  WHAT a packed launch runs -- kernel, K slices, blocks, workspace -- is decided by gemm_plan() (gemm_plan.h)
+// alone; gemm_dispatch.hip (launch_packed) computes the plan from this struct and the shape and attaches the workspace.
 struct GemmEpilogue {
     const float *bias = nullptr;   // [N]                                       (all)
     const float *resid = nullptr;  // [M, ldr] added after the activation       (all)
     int ldr = 0;
     int act = CAPDEC_ACT_NONE;     //                                           (all)
-    void *splitk_ws = nullptr;     // bf16x3p / f16x2p / x1: workspace for split-K partial tiles (gemm_splitk_ws_bytes);
-    size_t splitk_ws_bytes = 0;    // without it under-filled grids run unsplit
+    void *splitk_ws = nullptr;     // packed-A kernels: workspace [S][M][N] of a plan with S > 1 (GemmPlan::ws_bytes)
     void *packed_out = nullptr;    // bf16x3p / f16x2p / x1 / conv: write act(acc + bias) as the packed A operand (K = N, the
                                    // launch's format) of the next GEMM instead of fp32 C
     const Tuning *tune = nullptr;  // the context's environment knobs (config.h); nullptr = every default
-    const QkvScatter *qkv_scatter = nullptr;   // f16x2p / x1, unsplit grids only (see QkvScatter)
-    bool invariant = false;        // f16x2p only -- batch-invariant mode: the unsplit 128 x 128 kernel whatever M is (no
-                                   // planner, no split-K)
-    bool wide_ok = false;          // f16x2p only: the B operand is a weight with max |w| < 16, so its high plane can be scaled
-                                   // by 2^11 in fp16 registers (the single-accumulator kernels of gemm_h2w.hip)
+    const QkvScatter *qkv_scatter = nullptr;   // f16x2p / x1, unsplit plans only (see QkvScatter)
+    bool wide_ok = false;          // planner input, f16x2p only: the B operand is a weight with max |w| < 16, so its high plane
+                                   // can be scaled by 2^11 in fp16 registers (the single-accumulator kernels of gemm_h2w.hip)
     const void *resid_packed = nullptr;   // f16x2p / x1 with packed_out only: residual [M, N] stored as a packed operand of
                                           // the output's format (added after the activation; no split-K then)
     // bf16x3p / f16x2p / x1: optional LayerNorm of the RESULT rows, fused into the split-K reduce pass (only when the launch
@@ -159,6 +158,37 @@ inline int with_topk_k(int k, const char *what, F &&f) {
 }
 inline const Tuning &tuning_of(const GemmEpilogue &e) { return e.tune ? *e.tune : default_tuning(); }
 
+// ---- what every packed launcher does before it launches what its plan names
+// float4 epilogue when every row segment is 16-byte aligned (always the case on the decode path): a planner input
+inline bool gemm_vec4(const GemmEpilogue &epi, const float *C, int ldc, int N) {
+    return N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
+           (epi.bias == nullptr || ((uintptr_t)epi.bias & 15) == 0) &&
+           (epi.resid == nullptr || (epi.ldr % 4 == 0 && ((uintptr_t)epi.resid & 15) == 0));
+}
+struct PackedArgs {
+    const float *resid = nullptr;      // the kernels' one residual argument: packed with a packed output, else fp32
+    QkvScatter sc;
+    float *part = nullptr;             // split launches: the workspace [S][M][N]
+};
+inline int packed_args(const std::string &who, const GemmEpilogue &epi, const GemmPlan &plan, const float *C, int ldc, int M,
+                       int N, int K, PackedArgs *a) {
+    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, who + ": K must be a multiple of 64");
+    CAPDEC_CHECK(epi.packed_out == nullptr ||
+                     (N % 64 == 0 && epi.resid == nullptr && ((uintptr_t)epi.bias & 15) == 0),
+                 who + ": packed output needs N % 64 == 0, a 16-byte aligned bias and no residual");
+    const bool vec4 = gemm_vec4(epi, C, ldc, N);
+    CAPDEC_CHECK(plan.vec4 == vec4 && (plan.S == 1 || epi.splitk_ws), who + ": the plan was made for another launch");
+    CAPDEC_CHECK(epi.resid_packed == nullptr || epi.packed_out != nullptr, who + ": a packed residual needs a packed output");
+    a->resid = epi.packed_out ? (const float *)epi.resid_packed : epi.resid;
+    a->sc = epi.qkv_scatter ? *epi.qkv_scatter : QkvScatter();
+    a->part = (float *)epi.splitk_ws;
+    const QkvScatter &sc = a->sc;
+    CAPDEC_CHECK(!sc.kc || (vec4 && epi.bias && !epi.resid && !epi.packed_out && epi.act == CAPDEC_ACT_NONE && N == 3 * sc.d &&
+                            sc.d % GEMM_BN == 0 && plan.S == 1),
+                 who + ": the qkv scatter epilogue needs an unsplit, biased, plain [M, 3d] projection");
+    return 0;
+}
+
 // gemm_f32.hip
 int launch_gemm_f32(hipStream_t st, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc,
                     int M, int N, int K, const GemmEpilogue &epi);
@@ -178,14 +208,12 @@ int launch_gemm_bf16x3(hipStream_t st, const float *A, int lda, const void *Bpac
 int launch_gemm_bf16x3_topk(hipStream_t st, const float *A, int lda, const void *Bpacked, int M, int N, int K, int k,
                             float inv_temp, const TopkOut &o);
 // packed-A variants: A already split / tile-major (written by launch_layernorm_packed, launch_pack_planes): both
-// operands move by LDS-DMA
+// operands move by LDS-DMA.  Every packed launcher (here and below) takes the GemmPlan that gemm_plan() made for the launch:
+// it checks its arguments against the plan and launches the kernel, slices and blocks the plan names
 int launch_gemm_bf16x3p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                        const GemmEpilogue &epi);
+                        const GemmEpilogue &epi, const GemmPlan &plan);
 int launch_gemm_bf16x3p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
                              float inv_temp, const TopkOut &o);
-// split-K of the packed-A kernel for under-filled grids: number of K slices (1 = none) and the workspace it needs
-int gemm_splitk_slices(int M, int N, int K, const Tuning &t = default_tuning());
-size_t gemm_splitk_ws_bytes(int M, int N, int K, const Tuning &t = default_tuning());
 // adds the S partial tiles of a split-K launch in slice order and applies the epilogue (fmt: packed output format)
 int launch_splitk_reduce(hipStream_t st, const float *part, int S, int M, int N, const GemmEpilogue &epi, float *C,
                          int ldc, int fmt);
@@ -195,25 +223,21 @@ int launch_splitk_reduce(hipStream_t st, const float *part, int S, int M, int N,
 int launch_pack_planes_h2(hipStream_t st, const float *w, int ldw, int N, int K, void *out);
 // ... and the TRANSPOSE of src [rows][cols] (row stride ld) as the packed matrix [cols][Kp] (k = the rows of src, zero-padded to Kp)
 int launch_pack_planes_h2_t(hipStream_t st, const float *src, int ld, int rows, int cols, int Kp, void *out);
+// fmt: PK_F16X2, or PK_F16X1 / PK_BF16X1 -- the one-plane kernels on the same main loop (32-deep stages, one MFMA per product)
 int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                       const GemmEpilogue &epi);
+                       const GemmEpilogue &epi, int fmt, const GemmPlan &plan);
 int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                            float inv_temp, const TopkOut &o);
-// round-3 wide-tile kernels with ONE accumulator set (gemm_h2w.hip); scale = 2^(t - 11), t = pack-time pre-scale
-// exponent of the weights; `which`: 2 = 256x128, 8 = 128x192 (two blocks per CU)
-int h2w_plan(int M, int N, int K);
+                            float inv_temp, const TopkOut &o, int fmt);
+// round-3 wide-tile kernels with ONE accumulator set (gemm_h2w.hip); plan.geo: 2 = 256x128, 8 = 128x192 (two blocks per CU)
 int launch_absmax_bits(hipStream_t st, const float *w, size_t n, unsigned *d_out);
-int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
-                    int K, const GemmEpilogue &epi, float scale);
+int launch_gemm_h2w(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
+                    const GemmEpilogue &epi, const GemmPlan &plan);
 int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
                          float inv_temp, const TopkOut &o);
 // round-4 ping-pong kernels (gemm_pp.hip): ONE 8-wavefront block per CU, the two wavefronts of a SIMD alternate between a
-// load phase and a matrix phase; `which`: 10 = 256x128 (two accumulator sets), 14 = 256x192 (one set)
-int launch_gemm_pp(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
-                   int K, const GemmEpilogue &epi, float scale);
-// planner: 0 = keep the kernels of rounds 2-3, else a ping-pong geometry (10 = 256x128, 14 = 256x192)
-int pp_plan(int M, int N, int K, bool wide_ok, bool can_split);
-size_t pp_splitk_ws_bytes(int which, int M, int N, int K);
+// load phase and a matrix phase; plan.geo: 10 = 256x128 (two accumulator sets), 14 = 256x192 (one set)
+int launch_gemm_pp(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
+                   const GemmEpilogue &epi, const GemmPlan &plan);
 // exact second pass of the fused lm_head (decode.hip): k = 5 lists for the *m_dev rows of a compacted packed A operand
 int launch_gemm_h2w_topk_dev(hipStream_t st, const void *Apacked, const void *Bpacked, const int *m_dev, int N, int K,
                              float inv_temp, const TopkOut &o);
@@ -221,11 +245,6 @@ int launch_gemm_x1_topk_dev(hipStream_t st, const void *Apacked, const void *Bpa
                             float inv_temp, const TopkOut &o, int fmt);
 // generic packer for any PackFmt (gemm_f16x2.hip); the one-plane formats use it
 int launch_pack_planes_fmt(hipStream_t st, const float *w, int ldw, int N, int K, void *out, int fmt);
-// round-2 one-plane kernels on the f16x2 main loop (gemm_f16x2.hip): 128x128 tile, two blocks per CU, 32-deep stages
-int launch_gemm_x1(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                   const GemmEpilogue &epi, int fmt);
-int launch_gemm_x1_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                        float inv_temp, const TopkOut &o, int fmt);
 // LayerNorm whose output goes straight into the packed split-bf16 A format of the next GEMM (d % 16 == 0)
 int launch_layernorm_packed(hipStream_t st, const float *x, int ldx, const float *w, const float *b, float eps,
                             void *packed, int rows, int d, int fmt = 0);

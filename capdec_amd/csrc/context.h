@@ -261,12 +261,6 @@ int planes_of(capdec_ctx *c, const float *W, int N, int K, bool cache, const voi
               bool *wide_ok = nullptr);
 // profiler family of a packed-operand GEMM in format fmt (PK_*: bf16x3.h)
 int gemm_family(int fmt);
-// Fills the GemmEpilogue fields every launch shares; call it once e.wide_ok is known.
-//   tune       the context's knobs
-//   invariant  apply the batch-invariant rule: the unsplit 128 x 128 kernel whatever M is (callers pass c->batch_invariant;
-//              the test hook passes false)
-//   split      the caller allows split-K: the workspace is attached when the planner wants one (never batch-invariant)
-int gemm_epilogue(capdec_ctx *c, GemmEpilogue &e, int M, int N, int K, bool split, bool invariant);
 // C = epilogue(A . Bt^T) on the native fp32 MFMA kernel (the f32 mode, other K; the train step under CAPDEC_TRAIN_F16X2=0)
 int gemm_native(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N, int K,
                 GemmEpilogue e = GemmEpilogue());

@@ -49,7 +49,7 @@ int stack_body(capdec_ctx *c, const StackCfg &g, const StepShape &s, const KvCac
         const bool scatter = kv_direct && !s.prefill && g.keep_kv && mode_ok && use_packed_a(c, d) && w.bqkv &&
                              (((uintptr_t)w.bqkv | (uintptr_t)qkv) & 15) == 0 &&
                              d % GEMM_BN == 0 && (s.beam == 1 || s.beam == 5) &&
-                             (c->batch_invariant || gemm_splitk_slices(M, 3 * d, d, c->tune) == 1);
+                             (c->batch_invariant || plan_splitk_128(M, 3 * d, d, c->tune) == 1);
         if (scatter) {
             sc.kc = reinterpret_cast<float *>(kv.bf16 ? (void *)kv.kp<__bf16>(kl) : (void *)kv.kp<float>(kl));
             sc.vc = reinterpret_cast<float *>(kv.bf16 ? (void *)kv.vp<__bf16>(kl) : (void *)kv.vp<float>(kl));

@@ -15,6 +15,7 @@
 
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "gemm_packed.h"
 
 namespace capdec {
 
@@ -241,8 +242,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_topk_kernel(const float *_
 // 12 ds_read_b128, 24 MFMAs and 6 DMA pieces (tile kt+2 -> stage (kt+2)%3), and one counted s_waitcnt
 // vmcnt(6) in front of a raw s_barrier retires the pieces of tile kt+1.  Every vector-memory operation of the
 // loop is a DMA, so the in-order vmcnt count is exact.
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 // TR: the MFMA operands are swapped (D^T = B^T-fragment x A-fragment), so a lane ends up with FOUR CONSECUTIVE COLUMNS
 // of one output row (row = lane & 31, columns 8 (r >> 2) + 4 (lane >> 5) + (r & 3)) instead of four consecutive
@@ -543,70 +542,26 @@ int launch_splitk_reduce(hipStream_t st, const float *part, int S, int M, int N,
     return 0;
 }
 
-// slices for a [M, N, K] problem (1 = no split).  Two under-filled regimes (the chip runs 512 blocks at a time):
-//  (a) M <= 512 rows (at most four tile rows: the decode of small batches): S depends on K ONLY -- the largest divisor of
-//      the k-step count that leaves >= 8 (an even number of) k-steps per slice -- so a row's result is bit-identical for
-//      every batch size in this regime;
-//  (b) larger M whose grid is still at most HALF of the chip (<= 256 tiles: the N = 768 projections at a few thousand
-//      rows, e.g. 625 captions x beam 5 = 3125 rows -> 150 tiles): the largest S with tiles x S <= 512 and >= 16 (even)
-//      k-steps per slice.  mlp.c_proj (K = 3072, 150 tiles walking 192 k-steps each): 58 -> ~35 us.
-// Across a regime / S boundary the fp32 summation order of a row changes (round-off level; the unsplit regime above is
-// again batch-size independent).  CAPDEC_SPLITK=0 disables both, CAPDEC_SPLITK_MID=0 only (b).
-int gemm_splitk_slices(int M, int N, int K, const Tuning &t) {
-    const bool off = !t.splitk, mid_off = !t.splitk_mid;
-    const int nk = K / X3_BK;
-    if (off || N % 4 != 0) return 1;
-    int best = 1;
-    if (M <= 4 * GEMM_BM) {
-        for (int s = 2; s <= nk / 8; ++s)
-            if (nk % s == 0 && (nk / s) % 2 == 0) best = s;
-        return best;
-    }
-    if (mid_off) return 1;
-    const int tiles = ((M + GEMM_BM - 1) / GEMM_BM) * ((N + GEMM_BN - 1) / GEMM_BN);
-    if (tiles > 256) return 1;
-    for (int s = 2; s <= nk / 16 && tiles * s <= 512; ++s)
-        if (nk % s == 0 && (nk / s) % 2 == 0) best = s;
-    return best;
-}
-// (Tried and removed: cutting only the tiles of the last, partly filled round of a > 512-tile grid into K-slices inside
-//  the same launch, summed by the last piece to arrive at a per-tile counter.  Device-scope fences cost an L2 write-back +
-//  invalidate per piece; with sc1 write-through dumps instead, the dump + arrival + re-read still cost more than the
-//  round they save: 3125 x 3072 x 768: 55 -> 68 us, 25000 x 768 x 3072: 393 -> 440 us.  DESIGN.md section 5.)
-size_t gemm_splitk_ws_bytes(int M, int N, int K, const Tuning &t) {
-    const int s = gemm_splitk_slices(M, N, K, t);
-    size_t b = s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
-    for (int which : {10, 14}) b = std::max(b, pp_splitk_ws_bytes(which, M, N, K));         // (the ping-pong kernels' own split)
-    return b;
-}
-
 int launch_gemm_bf16x3p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                        const GemmEpilogue &epi) {
-    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_bf16x3p: K must be a multiple of 64");
-    CAPDEC_CHECK(epi.packed_out == nullptr ||
-                     (N % 64 == 0 && epi.resid == nullptr && ((uintptr_t)epi.bias & 15) == 0),
-                 "gemm_bf16x3p: packed output needs N % 64 == 0, a 16-byte aligned bias and no residual");
+                        const GemmEpilogue &epi, const GemmPlan &plan) {
+    PackedArgs a;
+    CAPDEC_TRY(packed_args("gemm_bf16x3p", epi, plan, C, ldc, M, N, K, &a));
+    CAPDEC_CHECK(plan.bm == GEMM_BM && plan.bn == GEMM_BN && plan.threads == 256 && !a.sc.kc && !epi.resid_packed,
+                 "gemm_bf16x3p: a plan for the 128 x 128 kernels; no qkv scatter and no packed residual in this format");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
-    // float4 epilogue when every row segment is 16-byte aligned (always the case on the decode path)
-    const bool vec4 = N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
-                      (epi.bias == nullptr || ((uintptr_t)epi.bias & 15) == 0) &&
-                      (epi.resid == nullptr || (epi.ldr % 4 == 0 && ((uintptr_t)epi.resid & 15) == 0));
-    const int S = (vec4 && epi.splitk_ws) ? gemm_splitk_slices(M, N, K, tuning_of(epi)) : 1;
-    if (S > 1 && epi.splitk_ws_bytes >= (size_t)S * M * N * sizeof(float)) {
-        float *part = (float *)epi.splitk_ws;
-        hipLaunchKernelGGL(gemm_bf16x3p_splitk_kernel, dim3(tiles_m * tiles_n * S), dim3(256), 0, st,
-                           (const __bf16 *)Apacked, (const __bf16 *)Bpacked, part, M, N, K, tiles_m, tiles_n, S);
+    const __bf16 *Ap = (const __bf16 *)Apacked, *Bp = (const __bf16 *)Bpacked;
+    if (plan.S > 1) {
+        hipLaunchKernelGGL(gemm_bf16x3p_splitk_kernel, dim3(plan.grid), dim3(256), 0, st, Ap, Bp, a.part, M, N, K, tiles_m,
+                           tiles_n, plan.S);
         CAPDEC_HIP(hipGetLastError());
-        return launch_splitk_reduce(st, part, S, M, N, epi, C, ldc, PK_BF16X3);
+        return launch_splitk_reduce(st, a.part, plan.S, M, N, epi, C, ldc, PK_BF16X3);
     }
-    if (vec4)
-        hipLaunchKernelGGL(gemm_bf16x3p_kernel<true>, dim3(tiles_m * tiles_n), dim3(256), 0, st, (const __bf16 *)Apacked,
-                           (const __bf16 *)Bpacked, C, ldc, M, N, K, epi.bias, epi.resid, epi.ldr, epi.act, tiles_m,
-                           tiles_n, (char *)epi.packed_out);
-    else
-        hipLaunchKernelGGL(gemm_bf16x3p_kernel<false>, dim3(tiles_m * tiles_n), dim3(256), 0, st, (const __bf16 *)Apacked,
-                           (const __bf16 *)Bpacked, C, ldc, M, N, K, epi.bias, epi.resid, epi.ldr, epi.act, tiles_m,
-                           tiles_n, (char *)epi.packed_out);
+    auto go = [&](auto V4) {
+        hipLaunchKernelGGL(gemm_bf16x3p_kernel<decltype(V4)::value>, dim3(plan.grid), dim3(256), 0, st, Ap, Bp, C, ldc, M, N, K,
+                           epi.bias, epi.resid, epi.ldr, epi.act, tiles_m, tiles_n, (char *)epi.packed_out);
+    };
+    if (plan.vec4) go(std::true_type());
+    else go(std::false_type());
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

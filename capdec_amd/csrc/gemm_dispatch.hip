@@ -1,8 +1,9 @@
-// The GEMM planner behind every projection of the path: the cache of packed weight planes, which kernel family and
-// operand format a launch takes in the context's precision mode, the shared epilogue fields and split-K workspace, the
-// LayerNorm -> GEMM and packed-chain forms of the block stack, the fused lm_head (LayerNorm -> GEMM -> per-tile top-k), and
-// capdec_gemm_f32 (the test / micro-benchmark hook onto the same launchers).  Tile geometry and split-K slices are chosen one
-// level down (launch_gemm_f16x2p / pp_plan / h2w_plan) from the shape and the context's Tuning.
+// The GEMM dispatch behind every projection of the path: the cache of packed weight planes, which operand format a launch
+// takes in the context's precision mode, the LayerNorm -> GEMM and packed-chain forms of the block stack, the fused lm_head
+// (LayerNorm -> GEMM -> per-tile top-k), and capdec_gemm_f32 (the test / micro-benchmark hook onto the same launchers).
+// Every packed launch goes through launch_packed, which asks gemm_plan() (gemm_plan.h: a pure host function, tested without
+// a GPU) for the kernel, tile geometry, split-K slices, grid and workspace size, attaches the workspace and hands the plan
+// to the launcher -- nothing about a launch is decided anywhere else.
 #include "context.h"
 
 namespace capdec {
@@ -83,27 +84,40 @@ int planes_of(capdec_ctx *c, const float *W, int N, int K, bool cache, const voi
 
 int gemm_family(int fmt) { return fmt == PK_F16X2 ? F_GEMM_H2P : fmt == PK_BF16X3 ? F_GEMM_X3P : F_GEMM_BF16P; }
 
-int gemm_epilogue(capdec_ctx *c, GemmEpilogue &e, int M, int N, int K, bool split, bool invariant) {
-    e.tune = &c->tune;
-    if (invariant) { e.wide_ok = false; e.invariant = true; }      // (the geometry planners look at M)
-    const size_t wsb = split && !c->batch_invariant ? gemm_splitk_ws_bytes(M, N, K, c->tune) : 0;
-    if (wsb) {
-        CAPDEC_TRY(c->splitk.ensure(wsb));
-        e.splitk_ws = c->splitk.p;
-        e.splitk_ws_bytes = c->splitk.cap;
-    }
-    return 0;
-}
+static_assert(PLAN_BF16X3 == PK_BF16X3 && PLAN_F16X2 == PK_F16X2 && PLAN_BF16X1 == PK_BF16X1 && PLAN_F16X1 == PK_F16X1 &&
+                  PLAN_BK == X3_BK && GEMM_BM == 128 && GEMM_BN == 128,
+              "gemm_plan.h restates these constants");
 
-// C = epilogue(Apk . Bpk^T) with both operands packed in format fmt: two fp16 planes -> f16x2p (whose planner picks among
-// the 128 x 128, wide and ping-pong tiles), three bf16 planes -> bf16x3p, one 16-bit plane -> x1.  flops: what the profiler
-// books for the launch
+// C = epilogue(Apk . Bpk^T) with both operands packed in format fmt.  The ONE place where a packed launch is decided:
+// gemm_plan() turns the shape, what the epilogue asks for and the caller's permissions into a plan (kernel, K slices, blocks,
+// workspace); the workspace is attached here and the launcher of the plan's kernel runs it as it stands.
+// split: the caller lets the launch split K; invariant: batch-invariant mode (the unsplit 128 x 128 kernel whatever M is).
+// flops: what the profiler books for the launch
 static int launch_packed(capdec_ctx *c, int fmt, const void *Apk, const void *Bpk, float *C, int ldc, int M, int N, int K,
-                         const GemmEpilogue &e, double flops) {
+                         GemmEpilogue &e, bool split, bool invariant, double flops) {
+    e.tune = &c->tune;
+    GemmPlanIn in;
+    in.fmt = fmt; in.M = M; in.N = N; in.K = K;
+    in.vec4 = gemm_vec4(e, C, ldc, N);
+    in.wide_ok = e.wide_ok;
+    in.invariant = invariant;
+    in.split_ok = split && !c->batch_invariant;
+    in.packed_out = e.packed_out != nullptr;
+    in.resid_packed = e.resid_packed != nullptr;
+    in.scatter = e.qkv_scatter != nullptr && e.qkv_scatter->kc != nullptr;
+    in.tune = &c->tune;
+    const GemmPlan plan = gemm_plan(in);
+    if (plan.ws_bytes) {
+        CAPDEC_TRY(c->splitk.ensure(plan.ws_bytes));
+        e.splitk_ws = c->splitk.p;
+    }
     ProfScope ps(c, gemm_family(fmt), flops);
-    if (fmt == PK_F16X2) return launch_gemm_f16x2p(c->stream, Apk, Bpk, C, ldc, M, N, K, e);
-    if (fmt == PK_BF16X3) return launch_gemm_bf16x3p(c->stream, Apk, Bpk, C, ldc, M, N, K, e);
-    return launch_gemm_x1(c->stream, Apk, Bpk, C, ldc, M, N, K, e, fmt);
+    switch (plan.kernel) {
+        case GK_H2W: return launch_gemm_h2w(c->stream, Apk, Bpk, C, ldc, M, N, K, e, plan);
+        case GK_PP: case GK_PP_SPLITK: return launch_gemm_pp(c->stream, Apk, Bpk, C, ldc, M, N, K, e, plan);
+        case GK_X3P: case GK_X3P_SPLITK: return launch_gemm_bf16x3p(c->stream, Apk, Bpk, C, ldc, M, N, K, e, plan);
+        default: return launch_gemm_f16x2p(c->stream, Apk, Bpk, C, ldc, M, N, K, e, fmt, plan);      // (two planes or one)
+    }
 }
 
 int gemm_native(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N, int K,
@@ -129,8 +143,8 @@ int gemm(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float
         CAPDEC_TRY(planes_of(c, Bt, N, K, weight, &pl, PK_F16X2, &e.wide_ok));
         CAPDEC_TRY(c->a_tmp.ensure(x3_packed_bytes(M, K, PK_F16X2)));
         { ProfScope ps(c, F_PACK); CAPDEC_TRY(launch_pack_planes_h2(c->stream, A, lda, M, K, c->a_tmp.p)); }
-        CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, /*split=*/true, c->batch_invariant));
-        return launch_packed(c, PK_F16X2, c->a_tmp.p, pl, C, ldc, M, N, K, e, 2.0 * M * (double)N * K);
+        return launch_packed(c, PK_F16X2, c->a_tmp.p, pl, C, ldc, M, N, K, e, /*split=*/true, c->batch_invariant,
+                             2.0 * M * (double)N * K);
     }
     // (bf16 mode: GEMMs whose A operand is fp32 in HBM -- mapper, patch embedding -- keep the split kernel)
     if (c->gemm_mode != GEMM_F32 && ldb == K && K % 64 == 0) {   // other K: native fp32 MFMA
@@ -155,8 +169,8 @@ int gemm_tn(capdec_ctx *c, const float *Xa, int lda, const float *Xb, int ldb, i
         CAPDEC_TRY(launch_pack_planes_h2_t(c->stream, Xb, ldb, rows, N2, Kp, c->x3_tmp.p));
     }
     GemmEpilogue e;
-    CAPDEC_TRY(gemm_epilogue(c, e, N1, N2, Kp, /*split=*/true, c->batch_invariant));
-    return launch_packed(c, PK_F16X2, c->a_tmp.p, c->x3_tmp.p, C, ldc, N1, N2, Kp, e, 2.0 * N1 * (double)N2 * rows);
+    return launch_packed(c, PK_F16X2, c->a_tmp.p, c->x3_tmp.p, C, ldc, N1, N2, Kp, e, /*split=*/true, c->batch_invariant,
+                         2.0 * N1 * (double)N2 * rows);
 }
 
 // LayerNorm -> GEMM with the normalised rows handed over as the packed A operand of the mode (never fp32 in HBM)?
@@ -189,8 +203,7 @@ int gemm_packed(capdec_ctx *c, const void *Apk, const float *W, float *C, int ld
     }
     // (no split-K under the qkv scatter; the one-plane kernels split only under CAPDEC_X1_SPLITK)
     const bool split = c->gemm_mode != GEMM_F32 && !qkv_scatter && (!mode_single(c) || c->tune.x1_splitk);
-    CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, split, c->batch_invariant));
-    return launch_packed(c, pack_fmt(c), Apk, pl, C, ldc, M, N, K, e, 2.0 * M * (double)N * K);
+    return launch_packed(c, pack_fmt(c), Apk, pl, C, ldc, M, N, K, e, split, c->batch_invariant, 2.0 * M * (double)N * K);
 }
 
 // (ln_ready: c->xpk already holds LayerNorm(h) -- written by the fused split-K reduce of the previous GEMM)
@@ -251,12 +264,12 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
             *k3 = k3_ok;
             return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o);
         }
-        return launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o);
+        return launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o, PK_F16X2);
     }
     if (mode_single(c)) {
         ProfScope ps(c, F_LMHEAD_BF16, flops);
         *k3 = k3_ok && M >= 2048 && !c->batch_invariant;      // (as for the wide two-plane tile above)
-        return launch_gemm_x1_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o, pack_fmt(c));
+        return launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o, pack_fmt(c));
     }
     ProfScope ps(c, F_LMHEAD_X3, flops);
     return launch_gemm_bf16x3p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o);
@@ -284,7 +297,7 @@ int gemm_topk(capdec_ctx *c, const void *A, const float *Bt, bool cache, bool b_
         if (topk_wide_tile(c, wide_ok || b_small, M))
             CAPDEC_TRY(launch_gemm_h2w_topk(c->stream, A, pl, M, N, K, k, 1.0f, o));
         else
-            CAPDEC_TRY(launch_gemm_f16x2p_topk(c->stream, A, pl, M, N, K, k, 1.0f, o));
+            CAPDEC_TRY(launch_gemm_f16x2p_topk(c->stream, A, pl, M, N, K, k, 1.0f, o, PK_F16X2));
     } else if (c->gemm_mode != GEMM_F32 && K % 64 == 0) {
         const void *pl = nullptr;
         CAPDEC_TRY(planes_of(c, Bt, N, K, cache, &pl, PK_BF16X3));
@@ -327,12 +340,11 @@ int capdec_gemm_f32(capdec_ctx *c, const float *a, int lda, const float *bt, int
         // (an uncached B keeps the two-accumulator kernels: measuring max |b| costs a reduction and a stream synchronisation
         //  per call -- paid only when a geometry is FORCED, CAPDEC_H2W >= 2: how the parity tests reach the wide tiles)
         if (!cache && fmt == PK_F16X2 && c->tune.h2w >= 2) CAPDEC_TRY(weight_wide_ok(c, bt, (size_t)N * K, &e.wide_ok));
-        // (the hook leaves the geometry planners on in the batch-invariant mode.  Split-K of the one-plane kernels: under
-        //  CAPDEC_HOOK_PACKA the decision of gemm_packed -- CAPDEC_X1_SPLITK -- so that the tests reach gemm_x1_splitk_kernel;
+        // (the hook leaves the planner's geometries on in the batch-invariant mode.  Split-K of the one-plane kernels: under
+        //  CAPDEC_HOOK_PACKA the decision of gemm_packed -- CAPDEC_X1_SPLITK -- so that the tests reach their split kernel;
         //  without the flag, the tools/ micro-benchmarks, never)
         const bool split = !mode_single(c) || (packa && c->tune.x1_splitk);
-        CAPDEC_TRY(gemm_epilogue(c, e, M, N, K, split, /*invariant=*/false));
-        return launch_packed(c, fmt, pa, pb, cc, ldc, M, N, K, e, 2.0 * M * (double)N * K);
+        return launch_packed(c, fmt, pa, pb, cc, ldc, M, N, K, e, split, /*invariant=*/false, 2.0 * M * (double)N * K);
     }
     return gemm(c, a, lda, bt, ldb, cc, ldc, M, N, K, bias, act, resid, ldr, /*weight=*/cache);
 }

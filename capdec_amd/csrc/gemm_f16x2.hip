@@ -26,11 +26,9 @@
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
 #include "gemm_epilogue_lds.h"
+#include "gemm_packed.h"
 
 namespace capdec {
-
-typedef __attribute__((address_space(3))) void lds_void_h;
-typedef const __attribute__((address_space(1))) void glb_void_h;
 
 constexpr int H2_STAGE_B = 2 * H2_BLOCK_B;                 // 16 KB: A block + B block of one k-step
 constexpr int H2_TOPK_LDS = 128 * CT_LD * 4;               // 66 048 B: logits tile of the fused lm_head epilogue
@@ -118,11 +116,6 @@ int launch_pack_planes_h2_t(hipStream_t st, const float *src, int ld, int rows, 
     return 0;
 }
 
-// s_waitcnt immediate (gfx9 encoding): vmcnt(N) expcnt(none) lgkmcnt(L: 0 = wait for all, 15 = do not wait)
-__host__ __device__ constexpr int waitcnt_imm(int vm, int lgkm) {
-    return (vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14);
-}
-
 // TR: MFMA operands swapped (D^T), a lane ends with four consecutive columns of one row (see gemm_bf16x3.hip).
 // am = sum hi_a hi_b, ac = sum (hi_a lo_b + lo_a hi_b) (weight 2^-11, applied by h2_join).
 // KIND: 0 = f16x2 (the fp32-accurate scheme above).  1 / 2 = ONE-plane fp16 / bf16 operands (formats PK_F16X1 /
@@ -186,8 +179,8 @@ __device__ __forceinline__ void h2p_mainloop(const _Float16 *__restrict__ Apk, c
             const char *sa = cv_cur + (size_t)cv_cs * H2_BLOCK_B;                                              \
             const _Float16 *sb = bp + (size_t)cv_ks * (H2_BLOCK_B / 2);                                        \
             _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                    \
-                __builtin_amdgcn_global_load_lds((glb_void_h *)(sa + p * X3_PLANE_B), (lds_void_h *)(d + p * X3_PLANE_B), 16, 0, 0); \
-                __builtin_amdgcn_global_load_lds((glb_void_h *)(sb + p * 2048), (lds_void_h *)(d + H2_BLOCK_B + p * X3_PLANE_B), 16, 0, 0); \
+                __builtin_amdgcn_global_load_lds((glb_void *)(sa + p * X3_PLANE_B), (lds_void *)(d + p * X3_PLANE_B), 16, 0, 0); \
+                __builtin_amdgcn_global_load_lds((glb_void *)(sb + p * 2048), (lds_void *)(d + H2_BLOCK_B + p * X3_PLANE_B), 16, 0, 0); \
             }                                                                                                  \
             if (cv_ks < nk - 1) {                                                                              \
                 ++cv_ks;                                                                                       \
@@ -196,8 +189,8 @@ __device__ __forceinline__ void h2p_mainloop(const _Float16 *__restrict__ Apk, c
         } else {                                                                                               \
             const _Float16 *sa = ap + (size_t)(ks_) * (H2_BLOCK_B / 2), *sb = bp + (size_t)(ks_) * (H2_BLOCK_B / 2); \
             _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                    \
-                __builtin_amdgcn_global_load_lds((glb_void_h *)(sa + p * 2048), (lds_void_h *)(d + p * X3_PLANE_B), 16, 0, 0); \
-                __builtin_amdgcn_global_load_lds((glb_void_h *)(sb + p * 2048), (lds_void_h *)(d + H2_BLOCK_B + p * X3_PLANE_B), 16, 0, 0); \
+                __builtin_amdgcn_global_load_lds((glb_void *)(sa + p * 2048), (lds_void *)(d + p * X3_PLANE_B), 16, 0, 0); \
+                __builtin_amdgcn_global_load_lds((glb_void *)(sb + p * 2048), (lds_void *)(d + H2_BLOCK_B + p * X3_PLANE_B), 16, 0, 0); \
             }                                                                                                  \
         }                                                                                                      \
     }
@@ -316,15 +309,15 @@ __device__ __forceinline__ void h2_join(f32x16 (&am)[2][2], const f32x16 (&ac)[2
 constexpr int H2_NS = 4;
 // wave grid of the 128 x 128 kernels for the coalesced epilogues (gemm_epilogue_lds.h): 2 x 2 wavefronts of 64 x 64
 struct H2Tile { static constexpr int WN = 2, TI = 2, TJ = 2; };
-// end of a persistent block's tile: the next tile's LDS-DMA pieces land in the epilogue's slabs
-__device__ __forceinline__ void h2_slab_release(bool more) {
-    if (more) {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    }
+
+// f(std::integral_constant<int, KIND>()) for the KIND of a runtime operand format (the caller has checked the format)
+template <class F>
+inline void with_kind(int fmt, F &&f) {
+    if (fmt == PK_F16X2) f(std::integral_constant<int, 0>());
+    else if (fmt == PK_F16X1) f(std::integral_constant<int, 1>());
+    else f(std::integral_constant<int, 2>());
 }
+
 __device__ __forceinline__ EpiArgs h2_epi_args(float *C, int ldc, int M, int N, int m0, int n0, const float *bias,
                                                const float *resid, int ldr, int act, char *packed_out, int fmt,
                                                const QkvScatter *sc) {
@@ -338,6 +331,8 @@ __device__ __forceinline__ EpiArgs h2_epi_args(float *C, int ldc, int M, int N, 
     return ea;
 }
 
+// (gemm_f16x2p_kernel and gemm_x1_kernel stay two kernels: a one-plane launch also names its output format, and sharing
+//  their text through one device function changed the code the compiler emits for them)
 template <bool VEC4, int NS>
 __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__restrict__ Apk,
                                                              const _Float16 *__restrict__ Bpk, float *C, int ldc, int M,
@@ -345,10 +340,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__r
                                                              const float *resid, int ldr, int act, int tiles_m,
                                                              int tiles_n, char *packed_out, QkvScatter sc) {
     __shared__ __attribute__((aligned(16))) char smem[NS * H2_STAGE_B];
-    // Persistent form: the launch has min(tiles, 512) blocks (two per CU) and block b walks tiles b, b + grid, ...  The
-    // hardware hands the blocks of a launch out breadth-first (one per CU, then the second slots), so the tiles of a
-    // partly filled last round are taken one per CU by blocks that by then have the CU to themselves -- where one block
-    // per tile lets the dispatcher put the leftovers two to a CU as slots free up (600 tiles: 2 x 37 us instead of
+    // Persistent form: the launch has min(tiles, slots) blocks (two per CU: gemm_plan.h) and block b walks tiles b,
+    // b + grid, ...  The hardware hands the blocks of a launch out breadth-first (one per CU, then the second slots), so the
+    // tiles of a partly filled last round are taken one per CU by blocks that by then have the CU to themselves -- where one
+    // block per tile lets the dispatcher put the leftovers two to a CU as slots free up (600 tiles: 2 x 37 us instead of
     // 37 + 15).  grid % 8 == 0 keeps a block's tiles on its own XCD's slice of the tile order.
     const int ntiles = tiles_m * tiles_n;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -362,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__r
             // (<.., true>: the tile's bias and residual quads are requested before the transposition -- the cross-term
             //  accumulators are dead after h2_join, their registers hold the 16 residual quads; gemm_epilogue_lds.h)
             epilogue_lds<H2Tile, true>(am, smem, ea);
-            h2_slab_release(tile + (int)gridDim.x < ntiles);
+            slab_release(tile + (int)gridDim.x < ntiles);
         } else if (packed_out) {
             epilogue_store_packed_t(am, packed_out, N >> 4, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, act, PK_F16X2,
                                     reinterpret_cast<const char *>(resid));  // (with packed_out, `resid` is a PACKED residual)
@@ -372,111 +367,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2p_kernel(const _Float16 *__r
     }
 }
 
-template <int KSEL>
-__global__ __launch_bounds__(256, 2) void gemm_f16x2p_topk_kernel(const _Float16 *__restrict__ Apk,
-                                                                  const _Float16 *__restrict__ Bpk, int M, int N, int K,
-                                                                  float inv_temp, float *tile_max, float *tile_sum,
-                                                                  float *cand_val, int *cand_idx, int tiles_m,
-                                                                  int tiles_n) {
-    __shared__ __attribute__((aligned(16))) char smem[H2Geo<H2_NS>::SMEM_B];
-    int tm, tn;
-    tile_coords(tiles_m, tiles_n, tm, tn);
-    f32x16 am[2][2], ac[2][2];
-    h2p_mainloop<false, H2_NS>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier
-    h2_join(am, ac);
-    epilogue_topk<KSEL, 2, true>(am, reinterpret_cast<float *>(smem), M, N, tm * GEMM_BM, tn * GEMM_BN, tn, tiles_n, inv_temp,
-                                 tile_max, tile_sum, cand_val, cand_idx);
-}
-
-// split-K for under-filled grids: raw fp32 partial tiles to a workspace [S][M][N], summed in a fixed order by
-// splitk_reduce_kernel (gemm_bf16x3.hip), which also applies the epilogue
-__global__ __launch_bounds__(256, 2) void gemm_f16x2p_splitk_kernel(const _Float16 *__restrict__ Apk,
-                                                                    const _Float16 *__restrict__ Bpk, float *part, int M,
-                                                                    int N, int K, int tiles_m, int tiles_n, int S) {
-    __shared__ __attribute__((aligned(16))) char smem[H2_NS * H2_STAGE_B];
-    const int ntiles = tiles_m * tiles_n;
-    const int slice = blockIdx.x / ntiles;
-    int tm, tn;
-    tile_coords(tiles_m, tiles_n, tm, tn, blockIdx.x - slice * ntiles);
-    const int nks = K / X3_BK / S;
-    f32x16 am[2][2], ac[2][2];
-    h2p_mainloop<true, H2_NS>(Apk, Bpk, K, tm, tn, smem, am, ac, slice * nks, nks);
-    h2_join(am, ac);
-    const EpiArgs ea = h2_epi_args(part + (size_t)slice * M * N, N, M, N, tm * GEMM_BM, tn * GEMM_BN, nullptr, nullptr, 0,
-                                   CAPDEC_ACT_NONE, nullptr, PK_F16X2, nullptr);
-    epilogue_lds_wave<2, 2, 0, CAPDEC_ACT_NONE>(am, reinterpret_cast<float *>(smem + (threadIdx.x >> 6) * EpiSlab<2>::BYTES),
-                                                ea.m0 + (threadIdx.x >> 7) * 64, ea.n0 + ((threadIdx.x >> 6) & 1) * 64, ea);
-}
-
-int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                       const GemmEpilogue &epi) {
-    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_f16x2p: K must be a multiple of 64");
-    CAPDEC_CHECK(epi.packed_out == nullptr ||
-                     (N % 64 == 0 && epi.resid == nullptr && ((uintptr_t)epi.bias & 15) == 0),
-                 "gemm_f16x2p: packed output needs N % 64 == 0, a 16-byte aligned bias and no residual");
-    const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
-    const bool vec4 = N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
-                      (epi.bias == nullptr || ((uintptr_t)epi.bias & 15) == 0) &&
-                      (epi.resid == nullptr || (epi.ldr % 4 == 0 && ((uintptr_t)epi.resid & 15) == 0));
-    CAPDEC_CHECK(epi.resid_packed == nullptr || epi.packed_out != nullptr, "gemm_f16x2p: a packed residual needs a packed output");
-    const float *resid_arg = epi.packed_out ? (const float *)epi.resid_packed : epi.resid;
-    const QkvScatter sc = epi.qkv_scatter ? *epi.qkv_scatter : QkvScatter();
-    CAPDEC_CHECK(!sc.kc || (vec4 && epi.bias && !epi.resid && !epi.packed_out && epi.act == CAPDEC_ACT_NONE && N == 3 * sc.d &&
-                            sc.d % GEMM_BN == 0 && !epi.splitk_ws),
-                 "gemm_f16x2p: the qkv scatter epilogue needs an unsplit, biased, plain [M, 3d] projection");
-    const Tuning &tn = tuning_of(epi);
-    // round-4 ping-pong kernels (gemm_pp.hip): forced (CAPDEC_H2W >= 10) or where the planner expects a gain from them
-    // (mid-size launches; the small-batch regime M <= 512 keeps its batch-size independent split-K)
-    if (vec4 && !epi.invariant) {
-        const bool can_split = epi.splitk_ws && !epi.resid_packed && !epi.packed_out && !sc.kc;
-        int which = 0;
-        if (tn.h2w >= 10) which = (tn.h2w == 10 || epi.wide_ok) ? tn.h2w : 0;
-        else if (tn.h2w == 1 && tn.pp && M > 4 * GEMM_BM) which = pp_plan(M, N, K, epi.wide_ok, can_split);
-        if (which) return launch_gemm_pp(st, which, Apacked, Bpacked, C, ldc, M, N, K, epi, 1.0f / H2_LO_SCALE);
-    }
-    const int S = (vec4 && epi.splitk_ws && !epi.resid_packed) ? gemm_splitk_slices(M, N, K, tn) : 1;
-    if (S > 1 && epi.splitk_ws_bytes >= (size_t)S * M * N * sizeof(float)) {
-        float *part = (float *)epi.splitk_ws;
-        hipLaunchKernelGGL(gemm_f16x2p_splitk_kernel, dim3(tiles_m * tiles_n * S), dim3(256), 0, st,
-                           (const _Float16 *)Apacked, (const _Float16 *)Bpacked, part, M, N, K, tiles_m, tiles_n, S);
-        CAPDEC_HIP(hipGetLastError());
-        return launch_splitk_reduce(st, part, S, M, N, epi, C, ldc, PK_F16X2);
-    }
-    if (vec4 && epi.wide_ok && tn.h2w >= 1 && tn.h2w < 10 && !sc.kc) {      // round-3 single-accumulator geometries where they remove a round
-        const int which = tn.h2w >= 2 ? tn.h2w : h2w_plan(M, N, K);
-        if (which) return launch_gemm_h2w(st, which, Apacked, Bpacked, C, ldc, M, N, K, epi, 1.0f / H2_LO_SCALE);
-    }
-    // persistent form for grids of up to four rounds, where the partly filled last round matters (625 captions: mlp.c_fc
-    // 600 tiles, 80 -> 70 us inside the decode loop); larger grids keep one block per tile (the dispatcher balances them:
-    // within noise either way at 25 000 rows).  CAPDEC_H2_PERSIST=<blocks> (0 = never)
-    const int persist = tn.h2_persist;
-    const int grid_h2 = (persist > 0 && tiles_m * tiles_n <= 4 * persist) ? std::min(tiles_m * tiles_n, persist) : tiles_m * tiles_n;
-#define LAUNCH_H2(V4, NSV)                                                                                            \
-    hipLaunchKernelGGL((gemm_f16x2p_kernel<V4, NSV>), dim3(grid_h2), dim3(256), 0, st, (const _Float16 *)Apacked, \
-                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, resid_arg, epi.ldr, epi.act, tiles_m,      \
-                       tiles_n, (char *)epi.packed_out, sc)
-    if (vec4) LAUNCH_H2(true, H2_NS);
-    else LAUNCH_H2(false, H2_NS);
-#undef LAUNCH_H2
-    CAPDEC_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                            float inv_temp, const TopkOut &o) {
-    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_f16x2p_topk: K must be a multiple of 64");
-    const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
-    dim3 grid(tiles_m * tiles_n), block(256);
-    CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
-        hipLaunchKernelGGL(gemm_f16x2p_topk_kernel<KS>, grid, block, 0, st, (const _Float16 *)Apacked,
-                           (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
-                           tiles_m, tiles_n);
-    }));
-    CAPDEC_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- one-plane (reduced-precision) kernels on the same main loop: KIND 1 = fp16 operands, 2 = bf16 operands
+// one-plane (reduced-precision) operands on the same main loop: KIND 1 = fp16, 2 = bf16
 // (NS = 4: 64 KB, two blocks per CU; NS = 3: 48 KB and <= 168 registers, THREE blocks per CU -- the vec4 form)
 template <bool VEC4, int KIND, int NS>
 __global__ __launch_bounds__(256, (NS == 3 ? 3 : 2)) void gemm_x1_kernel(const _Float16 *__restrict__ Apk, const _Float16 *__restrict__ Bpk,
@@ -494,7 +385,7 @@ __global__ __launch_bounds__(256, (NS == 3 ? 3 : 2)) void gemm_x1_kernel(const _
         if constexpr (VEC4) {
             const EpiArgs ea = h2_epi_args(C, ldc, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, resid, ldr, act, packed_out, out_fmt, &sc);
             epilogue_lds<H2Tile>(am, smem, ea);
-            h2_slab_release(tile + (int)gridDim.x < ntiles);
+            slab_release(tile + (int)gridDim.x < ntiles);
         } else if (packed_out) {
             epilogue_store_packed_t(am, packed_out, N >> 4, M, N, tm * GEMM_BM, tn * GEMM_BN, bias, act, out_fmt,
                                     reinterpret_cast<const char *>(resid));  // (with packed_out, `resid` is a PACKED residual)
@@ -505,17 +396,40 @@ __global__ __launch_bounds__(256, (NS == 3 ? 3 : 2)) void gemm_x1_kernel(const _
 }
 
 template <int KSEL, int KIND>
-__global__ __launch_bounds__(256, 2) void gemm_x1_topk_kernel(const _Float16 *__restrict__ Apk,
-                                                              const _Float16 *__restrict__ Bpk, int M, int N, int K,
-                                                              float inv_temp, float *tile_max, float *tile_sum,
-                                                              float *cand_val, int *cand_idx, int tiles_m, int tiles_n) {
+__global__ __launch_bounds__(256, 2) void gemm_f16x2p_topk_kernel(const _Float16 *__restrict__ Apk,
+                                                                  const _Float16 *__restrict__ Bpk, int M, int N, int K,
+                                                                  float inv_temp, float *tile_max, float *tile_sum,
+                                                                  float *cand_val, int *cand_idx, int tiles_m,
+                                                                  int tiles_n) {
     __shared__ __attribute__((aligned(16))) char smem[H2Geo<H2_NS>::SMEM_B];
     int tm, tn;
     tile_coords(tiles_m, tiles_n, tm, tn);
     f32x16 am[2][2], ac[2][2];
     h2p_mainloop<false, H2_NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac);      // ends with a barrier
+    if constexpr (KIND == 0) h2_join(am, ac);
     epilogue_topk<KSEL, 2, true>(am, reinterpret_cast<float *>(smem), M, N, tm * GEMM_BM, tn * GEMM_BN, tn, tiles_n, inv_temp,
                                  tile_max, tile_sum, cand_val, cand_idx);
+}
+
+// split-K for under-filled grids: raw fp32 partial tiles to a workspace [S][M][N], summed in a fixed order by
+// splitk_reduce_kernel (gemm_bf16x3.hip), which also applies the epilogue
+template <int KIND>
+__global__ __launch_bounds__(256, 2) void gemm_f16x2p_splitk_kernel(const _Float16 *__restrict__ Apk,
+                                                                    const _Float16 *__restrict__ Bpk, float *part, int M,
+                                                                    int N, int K, int tiles_m, int tiles_n, int S) {
+    __shared__ __attribute__((aligned(16))) char smem[H2_NS * H2_STAGE_B];
+    const int ntiles = tiles_m * tiles_n;
+    const int slice = blockIdx.x / ntiles;
+    int tm, tn;
+    tile_coords(tiles_m, tiles_n, tm, tn, blockIdx.x - slice * ntiles);
+    const int nks = K / (KIND == 0 ? X3_BK : 2 * X3_BK) / S;      // stages of this slice (one-plane: two k-steps each)
+    f32x16 am[2][2], ac[2][2];
+    h2p_mainloop<true, H2_NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac, slice * nks, nks);
+    if constexpr (KIND == 0) h2_join(am, ac);
+    const EpiArgs ea = h2_epi_args(part + (size_t)slice * M * N, N, M, N, tm * GEMM_BM, tn * GEMM_BN, nullptr, nullptr, 0,
+                                   CAPDEC_ACT_NONE, nullptr, PK_F16X2, nullptr);
+    epilogue_lds_wave<2, 2, 0, CAPDEC_ACT_NONE>(am, reinterpret_cast<float *>(smem + (threadIdx.x >> 6) * EpiSlab<2>::BYTES),
+                                                ea.m0 + (threadIdx.x >> 7) * 64, ea.n0 + ((threadIdx.x >> 6) & 1) * 64, ea);
 }
 
 // the same kernel (k = 5) over *m_dev rows of a compacted A operand: the exact second pass of the fused lm_head in the
@@ -555,94 +469,56 @@ int launch_gemm_x1_topk_dev(hipStream_t st, const void *Apacked, const void *Bpa
     return 0;
 }
 
-// split-K of the one-plane kernels (same regimes and reduce pass as the two-plane kernel: gemm_splitk_slices)
-template <int KIND>
-__global__ __launch_bounds__(256, 2) void gemm_x1_splitk_kernel(const _Float16 *__restrict__ Apk,
-                                                                const _Float16 *__restrict__ Bpk, float *part, int M, int N,
-                                                                int K, int tiles_m, int tiles_n, int S) {
-    __shared__ __attribute__((aligned(16))) char smem[H2_NS * H2_STAGE_B];
-    const int ntiles = tiles_m * tiles_n;
-    const int slice = blockIdx.x / ntiles;
-    int tm, tn;
-    tile_coords(tiles_m, tiles_n, tm, tn, blockIdx.x - slice * ntiles);
-    const int nks = K / (2 * X3_BK) / S;                 // stages (two k-steps each) of this slice
-    f32x16 am[2][2], ac[2][2];
-    h2p_mainloop<true, H2_NS, KIND>(Apk, Bpk, K, tm, tn, smem, am, ac, slice * nks, nks);
-    const EpiArgs ea = h2_epi_args(part + (size_t)slice * M * N, N, M, N, tm * GEMM_BM, tn * GEMM_BN, nullptr, nullptr, 0,
-                                   CAPDEC_ACT_NONE, nullptr, PK_F16X2, nullptr);
-    epilogue_lds_wave<2, 2, 0, CAPDEC_ACT_NONE>(am, reinterpret_cast<float *>(smem + (threadIdx.x >> 6) * EpiSlab<2>::BYTES),
-                                                ea.m0 + (threadIdx.x >> 7) * 64, ea.n0 + ((threadIdx.x >> 6) & 1) * 64, ea);
-}
-
-// fmt = PK_F16X1 or PK_BF16X1 (both operands; a packed output is written in the same format)
-int launch_gemm_x1(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                   const GemmEpilogue &epi, int fmt) {
-    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_x1: K must be a multiple of 64");
-    CAPDEC_CHECK(fmt == PK_F16X1 || fmt == PK_BF16X1, "gemm_x1: one-plane operand formats only");
-    CAPDEC_CHECK(epi.packed_out == nullptr ||
-                     (N % 64 == 0 && epi.resid == nullptr && ((uintptr_t)epi.bias & 15) == 0),
-                 "gemm_x1: packed output needs N % 64 == 0, a 16-byte aligned bias and no residual");
+// ---- launchers of the 128 x 128 kernels: what runs (kernel, slices, blocks) is the plan's decision (gemm_plan.h).
+// fmt = PK_F16X2, or a one-plane format (both operands; a packed output is written in the same format)
+int launch_gemm_f16x2p(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
+                       const GemmEpilogue &epi, int fmt, const GemmPlan &plan) {
+    CAPDEC_CHECK(fmt == PK_F16X2 || fmt == PK_F16X1 || fmt == PK_BF16X1, "gemm_f16x2p: two fp16 planes or a one-plane format");
+    const std::string who = fmt == PK_F16X2 ? "gemm_f16x2p" : "gemm_x1";
+    PackedArgs a;
+    CAPDEC_TRY(packed_args(who, epi, plan, C, ldc, M, N, K, &a));
+    CAPDEC_CHECK(plan.bm == GEMM_BM && plan.bn == GEMM_BN && plan.threads == 256, who + ": not a plan for the 128 x 128 kernels");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
-    const bool vec4 = N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
-                      (epi.bias == nullptr || ((uintptr_t)epi.bias & 15) == 0) &&
-                      (epi.resid == nullptr || (epi.ldr % 4 == 0 && ((uintptr_t)epi.resid & 15) == 0));
-    // (Round 5 measured the ping-pong tiles of gemm_pp.hip under one-plane operands -- 256 x 256 / 256 x 192 / 256 x 128,
-    //  rings of 4-5 and of 5-6 stages -- against this kernel inside the decode loop: 12-15 % SLOWER per launch at 5000 rows,
-    //  25 % at 25 000 (profiles/r5_x1_pingpong_ab.txt); the variant was removed again.)
-    const QkvScatter sc = epi.qkv_scatter ? *epi.qkv_scatter : QkvScatter();
-    CAPDEC_CHECK(!sc.kc || (vec4 && epi.bias && !epi.resid && !epi.packed_out && epi.act == CAPDEC_ACT_NONE && N == 3 * sc.d &&
-                            sc.d % GEMM_BN == 0 && !epi.splitk_ws),
-                 "gemm_x1: the qkv scatter epilogue needs an unsplit, biased, plain [M, 3d] projection");
-    {
-        int S = (vec4 && epi.splitk_ws && !epi.resid_packed) ? gemm_splitk_slices(M, N, K, tuning_of(epi)) : 1;
-        if (S > 1 && ((K / X3_BK / S) % 4 != 0 || epi.splitk_ws_bytes < (size_t)S * M * N * sizeof(float))) S = 1;
-        if (S > 1) {     // a slice is a whole, even number of two-k-step stages
-            float *part = (float *)epi.splitk_ws;
-            if (fmt == PK_F16X1)
-                hipLaunchKernelGGL(gemm_x1_splitk_kernel<1>, dim3(tiles_m * tiles_n * S), dim3(256), 0, st,
-                                   (const _Float16 *)Apacked, (const _Float16 *)Bpacked, part, M, N, K, tiles_m, tiles_n, S);
-            else
-                hipLaunchKernelGGL(gemm_x1_splitk_kernel<2>, dim3(tiles_m * tiles_n * S), dim3(256), 0, st,
-                                   (const _Float16 *)Apacked, (const _Float16 *)Bpacked, part, M, N, K, tiles_m, tiles_n, S);
-            CAPDEC_HIP(hipGetLastError());
-            return launch_splitk_reduce(st, part, S, M, N, epi, C, ldc, fmt);
-        }
+    const _Float16 *Ap = (const _Float16 *)Apacked, *Bp = (const _Float16 *)Bpacked;
+    const dim3 grid(plan.grid), block(plan.threads);
+    if (plan.S > 1) {
+        with_kind(fmt, [&](auto KD) {
+            hipLaunchKernelGGL(gemm_f16x2p_splitk_kernel<decltype(KD)::value>, grid, block, 0, st, Ap, Bp, a.part, M, N, K,
+                               tiles_m, tiles_n, plan.S);
+        });
+        CAPDEC_HIP(hipGetLastError());
+        return launch_splitk_reduce(st, a.part, plan.S, M, N, epi, C, ldc, fmt);
     }
-    // vec4: ring of 3, three blocks per CU (measured +3 % at 25 000 rows, +1.3 % on the greedy bf16 workload against two)
-    // persistent blocks for grids of up to four rounds (768 slots with three blocks per CU, 512 with two)
-    const int persist = tuning_of(epi).h2_persist;
-    const int slots = persist > 0 ? (vec4 ? persist * 3 / 2 : persist) : 0;
-    const int grid_x1 = (slots > 0 && tiles_m * tiles_n <= 4 * slots) ? std::min(tiles_m * tiles_n, slots) : tiles_m * tiles_n;
-#define LAUNCH_X1V(V4, KD, NSV)                                                                                         \
-    hipLaunchKernelGGL((gemm_x1_kernel<V4, KD, NSV>), dim3(grid_x1), dim3(256), 0, st, (const _Float16 *)Apacked, \
-                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias,                                           \
-                       epi.packed_out ? (const float *)epi.resid_packed : epi.resid, epi.ldr, epi.act, tiles_m,       \
-                       tiles_n, (char *)epi.packed_out, fmt, sc)
-#define LAUNCH_X1K(KD)                                                                        \
-    if (vec4) LAUNCH_X1V(true, KD, 3);                                                        \
-    else LAUNCH_X1V(false, KD, 4)
-    if (fmt == PK_F16X1) { LAUNCH_X1K(1); } else { LAUNCH_X1K(2); }
-#undef LAUNCH_X1K
-#undef LAUNCH_X1V
+    with_kind(fmt, [&](auto KD) {
+        constexpr int kind = decltype(KD)::value;
+        auto go = [&](auto V4) {
+            constexpr bool v4 = decltype(V4)::value;
+            if constexpr (kind == 0)
+                hipLaunchKernelGGL((gemm_f16x2p_kernel<v4, H2_NS>), grid, block, 0, st, Ap, Bp, C, ldc, M, N, K, epi.bias, a.resid,
+                                   epi.ldr, epi.act, tiles_m, tiles_n, (char *)epi.packed_out, a.sc);
+            else      // (a packed output is written in the operands' format)
+                hipLaunchKernelGGL((gemm_x1_kernel<v4, kind, (v4 ? 3 : H2_NS)>), grid, block, 0, st, Ap, Bp, C, ldc, M, N, K,
+                                   epi.bias, a.resid, epi.ldr, epi.act, tiles_m, tiles_n, (char *)epi.packed_out, fmt, a.sc);
+        };
+        if (plan.vec4) go(std::true_type());
+        else go(std::false_type());
+    });
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_gemm_x1_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
-                        float inv_temp, const TopkOut &o, int fmt) {
-    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_x1_topk: K must be a multiple of 64");
-    CAPDEC_CHECK(fmt == PK_F16X1 || fmt == PK_BF16X1, "gemm_x1_topk: one-plane operand formats only");
+int launch_gemm_f16x2p_topk(hipStream_t st, const void *Apacked, const void *Bpacked, int M, int N, int K, int k,
+                            float inv_temp, const TopkOut &o, int fmt) {
+    CAPDEC_CHECK(fmt == PK_F16X2 || fmt == PK_F16X1 || fmt == PK_BF16X1, "gemm_f16x2p_topk: two fp16 planes or a one-plane format");
+    CAPDEC_CHECK(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_f16x2p_topk: K must be a multiple of 64");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid(tiles_m * tiles_n), block(256);
     CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
-        if (fmt == PK_F16X1)
-            hipLaunchKernelGGL((gemm_x1_topk_kernel<KS, 1>), grid, block, 0, st, (const _Float16 *)Apacked,
-                               (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
-                               tiles_m, tiles_n);
-        else
-            hipLaunchKernelGGL((gemm_x1_topk_kernel<KS, 2>), grid, block, 0, st, (const _Float16 *)Apacked,
-                               (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
-                               tiles_m, tiles_n);
+        with_kind(fmt, [&](auto KD) {
+            hipLaunchKernelGGL((gemm_f16x2p_topk_kernel<decltype(KS)::value, decltype(KD)::value>), grid, block, 0, st,
+                               (const _Float16 *)Apacked, (const _Float16 *)Bpacked, M, N, K, inv_temp, o.tile_max, o.tile_sum,
+                               o.cand_val, o.cand_idx, tiles_m, tiles_n);
+        });
     }));
     CAPDEC_HIP(hipGetLastError());
     return 0;
@@ -682,17 +558,13 @@ int launch_conv3x3_packed(hipStream_t st, const void *act_pk, const void *Bpacke
     CAPDEC_CHECK(zeros && zero_bytes >= (size_t)(cg.ncs + 1) * H2_BLOCK_B, "conv3x3: zero block too small");
     CAPDEC_CHECK(epi.packed_out == nullptr || (N % 64 == 0 && epi.resid == nullptr && ((uintptr_t)epi.bias & 15) == 0),
                  "conv3x3: packed output needs Cout % 64 == 0, a 16-byte aligned bias and no residual");
-    CAPDEC_CHECK(epi.packed_out != nullptr ||
-                     (ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 && (epi.bias == nullptr || ((uintptr_t)epi.bias & 15) == 0) &&
-                      (epi.resid == nullptr || (epi.ldr % 4 == 0 && ((uintptr_t)epi.resid & 15) == 0))),
-                 "conv3x3: 16-byte aligned output rows, bias and residual");
+    CAPDEC_CHECK(epi.packed_out != nullptr || gemm_vec4(epi, C, ldc, N), "conv3x3: 16-byte aligned output rows, bias and residual");
     const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
-#define LAUNCH_CONV(KD)                                                                                                  \
-    hipLaunchKernelGGL((conv3x3_packed_kernel<KD>), dim3(tiles_m * tiles_n), dim3(256), 0, st, (const _Float16 *)act_pk,   \
-                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, epi.resid, epi.ldr, epi.act, tiles_m, tiles_n, \
-                       (char *)epi.packed_out, fmt, cg)
-    if (fmt == PK_F16X2) LAUNCH_CONV(0); else if (fmt == PK_F16X1) LAUNCH_CONV(1); else LAUNCH_CONV(2);
-#undef LAUNCH_CONV
+    with_kind(fmt, [&](auto KD) {
+        hipLaunchKernelGGL(conv3x3_packed_kernel<decltype(KD)::value>, dim3(tiles_m * tiles_n), dim3(256), 0, st,
+                           (const _Float16 *)act_pk, (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, epi.resid, epi.ldr,
+                           epi.act, tiles_m, tiles_n, (char *)epi.packed_out, fmt, cg);
+    });
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

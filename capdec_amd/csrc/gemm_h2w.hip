@@ -28,15 +28,9 @@
 #include "bf16x3.h"
 #include "gemm_epilogue_lds.h"
 #include "gemm_epilogue_w.h"
+#include "gemm_packed.h"
 
 namespace capdec {
-
-typedef __attribute__((address_space(3))) void lds_void_w;
-typedef const __attribute__((address_space(1))) void glb_void_w;
-
-__host__ __device__ constexpr int waitcnt_imm_w(int vm, int lgkm) {
-    return (vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14);
-}
 
 template <int WM_, int WN_, int TI_, int TJ_, int NS_, int MINW_>
 struct WGeo {
@@ -117,8 +111,8 @@ __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, c
 #define W_DMA(stage, ks_, e0, e1)                                                                               \
     {                                                                                                           \
         _Pragma("unroll") for (int e = (e0); e < (e1); ++e)                                                     \
-            __builtin_amdgcn_global_load_lds((glb_void_w *)(src[e] + (size_t)(ks_) * H2_BLOCK_B),                \
-                                             (lds_void_w *)(dst0 + (stage) * SB + e * 1024), 16, 0, 0);         \
+            __builtin_amdgcn_global_load_lds((glb_void *)(src[e] + (size_t)(ks_) * H2_BLOCK_B),                \
+                                             (lds_void *)(dst0 + (stage) * SB + e * 1024), 16, 0, 0);         \
     }
 #pragma unroll
     for (int i = 0; i < TI; ++i)
@@ -155,7 +149,7 @@ __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, c
     _Pragma("unroll") for (int j = 0; j < TJ; ++j) acc[i][j] = W_MM(F##a[i][0], F##b[j][1], acc[i][j]);
 #define W_SYNC()                                                                       \
     asm volatile("" ::: "memory");                                                     \
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm_w(PPW * (NS - 2), 0));                      \
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW * (NS - 2), 0));                      \
     __builtin_amdgcn_s_barrier();                                                      \
     asm volatile("" ::: "memory");                                                     \
     __builtin_amdgcn_sched_barrier(0);     /* (the next k-step's MFMAs only read registers: keep them behind the barrier) */
@@ -183,7 +177,7 @@ __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, c
     // prologue: tiles 0 .. NS-1 in flight (stage s <- tile s); tile 0 landed -> fragment set f0; tile 1 landed
 #pragma unroll
     for (int s = 0; s < NS; ++s) W_DMA(s, min(s, nk - 1), 0, PPW)
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm_w(PPW * (NS - 1), 15));
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW * (NS - 1), 15));
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     W_READ_B(f0, 0)
@@ -200,7 +194,7 @@ __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, c
         W_STEP(f1, f0, s2, s1, min(kt + 1 + NS, nk - 1))
         s0 = s2;
     }
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm_w(0, 15));            // clamped tail pieces must land before LDS is reused
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 15));            // clamped tail pieces must land before LDS is reused
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 #undef W_DMA
@@ -236,12 +230,7 @@ __global__ __launch_bounds__(G::THREADS, G::MINW) void gemm_h2w_kernel(const _Fl
         if (packed_out) ea.resid_pk = reinterpret_cast<const char *>(resid);      // (with packed_out, `resid` is PACKED)
         else ea.resid = resid;
         epilogue_lds<G>(acc, smem, ea);
-        if (tile + (int)gridDim.x < ntiles) {       // the next tile's DMA pieces land in the slabs
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt(waitcnt_imm_w(63, 0));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
+        slab_release(tile + (int)gridDim.x < ntiles);
     }
 }
 
@@ -306,53 +295,30 @@ int launch_absmax_bits(hipStream_t st, const float *w, size_t n, unsigned *d_out
     return 0;
 }
 
-// Which kernel for an f16x2 GEMM [M, N, K] whose grid is not split along K: 0 = the round-2 128x128 two-accumulator
-// kernel, else a WGeo id of launch_gemm_h2w.  Estimated time = (full rounds of 512 blocks + what the partly filled last
-// round costs) x tile area / relative loop efficiency; a block alone on its CU runs ~1.64x faster than one of a pair
-// (measured: one block per CU = 0.82 of two), so a last round of <= 256 tiles costs 0.61.  The wide tiles only win
-// where they remove a round: at 25 000 rows the estimates tie (measured: within +-3 %, profiles/r3_gemm_geometries.txt)
-// and the round-2 kernel stays; at a few thousand rows mlp.c_fc (600 tiles of 128x128 = 1.17 rounds) takes the
-// 128x192 tile (400 tiles, one round).
-int h2w_plan(int M, int N, int K) {
-    (void)K;
-    auto cost = [&](int bm, int bn, double eff) {
-        const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        const long full = tiles / 512, rem = tiles % 512;
-        const double rounds = (double)full + (rem == 0 ? 0.0 : rem <= 256 ? 0.61 : 1.0);
-        return rounds * bm * bn / eff;
-    };
-    const double c0 = cost(128, 128, 1.0), c8 = cost(128, 192, 1.04), c2 = cost(256, 128, 1.05);
-    int best = 0;
-    double cb = c0 * 0.97;                       // the wide kernel must be worth >= 3 %
-    if (c8 < cb) { best = 8; cb = c8; }
-    if (c2 < cb) { best = 2; cb = c2; }
-    return best;
-}
-
 template <class G>
 static int launch_h2w(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                      const GemmEpilogue &epi, float scale, int slots) {
+                      const GemmEpilogue &epi, const GemmPlan &plan, const PackedArgs &a) {
+    CAPDEC_CHECK(plan.bm == G::BM && plan.bn == G::BN && plan.threads == G::THREADS && plan.ns == G::NS,
+                 "gemm_h2w: the plan names another geometry");
     const int tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
-    const int ntiles = tiles_m * tiles_n;
-    const int grid = ntiles <= 4 * slots ? std::min(ntiles, slots) : ntiles;
-    const float *resid_arg = epi.packed_out ? (const float *)epi.resid_packed : epi.resid;
-    hipLaunchKernelGGL((gemm_h2w_kernel<G>), dim3(grid), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
-                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, resid_arg, epi.ldr, epi.act, tiles_m, tiles_n,
-                       (char *)epi.packed_out, scale);
+    hipLaunchKernelGGL((gemm_h2w_kernel<G>), dim3(plan.grid), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
+                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, a.resid, epi.ldr, epi.act, tiles_m, tiles_n,
+                       (char *)epi.packed_out, 1.0f / H2_LO_SCALE);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
 
-// scale = 2^-11 (x 2^t for weights packed with a pre-scale 2^-t; t = 0 today: weights with |w| >= 16 keep the
-// two-accumulator kernel, see planes_of in capi.hip).  Requires the float4 epilogue (caller checks).
-int launch_gemm_h2w(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
-                    int K, const GemmEpilogue &epi, float scale) {
-    switch (which) {
-        case 2: return launch_h2w<W256x128>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, 512);
-        case 8: return launch_h2w<W128x192>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, 512);
-        default: CAPDEC_CHECK(false, "gemm_h2w: unknown geometry");
-    }
-    return 0;
+// plan.geo: 2 = 256x128, 8 = 128x192 (chosen by gemm_plan.h: only for weights with |w| < 16 and a float4 epilogue).
+// The kernels scale the result by 2^-11 (x 2^t for weights packed with a pre-scale 2^-t; t = 0 today: weights with
+// |w| >= 16 keep the two-accumulator kernel, see planes_of in gemm_dispatch.hip)
+int launch_gemm_h2w(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
+                    const GemmEpilogue &epi, const GemmPlan &plan) {
+    PackedArgs a;
+    CAPDEC_TRY(packed_args("gemm_f16x2p", epi, plan, C, ldc, M, N, K, &a));
+    CAPDEC_CHECK(plan.vec4 && plan.S == 1 && !a.sc.kc, "gemm_h2w: needs the float4 epilogue, an unsplit plan and no qkv scatter");
+    if (plan.geo == 2) return launch_h2w<W256x128>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, plan, a);
+    CAPDEC_CHECK(plan.geo == 8, "gemm_h2w: unknown geometry");
+    return launch_h2w<W128x192>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, plan, a);
 }
 
 // fused lm_head on the 256 x 128 tile: same partial lists per (row, 128-column tile) as launch_gemm_f16x2p_topk

@@ -34,15 +34,9 @@
 
 #include "bf16x3.h"
 #include "gemm_epilogue_lds.h"
+#include "gemm_packed.h"
 
 namespace capdec {
-
-typedef __attribute__((address_space(3))) void lds_void_p;
-typedef const __attribute__((address_space(1))) void glb_void_p;
-
-__host__ __device__ constexpr int waitcnt_imm_p(int vm, int lgkm) {
-    return (vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14);
-}
 
 template <int WM_, int WN_, int TI_, int TJ_, int NS_, bool TWOACC_>
 struct PGeo {
@@ -90,8 +84,8 @@ __device__ __forceinline__ void pp_mainloop(const _Float16 *__restrict__ Apk, co
 #define P_DMA(stage, ks_)                                                                                        \
     {                                                                                                            \
         _Pragma("unroll") for (int e = 0; e < PPW; ++e)                                                          \
-            __builtin_amdgcn_global_load_lds((glb_void_p *)(src[e] + (size_t)(ks_) * H2_BLOCK_B),                 \
-                                             (lds_void_p *)(smem + (stage) * SB + dofs[e]), 16, 0, 0);           \
+            __builtin_amdgcn_global_load_lds((glb_void *)(src[e] + (size_t)(ks_) * H2_BLOCK_B),                 \
+                                             (lds_void *)(smem + (stage) * SB + dofs[e]), 16, 0, 0);           \
     }
 #pragma unroll
     for (int i = 0; i < TI; ++i)
@@ -134,7 +128,7 @@ __device__ __forceinline__ void pp_mainloop(const _Float16 *__restrict__ Apk, co
     // prologue: tiles 0 .. D-1 in flight, tile 0 landed everywhere; group 1 then waits one barrier more (half a k-step)
 #pragma unroll
     for (int s = 0; s < D; ++s) P_DMA(s, min(s, nk - 1))
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm_p(PPW * (D - 1), 15));
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW * (D - 1), 15));
     P_BARRIER()
     if (grp == 1) { P_BARRIER() }
     int s0 = 0, sd = D % NS;                     // kt % NS, (kt + D) % NS
@@ -143,10 +137,10 @@ __device__ __forceinline__ void pp_mainloop(const _Float16 *__restrict__ Apk, co
         P_READ(s0)
         P_DMA(sd, min(kt + D, nk - 1))
         asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm_p(PPW * (D - 1), 15));
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(PPW * (D - 1), 15));
         P_BARRIER()
         // ---- MMA(kt)
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm_p(63, 0));
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         if constexpr (G::TWOACC) {
@@ -187,7 +181,7 @@ __device__ __forceinline__ void pp_mainloop(const _Float16 *__restrict__ Apk, co
         sd = sd + 1 == NS ? 0 : sd + 1;
     }
     if (grp == 0) { P_BARRIER() }
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm_p(0, 15));            // clamped tail pieces must land before the ring is reused
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 15));            // clamped tail pieces must land before the ring is reused
     P_BARRIER()
 #undef P_DMA
 #undef P_READ
@@ -232,12 +226,7 @@ __global__ __launch_bounds__(G::THREADS, G::MINW) void gemm_pp_kernel(const _Flo
         else ea.resid = resid;
         ea.sc = &sc;
         epilogue_lds<G>(acc, smem, ea);
-        if (tile + (int)gridDim.x < ntiles) {       // the next tile's DMA pieces land in the slabs: every wavefront must be done reading
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt(waitcnt_imm_p(63, 0));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
+        slab_release(tile + (int)gridDim.x < ntiles);
     }
 }
 
@@ -272,96 +261,35 @@ using P256x192s = PGeo<4, 2, 2, 3, 4, false>;     // 8 waves x (64 x 96), ONE ac
 //  accumulator registers or 256 KB of LDS to park them.  It, the one-set 256 x 128 and the 128 x 256 forms are gone:
 //  profiles/r4_gemm_pp.txt, docs/rounds.md.)
 
-int pp_splitk_slices(int which, int M, int N, int K);
-
 template <class G>
 static int launch_pp(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
-                     const GemmEpilogue &epi, float scale, int S) {
+                     const GemmEpilogue &epi, const GemmPlan &plan, const PackedArgs &a) {
+    CAPDEC_CHECK(plan.bm == G::BM && plan.bn == G::BN && plan.threads == G::THREADS && plan.ns == G::NS,
+                 "gemm_pp: the plan names another geometry");
     const int tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
-    const int ntiles = tiles_m * tiles_n;
-    const float kscale = G::TWOACC ? 1.0f : scale;
-    if (S > 1) {
-        float *part = (float *)epi.splitk_ws;
-        hipLaunchKernelGGL((gemm_pp_splitk_kernel<G>), dim3(ntiles * S), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
-                           (const _Float16 *)Bpacked, part, M, N, K, tiles_m, tiles_n, S, kscale);
+    const float kscale = G::TWOACC ? 1.0f : 1.0f / H2_LO_SCALE;      // (single-set geometries scale the result by 2^-11)
+    if (plan.S > 1) {
+        hipLaunchKernelGGL((gemm_pp_splitk_kernel<G>), dim3(plan.grid), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
+                           (const _Float16 *)Bpacked, a.part, M, N, K, tiles_m, tiles_n, plan.S, kscale);
         CAPDEC_HIP(hipGetLastError());
-        return launch_splitk_reduce(st, part, S, M, N, epi, C, ldc, PK_F16X2);
+        return launch_splitk_reduce(st, a.part, plan.S, M, N, epi, C, ldc, PK_F16X2);
     }
-    const int grid = ntiles <= 4 * 256 ? std::min(ntiles, 256) : ntiles;
-    const float *resid_arg = epi.packed_out ? (const float *)epi.resid_packed : epi.resid;
-    const QkvScatter sc = epi.qkv_scatter ? *epi.qkv_scatter : QkvScatter();
-    hipLaunchKernelGGL((gemm_pp_kernel<G>), dim3(grid), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
-                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, resid_arg, epi.ldr, epi.act, tiles_m, tiles_n,
-                       (char *)epi.packed_out, kscale, sc);
+    hipLaunchKernelGGL((gemm_pp_kernel<G>), dim3(plan.grid), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
+                       (const _Float16 *)Bpacked, C, ldc, M, N, K, epi.bias, a.resid, epi.ldr, epi.act, tiles_m, tiles_n,
+                       (char *)epi.packed_out, kscale, a.sc);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
 
-static void pp_tile(int which, int &bm, int &bn) {
-    bm = 256;
-    bn = which == 14 ? 192 : 128;
-}
-
-// K slices for a ping-pong launch (1 = none): grids of at most a third of the CUs are cut along K -- the largest S with
-// tiles x S <= 256 that divides the k-steps and leaves >= 8 per slice.  (625 captions x beam 5 = 3125 rows: the N = 768
-// projections are 78 tiles of 256 x 128 -> S = 3, 234 blocks.)  Needs the fp32 workspace and a float4-able result.
-int pp_splitk_slices(int which, int M, int N, int K) {
-    int bm, bn;
-    pp_tile(which, bm, bn);
-    const int tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn), nk = K / X3_BK;
-    // (M <= 512 -- the small-batch regime whose results must not depend on the batch size -- is never cut here: the planner
-    //  does not use these kernels there, and a FORCED geometry, CAPDEC_H2W >= 10, then runs unsplit whatever M is)
-    if (N % 4 != 0 || tiles * 3 > 256 || M <= 512) return 1;
-    int best = 1;
-    for (int s = 2; tiles * s <= 256 && s <= nk / 8; ++s)
-        if (nk % s == 0) best = s;
-    return best;
-}
-size_t pp_splitk_ws_bytes(int which, int M, int N, int K) {
-    const int s = pp_splitk_slices(which, M, N, K);
-    return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
-}
-
-// Which kernel for an f16x2 GEMM [M, N, K] of more than 512 rows: 0 = the kernels of rounds 2-3 (launch_gemm_f16x2p's own
-// planner), else a ping-pong geometry.  The chip runs these GEMMs at its power limit (sustained launches of the old and
-// the new structure reach the same k-steps per second per CU: profiles/r4_gemm_pp.txt), so the ping-pong kernels are
-// used only where they were MEASURED faster inside the decode loop: mid-size launches (513 .. 8191 rows, about one round),
-// with the tile whose grid fills the 256 CUs best -- 256 x 192 for mlp.c_fc (3125 rows: 208 blocks instead of 400
-// half-speed ones), 256 x 128 cut along K for the N = 768 projections.  Large launches (>= 8192 rows, several rounds) stay
-// with the round-2 kernels: inside the 5000-caption decode loop a 256 x 256 tile came out 2 % slower than they are.
-int pp_plan(int M, int N, int K, bool wide_ok, bool can_split) {
-    if (M >= 8192) return 0;
-    auto blocks_pp = [&](int which) {
-        int bm, bn;
-        pp_tile(which, bm, bn);
-        const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        return tiles * (can_split ? pp_splitk_slices(which, M, N, K) : 1);
-    };
-    // one round of blocks that fills >= 75 % of the CUs: prefer the larger tile
-    if (wide_ok && N >= 2048) {
-        const long b14 = blocks_pp(14);
-        if (b14 <= 256 && b14 >= 192 && N % 192 == 0) return 14;
-    }
-    const long b10 = blocks_pp(10);
-    if (b10 <= 256 && b10 >= 192 && N <= 1024) return 10;
-    return 0;
-}
-
-// `which`: 10 = 256x128 (two accumulator sets), 14 = 256x192 (one set: wide_ok weights).
-// scale = 2^-11 (single-set geometries; ignored by the two-set ones).  Requires the float4 epilogue (caller checks).
-int launch_gemm_pp(hipStream_t st, int which, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N,
-                   int K, const GemmEpilogue &epi, float scale) {
-    int S = 1;
-    if (epi.splitk_ws && !epi.resid_packed && !epi.packed_out && !epi.qkv_scatter && (which == 10 || which == 14)) {
-        S = pp_splitk_slices(which, M, N, K);
-        if (S > 1 && epi.splitk_ws_bytes < (size_t)S * M * N * sizeof(float)) S = 1;
-    }
-    switch (which) {
-        case 10: return launch_pp<P256x128>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, S);
-        case 14: return launch_pp<P256x192s>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, scale, S);
-        default: CAPDEC_CHECK(false, "gemm_pp: unknown geometry");
-    }
-    return 0;
+// plan.geo: 10 = 256x128 (two accumulator sets), 14 = 256x192 (one set: weights with |w| < 16), chosen by gemm_plan.h
+int launch_gemm_pp(hipStream_t st, const void *Apacked, const void *Bpacked, float *C, int ldc, int M, int N, int K,
+                   const GemmEpilogue &epi, const GemmPlan &plan) {
+    PackedArgs a;
+    CAPDEC_TRY(packed_args("gemm_f16x2p", epi, plan, C, ldc, M, N, K, &a));
+    CAPDEC_CHECK(plan.vec4, "gemm_pp: needs the float4 epilogue");
+    if (plan.geo == 10) return launch_pp<P256x128>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, plan, a);
+    CAPDEC_CHECK(plan.geo == 14, "gemm_pp: unknown geometry");
+    return launch_pp<P256x192s>(st, Apacked, Bpacked, C, ldc, M, N, K, epi, plan, a);
 }
 
 CAPDEC_SAT_ACCESSOR(sat_count_gemm_pp)

@@ -4,7 +4,7 @@ tests/decode_attn_def.py and the KV-cached oracle -- at every value of the prefi
 rounds, at GPT-2's last position, and where the launch needs more than 64 KB of LDS.
 
 CASES is a table: one row per case with the kernel form ``<BEAM, KV, OCC, NA, CUR, DMA>`` the row CLAIMS to launch,
-restated by hand from ``stack_body`` (decode.hip), ``gemm_splitk_slices`` and ``attn_decode_typed`` (attention.hip).
+restated by hand from ``stack_body`` (decode.hip), ``plan_splitk_128`` (gemm_plan.h) and ``attn_decode_typed`` (attention.hip).
 ``test_cases_launch_the_forms_they_claim`` runs this file as a script in a child process under ``rocprofv3
 --kernel-trace`` and checks each claim against the launches it observed, so a condition that moves in one of those three
 places turns a row red instead of silently re-routing it.

@@ -1,8 +1,8 @@
 """Every GEMM kernel and planner regime, element by element against an fp64 product.  Needs an MI355X: ``pytest -m gpu``.
 
 CASES is a table: precision mode, environment knobs, shape, strides, epilogue -- and the kernel, block count, workgroup
-size and split-K slice count the case CLAIMS to reach (restated by hand from launch_gemm_f16x2p / launch_gemm_x1 /
-launch_gemm_bf16x3p / pp_plan / h2w_plan / gemm_splitk_slices).  ``test_gemm_plan_case`` runs each case through the
+size and split-K slice count the case CLAIMS to reach (the decisions of gemm_plan(), gemm_plan.h; tests/test_gemm_plan.py
+checks the packed rows against that planner without a GPU).  ``test_gemm_plan_case`` runs each case through the
 capdec_gemm_f32 hook in a fresh Engine and compares ALL elements with the fp64 CPU product;
 ``test_cases_run_the_kernels_they_claim`` runs this file as a script (every case once, in table order) in a child
 process under ``rocprofv3 --kernel-trace`` and checks each claim against the launch that was observed, so that a
@@ -38,7 +38,7 @@ KNOBS = ("CAPDEC_GEMM_MODE", "CAPDEC_HOOK_PACKA", "CAPDEC_HOOK_CACHE", "CAPDEC_H
 # ---- kernels as (name, template arguments): what the trace shows, mangled or demangled (kernel_signature)
 H2P = ("gemm_f16x2p_kernel", (1, 4))                      # 128 x 128, two accumulator sets, float4 epilogue through LDS
 H2P_SC = ("gemm_f16x2p_kernel", (0, 4))                   # ... scalar epilogue (N % 4 != 0 or an unaligned stride)
-H2P_SK = ("gemm_f16x2p_splitk_kernel", ())
+H2P_SK = ("gemm_f16x2p_splitk_kernel", (0,))               # split-K of the 128 x 128 kernels: one template over KIND (0 = two planes)
 PP10 = ("gemm_pp_kernel", (4, 2, 2, 2, 5, 1))             # ping-pong 256 x 128 (P256x128), 512 threads
 PP14 = ("gemm_pp_kernel", (4, 2, 2, 3, 4, 0))             # ping-pong 256 x 192 (P256x192s)
 PP10_SK = ("gemm_pp_splitk_kernel", (4, 2, 2, 2, 5, 1))
@@ -59,7 +59,7 @@ def X1(mode, vec4=True):                                  # one-plane kernels: <
 
 
 def X1_SK(mode):
-    return ("gemm_x1_splitk_kernel", (KIND[mode],))
+    return ("gemm_f16x2p_splitk_kernel", (KIND[mode],))
 
 
 Case = collections.namedtuple("Case", "id mode env M N K kernel blocks wg S bias act resid lda ldc ldr")
@@ -518,7 +518,7 @@ def test_cases_run_the_kernels_they_claim(tmp_path, clean_env):
     fused, unfused = tail[:len(tail) // 2], tail[len(tail) // 2:]
     assert [g[:4] for g in fused] == [g[:4] for g in unfused], "CAPDEC_FUSE_LN changed a GEMM launch"
     rows = LN_ROWS[0][0] * LN_ROWS[0][1]
-    want = {("gemm_f16x2p_splitk_kernel", (), tiles(rows, 768) * 3, 256), PP10_SK + (tiles(rows, 768, 256, 128) * 8, 512)}
+    want = {H2P_SK + (tiles(rows, 768) * 3, 256), PP10_SK + (tiles(rows, 768, 256, 128) * 8, 512)}
     into_ln = [g for g in fused if g[4] == ["splitk_reduce_ln_kernel"]]
     assert {g[:4] for g in into_ln} == want, into_ln
     assert all(g[4] in ([], ["splitk_reduce_kernel"]) for g in fused if g not in into_ln), fused
