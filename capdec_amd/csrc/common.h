@@ -386,6 +386,29 @@ int launch_group_beam_step(hipStream_t st, const BeamState &s, const float *lse,
                            int vocab, int stop_id, const int *cmap = nullptr);
 // logp_out[cap, rank] = s.logp[cap, order[cap, rank]]: the unpenalised sums in the order launch_beam_finalize returned
 int launch_group_beam_logp(hipStream_t st, const BeamState &s, int ncap, int beam, const int *order, float *logp_out);
+// contrastive.hip: contrastive search (capdec_decode_contrastive; the contract: include/capdec.h).  K candidate rows per
+// caption in the beam layout (row = caption * K + c); hist [ncap, ctx, d] holds ln_f of every position of the chosen path,
+// L2-normalised.
+struct ContrastState {
+    int *ids = nullptr;         // [ncap, T]
+    int *lens = nullptr;        // [ncap]
+    uint8_t *done = nullptr;    // [ncap]
+    uint8_t *anc = nullptr;     // [ncap, K, ctx]
+    int *alive_count = nullptr; // [1] captions still running (device counter, polled by the host)
+    float *hist = nullptr;      // [ncap, ctx, d]
+    float *last = nullptr;      // [ncap, d] the chosen candidate's residual row (before ln_f), by caption
+    float *sel = nullptr;       // [active captions, d] the same, by compact activation row: the next lm_head's input
+    float *trace = nullptr;     // [ncap, T, 2] (p, sim) of the chosen candidate, or nullptr
+    int T = 0, ctx = 0, d = 0, stop_id = -1, alt_stop_id = -1;
+};
+// hist[cap][p] = normalise(ln_f(h[cap * P + p])) for the ncap * P prefill rows; last[cap] = sel[cap] = h[cap * P + P - 1]
+int launch_contrast_prefill(hipStream_t st, const ContrastState &s, const float *h, const float *lnw, const float *lnb,
+                            float eps, int ncap, int P);
+// one selection: block i takes the K rows h[i * K ..] of caption cmap[i] fed at position `pos`, their tokens / logits
+// top_idx / top_val [i, K] and lse [i], and emits the winner at `step` (see the contract)
+int launch_contrast_select(hipStream_t st, const ContrastState &s, const float *h, const float *lnw, const float *lnb,
+                           float eps, const float *lse, const float *top_val, const int *top_idx, int nact, int K,
+                           float alpha, int step, int pos, const int *cmap);
 // The state the greedy family of decodes (arg-max, teacher-forced, sampling) keeps per caption, and the constants of the
 // call that its step kernels need
 struct GreedyState {

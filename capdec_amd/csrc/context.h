@@ -120,7 +120,7 @@ struct ResNet {
 };
 
 enum Family { F_GEMM = 0, F_LMHEAD, F_ATTN_DEC, F_ATTN_PRE, F_LN, F_EMBED, F_SELECT, F_MAP_ATTN, F_OTHER, F_GEMM_X3,
-              F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_NEAREST, F_COUNT };
+              F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_NEAREST, F_CONTRAST, F_COUNT };
 extern const char *const kFamilyNames[F_COUNT];
 constexpr int PROF_SLOTS = 24;   // capdec_profile_get fills at most this many families (engine.py sizes its arrays by it)
 static_assert(F_COUNT <= PROF_SLOTS, "profile arrays too small");
@@ -178,6 +178,8 @@ struct capdec_ctx {
     DBuf h, x, qkv, att, ff, xl, tmax, tsum, cval, cidx, lse, topv, topi, kc, vc;
     DBuf tokens, scores, seq, stopped, done, anc, next_tok, alive, gids, glens, cmap, kvstat;
     DBuf glogp;            // diverse beam search (capdec_decode_beam_groups): the unpenalised log-prob sums [rows] (BeamState::logp)
+    DBuf cs_hist, cs_last, cs_sel;   // contrastive search (contrastive.hip): the L2-normalised ln_f history [captions, ctx, d],
+                                     // the chosen candidate's residual row by caption and by compact activation row [captions, d]
     capdec::TrainState *train = nullptr;     // created by the first capdec_train_step, freed by train_release
     int train_scope = 0;                     // capdec_train_set_scope: survives capdec_train_reset and weight reloads
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
@@ -337,6 +339,39 @@ void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd);
 int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv);
 int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp);
 int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads = 0, int hd = 0, int layers = 0);
+// The constants of one decode call; the extern "C" entry points fill it, decode_common offsets the pointers per chunk.
+struct DecodeCall {
+    int P = 0, beam = 1;
+    bool greedy = true;         // the greedy family (arg-max, teacher-forced, sampling): beam == 1
+    int stop_id = -1, alt_stop_id = -1, T = 0;
+    float temperature = 1.0f;
+    int *ids = nullptr, *lens = nullptr;        // [n, beam, T], [n, beam]
+    float *scores = nullptr;    // [n, beam] (beam)
+    int *order = nullptr;       // [n, beam] or nullptr (beam)
+    const int *forced = nullptr;    // [n, T] teacher forcing: fed instead of the arg-max (greedy)
+    float *stats = nullptr;     // [n, T, 3] or nullptr (teacher forcing)
+    // the sampling decode (capdec_decode_sample): the greedy loop with the arg-max replaced by a draw.  The Philox counter
+    // is (cap_off + caption, step) and nothing else, so a caption's draws do not depend on the chunking, on the compaction or
+    // on the rest of the batch.
+    bool sample = false;
+    float top_p = 0.f;
+    uint64_t seed = 0;
+    const float *u = nullptr;   // [n, T] or nullptr (Philox)
+    float *logp = nullptr;      // [n, T] or nullptr
+    // diverse beam search (capdec_decode_beam_groups): groups > 0 sends the beam bookkeeping to diverse.hip's group kernels
+    int groups = 0;
+    float diversity = 0.f;
+    float *glogp = nullptr;     // [n, beam] or nullptr: the unpenalised log-prob sums, in the returned order
+    int cap_off = 0;            // index of the chunk's first caption within the call: the Philox counter's caption offset, and
+                                // the offset of the chunk's slice of the per-call K/V-slot statistic (BeamState::kv_stat)
+};
+// ... and what the contrastive search (contrastive.hip) shares with the drivers above: whether the call runs the logits
+// processors, the lm_head route through materialised logits, the alive-count poll and the captions-per-chunk computation
+bool processors_on(const capdec_ctx *c, bool sampling);
+int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const DecodeCall &a,
+                 const GreedyState &gs, bool proc, int step, int beam, const int *hist);
+int poll_alive(capdec_ctx *c, int *alive);
+int chunk_captions(capdec_ctx *c, int n, int beam, int ctx, size_t extra_per_cap = 0);
 
 // ---- nearest.hip
 void drop_wte_norm(capdec_ctx *c);      // the normalised copy of wte and its planes (wte was reloaded or updated)

@@ -164,36 +164,9 @@ static int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float 
     return gemm(c, c->xl.as<float>(), d, g.wte, d, logits, ld, R, g.vocab, d, nullptr, CAPDEC_ACT_NONE);
 }
 
-// The constants of one decode call; the extern "C" entry points fill it, decode_common offsets the pointers per chunk.
-struct DecodeCall {
-    int P = 0, beam = 1;
-    bool greedy = true;         // the greedy family (arg-max, teacher-forced, sampling): beam == 1
-    int stop_id = -1, alt_stop_id = -1, T = 0;
-    float temperature = 1.0f;
-    int *ids = nullptr, *lens = nullptr;        // [n, beam, T], [n, beam]
-    float *scores = nullptr;    // [n, beam] (beam)
-    int *order = nullptr;       // [n, beam] or nullptr (beam)
-    const int *forced = nullptr;    // [n, T] teacher forcing: fed instead of the arg-max (greedy)
-    float *stats = nullptr;     // [n, T, 3] or nullptr (teacher forcing)
-    // the sampling decode (capdec_decode_sample): the greedy loop with the arg-max replaced by a draw.  The Philox counter
-    // is (cap_off + caption, step) and nothing else, so a caption's draws do not depend on the chunking, on the compaction or
-    // on the rest of the batch.
-    bool sample = false;
-    float top_p = 0.f;
-    uint64_t seed = 0;
-    const float *u = nullptr;   // [n, T] or nullptr (Philox)
-    float *logp = nullptr;      // [n, T] or nullptr
-    // diverse beam search (capdec_decode_beam_groups): groups > 0 sends the beam bookkeeping to diverse.hip's group kernels
-    int groups = 0;
-    float diversity = 0.f;
-    float *glogp = nullptr;     // [n, beam] or nullptr: the unpenalised log-prob sums, in the returned order
-    int cap_off = 0;            // index of the chunk's first caption within the call: the Philox counter's caption offset, and
-                                // the offset of the chunk's slice of the per-call K/V-slot statistic (BeamState::kv_stat)
-};
-
 // Does this call run the logits processors (capdec_set_logits_processors / capdec_set_logit_bias)?  top_k counts in the
 // sampling decode only.
-static bool processors_on(const capdec_ctx *c, bool sampling) {
+bool processors_on(const capdec_ctx *c, bool sampling) {
     const LogitsProc &p = c->proc;
     return p.theta != 1.0f || p.ngram > 0 || p.min_len > 0 || c->proc_bias_n > 0 || (sampling && p.top_k > 0);
 }
@@ -205,7 +178,7 @@ static bool processors_on(const capdec_ctx *c, bool sampling) {
 //   sampling      top_k where it removes something, the nucleus-sampling kernel (it writes what launch_greedy_step
 //                 writes, into gs), the logp shift under top_k.
 // hist: the rows' histories [captions, beam, T] -- `ids` or BeamState::tokens; `step` entries of each are read.
-static int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const DecodeCall &a,
+int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const DecodeCall &a,
                         const GreedyState &gs, bool proc, int step, int beam, const int *hist) {
     const int V = c->gpt.vocab, ld = (V + 63) / 64 * 64, blk = std::min(R, std::max(1, c->tune.sample_rows));
     const LogitsProc &p = c->proc;
@@ -263,7 +236,7 @@ int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads, int hd, 
     return 0;
 }
 
-static int poll_alive(capdec_ctx *c, int *alive) {
+int poll_alive(capdec_ctx *c, int *alive) {
     CAPDEC_HIP(hipMemcpyAsync(c->alive_host, c->alive.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     const bool watch = c->lmflag_live && !c->k3_off;
     if (watch) CAPDEC_HIP(hipMemcpyAsync(c->alive_host + 1, c->lmflag.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -278,10 +251,10 @@ static int poll_alive(capdec_ctx *c, int *alive) {
 // captions per chunk so that the fp32 KV cache fits the budget: the configured budget (capdec_set_kv_budget, default
 // 192 GiB), clamped to 85 % of what the device can still give (free memory + what the KV buffers already hold), so
 // a GPU that is partly occupied -- torch's caching allocator, the CLIP towers, a smaller part -- gets smaller chunks
-// instead of a failed hipMalloc
-static int chunk_captions(capdec_ctx *c, int n, int beam, int ctx) {
+// instead of a failed hipMalloc.  extra_per_cap: bytes a caption keeps next to its K/V (the contrastive search's history)
+int chunk_captions(capdec_ctx *c, int n, int beam, int ctx, size_t extra_per_cap) {
     const Gpt2 &g = c->gpt;
-    const size_t per_cap = (size_t)beam * ctx * g.d * 2 * (c->gemm_mode == GEMM_BF16 ? 2 : 4) * g.n_layer;
+    const size_t per_cap = (size_t)beam * ctx * g.d * 2 * (c->gemm_mode == GEMM_BF16 ? 2 : 4) * g.n_layer + extra_per_cap;
     size_t budget = c->kv_budget, free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         const size_t avail = (size_t)((double)(free_b + c->kc.cap + c->vc.cap) * 0.85);

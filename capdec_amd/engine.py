@@ -595,8 +595,45 @@ class Engine:
                   "capdec_decode_beam_groups")
         return ids, lens, scores, order, logp
 
+    def decode_contrastive(self, prefix_embed: torch.Tensor, top_k: int = 4, penalty_alpha: float = 0.6, stop_id: int = 13,
+                           alt_stop_id: int = -1, entry_length: int = 67, return_trace: bool = False, *,
+                           repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                           min_length: Optional[int] = None, logit_bias=None):
+        """contrastive search (capdec_decode_contrastive; Su et al. 2022): per step the ``top_k`` most probable tokens are
+        each fed through the model, and the one with the best ``(1 - penalty_alpha) * p - penalty_alpha * max cosine`` of
+        its ln_f hidden state against those of the whole context so far is emitted.  -> ids [n, T] (zero padded), lens
+        [n] (including the stop token; ``stop_id`` defaults to GPT-2's '.') and, with ``return_trace``, trace [n, T, 2] =
+        (p, sim) of every chosen candidate.  ``penalty_alpha=0`` or ``top_k=1`` is :meth:`decode_greedy`.  Needs
+        ``P + entry_length <= n_positions``.  The keyword-only processors as in :meth:`decode_greedy`."""
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)):
+            raise CapdecError(f"decode_contrastive: top_k must be an integer, got {top_k!r}")
+        if not 1 <= top_k <= 8:
+            raise CapdecError(f"decode_contrastive: top_k must be in 1..8, got {top_k}")
+        a = penalty_alpha
+        if isinstance(a, bool) or not isinstance(a, (int, float, np.floating)) or not 0 <= a <= 1:
+            raise CapdecError(f"decode_contrastive: penalty_alpha must be a number in [0, 1], got {a!r}")
+        if isinstance(entry_length, bool) or not isinstance(entry_length, (int, np.integer)) or entry_length < 1:
+            raise CapdecError(f"decode_contrastive: entry_length must be a positive integer, got {entry_length!r}")
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias):
+            return self._decode_contrastive(prefix_embed, int(top_k), float(a), stop_id, alt_stop_id, int(entry_length),
+                                            bool(return_trace))
+
+    def _decode_contrastive(self, prefix_embed, top_k, alpha, stop_id, alt_stop_id, entry_length, return_trace):
+        p = self._dev(prefix_embed)
+        n, P, _ = p.shape
+        ids = torch.empty(n, entry_length, device=self.device, dtype=torch.int32)
+        lens = torch.empty(n, device=self.device, dtype=torch.int32)
+        trace = torch.empty(n, entry_length, 2, device=self.device, dtype=torch.float32) if return_trace else None
+        self._sync_stream()
+        self._chk(self.lib.capdec_decode_contrastive(self._h, p.data_ptr(), n, P, top_k, alpha, int(stop_id), int(alt_stop_id),
+                                                     entry_length, ids.data_ptr(), lens.data_ptr(),
+                                                     trace.data_ptr() if trace is not None else None),
+                  "capdec_decode_contrastive")
+        return (ids, lens, trace) if return_trace else (ids, lens)
+
     # ------------------------------------------------------------------ scoring
-    def score(self, prefix_embed: torch.Tensor, tokens: torch.Tensor, lens=None, ignore_id: int = -1,
+    def score(self,prefix_embed: torch.Tensor, tokens: torch.Tensor, lens=None, ignore_id: int = -1,
               temperature: float = 1.0, return_top1: bool = False):
         """teacher-forced log-probabilities of given captions (capdec_score): ``prefix_embed`` [n, P, d], ``tokens``
         [n, L], ``lens`` [n] in 0..L (None: every caption has L tokens) -> device tensors logp [n, L] (0 past ``lens``

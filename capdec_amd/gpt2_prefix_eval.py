@@ -297,6 +297,48 @@ def generate_samples(model, tokenizer, tokens=None, prompt=None, embed=None, ent
     return [tokenizer.decode((prompt_ids or []) + [int(t) for t in ids[e, :lens[e]]]) for e in range(entry_count)]
 
 
+# --------------------------------------------------------------------------- contrastive search
+def decode_contrastive_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, top_k: int = 4,
+                           penalty_alpha: float = 0.6, entry_length: int = 67, alt_stop_id: int = ALT_STOP_ID,
+                           return_trace: bool = False, *, repetition_penalty: Optional[float] = None,
+                           no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None, logit_bias=None):
+    """embed [N, P, d] -> ids int32 [N, entry_length] (zero padded), lens int32 [N] (including the stop token) of the
+    contrastive search (``capdec_decode_contrastive``: ``top_k`` / ``penalty_alpha`` of ``transformers.generate``) and,
+    with ``return_trace``, trace [N, entry_length, 2] = (probability, max cosine) of every chosen candidate."""
+    kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    return model.engine.decode_contrastive(embed, top_k, penalty_alpha, stop_token_index, alt_stop_id, entry_length,
+                                           return_trace, **kw)
+
+
+def generate_contrastive_batch(model, tokenizer, embed: torch.Tensor, entry_length: int = 67, top_k: int = 4,
+                               penalty_alpha: float = 0.6, stop_token: str = '.', *,
+                               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                               min_length: Optional[int] = None, logit_bias=None) -> List[str]:
+    """``generate2_batch`` with contrastive search: embed [N, P, d] -> one text per caption"""
+    stop = tokenizer.encode(stop_token)[0]
+    ids, lens = decode_contrastive_ids(model, embed, stop, top_k, penalty_alpha, entry_length,
+                                       repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                       min_length=min_length, logit_bias=logit_bias)
+    ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+    return [tokenizer.decode(list(ids[r, :lens[r]])) for r in range(ids.shape[0])]
+
+
+def generate_contrastive(model, tokenizer, tokens=None, prompt=None, embed=None, entry_length=67, top_k: int = 4,
+                         penalty_alpha: float = 0.6, stop_token: str = '.') -> str:
+    """``generate2`` with contrastive search instead of the arg-max: one caption ([1, P, d], tokens or a prompt) -> str.
+    Prompt tokens stay in front and 764 is the second stop id, as in ``generate2``; ``penalty_alpha=0`` or ``top_k=1``
+    gives ``generate2``'s tokens.  (Logits processors: ``model.logits_processors``.)"""
+    model.eval()
+    prefix, prompt_ids = _prefix_from(model, tokenizer, tokens, prompt, embed)
+    if prefix.shape[0] != 1:
+        raise CapdecError("generate_contrastive takes one caption ([1, P, d]); use generate_contrastive_batch for [N, P, d]")
+    stop = tokenizer.encode(stop_token)[0]
+    ids, lens = decode_contrastive_ids(model, prefix, stop, top_k, penalty_alpha, entry_length)
+    n = int(lens.cpu()[0])
+    out = [int(t) for t in ids.cpu().numpy()[0, :n]]
+    return tokenizer.decode((prompt_ids or []) + out)
+
+
 # --------------------------------------------------------------------------- prefix interpretation and editing
 def _nearest(embeddings, x: torch.Tensor, k: int = 1, model=None):
     """(ids, sims) of the rows of ``x`` [..., d] against ``embeddings``: a ClipCaptionModel (its wte, normalised once and

@@ -387,6 +387,32 @@ int capdec_decode_beam_groups(capdec_ctx *ctx, const float *d_prefix, int n, int
                               int32_t *d_ids, int32_t *d_lens, float *d_scores,
                               int32_t *d_order,
                               float *d_logp /* [n, beam] or NULL */);
+/* Contrastive search (Su et al. 2022; `penalty_alpha` / `top_k` of transformers.generate): the one decode that reads the
+ * model's hidden states.  top_k = K in 1..8, penalty_alpha = a in [0, 1] (finite), prefix_length + entry_length <=
+ * min(1024, n_positions) -- one position more than capdec_decode_greedy, because every emitted token is chosen after its
+ * own candidate pass.  hid(x) is the ln_f output of the last layer (the vector that multiplies wte; transformers'
+ * hidden_states[-1] for GPT-2).  Per caption, with prefix [P, d] and T = entry_length:
+ *   prefill  H = [hid of prefix positions 0..P-1], every row divided by max(its L2 norm, 1e-12); last = hid(position P-1);
+ *   for t = 0..T-1, pos = P + t:
+ *     lg = last . wte^T, with the logits processors that are set (repetition_penalty, no_repeat_ngram_size, min_length,
+ *          logit_bias) applied with the caption's chosen ids as history, exactly as in capdec_decode_greedy (the processors'
+ *          top_k is sampling-only and ignored; there is no temperature);
+ *     candidates v_0..v_{K-1} = the K largest processed logits (larger value, then smaller token); p_c = softmax(lg)[v_c];
+ *     every candidate is fed at pos (wte[v_c] + wpe[pos]) and attends to the chosen path's K/V: h_c = hid(...);
+ *     sim_c = max over j < pos of cos(h_c, H_j) -- the prefix positions count as context;
+ *     score_c = (1 - a) * p_c - a * sim_c in fp32; the winner w = argmax_c score_c, an exact tie going to the lower c;
+ *     d_ids[t] = v_w, d_lens = t + 1; the normalised h_w is appended to H, the K/V candidate w wrote at pos becomes the
+ *     path's, last = h_w; v_w == stop_id or alt_stop_id finishes the caption (the stop token is part of the output).
+ * a = 0 or K = 1 gives capdec_decode_greedy's tokens.  d_ids [n, entry_length] zero padded, d_lens [n]; d_trace (may be
+ * NULL) fp32 [n, entry_length, 2] = (p, sim) of the chosen candidate of every emitted token, zero elsewhere.  A caption's
+ * result does not depend on chunking, compaction or the other captions (capdec_set_batch_invariant's caveat applies).  The
+ * K candidates are K beam rows (row = caption * K + c) on the ancestor-table attention; the lm_head runs on one row per
+ * caption; the per-caption history [P + T, d] fp32 counts against the KV budget.  Errors (capdec_last_error): top_k
+ * outside 1..8, penalty_alpha outside [0, 1] or NaN, a context that is too long, head_dim other than 64. */
+int capdec_decode_contrastive(capdec_ctx *ctx, const float *d_prefix, int n, int P, int top_k, float penalty_alpha,
+                              int stop_id, int alt_stop_id, int entry_length,
+                              int32_t *d_ids /* [n, T] */, int32_t *d_lens /* [n] */,
+                              float *d_trace /* [n, T, 2] or NULL */);
 /* Nucleus-sampling decode: the greedy loop with the arg-max replaced by one draw per step.  For a row of logits l, with
  * s = l / (temperature > 0 ? temperature : 1) and p = softmax(s): token j is in the nucleus iff it is the arg-max or the
  * sum of p[i] over all p[i] > p[j] is <= top_p (the filter of reference gpt2_prefix_eval.py:166-175; exactly equal
