@@ -80,12 +80,26 @@ __device__ __forceinline__ float h2_clamp(float a) {       // NaN-preserving (fm
     return a != a ? a : __builtin_fminf(__builtin_fmaxf(a, -65504.f), 65504.f);
 }
 
+// the same count without a branch: 1 when the quad saturates.  A caller adds it to a counter in a register and posts the
+// sum once (h2_post_saturated) -- where h2_clamp_count costs an exec-mask save, a branch and an atomic site per quad.
+__device__ __forceinline__ unsigned int h2_saturates(const float4 v) {
+    const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)),
+                                    __builtin_fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w)));
+    return m > 65504.f ? 1u : 0u;
+}
+__device__ __forceinline__ void h2_post_saturated(unsigned int n) {
+    if (n) atomicAdd(&g_h2_saturated, n);
+}
+
+// COUNTED = false: the caller counts the quad itself (h2_saturates).  CLAMP = false: the caller knows that no element is
+// beyond +-65504 (h2_saturates gave 0), where h2_clamp returns its argument unchanged -- NaN, +-0 and subnormals included.
+template <bool COUNTED = true, bool CLAMP = true>
 __device__ __forceinline__ void split2h(const float4 v, f16x4 &h, f16x4 &l) {
     const float a[4] = {v.x, v.y, v.z, v.w};
-    (void)h2_clamp_count(v);
+    if constexpr (COUNTED) (void)h2_clamp_count(v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float c = h2_clamp(a[e]);
+        const float c = CLAMP ? h2_clamp(a[e]) : a[e];
         const _Float16 hh = __builtin_fabsf(c) < 0x1p-14f ? (_Float16)0.f : (_Float16)c;
         const float r = c - (float)hh;                // exact
         h[e] = hh;

@@ -132,11 +132,82 @@ __global__ __launch_bounds__(256) void layernorm_packed_kernel(const float *__re
 #undef LN_LOAD
 }
 
+// The large-row form with whole-line stores (d % 64 == 0).  Above, a lane owns quads lane + 64 i of ONE row: a store
+// instruction of a wavefront touches 16 separate 32-byte fragments (16 k-steps, 8 KB apart), and the 128-byte line of a
+// plane -- four rows x 32 B of one k-step -- is completed by four wavefronts at four different times.  Here a wavefront owns
+// FOUR adjacent rows, 16 lanes (one DPP row) each: lane (g, t) holds quads 16 j + t of row 4 * group + g.  Loads stay 256 B
+// contiguous per row; a store instruction writes, per plane, the whole lines of four k-steps.
+// The statistics are those of the form above, bit for bit: its lane L = 16 m + t sums quads L + 64 i over i, and
+// wave_sum is row16_sum over lanes 16 m .. 16 m + 15 followed by (R0 + R1) + (R2 + R3).  Quad L + 64 i is 16 (4 i + m) + t:
+// lane (g, t) holds all of them for every m, so it forms the four partial sums s[m] in the same order, row16_sum runs over
+// the same 16 values in the same lane positions t, and the four row sums are paired the same way.  (A partial sum starts
+// at +0 and can never become -0, so the zeros the form above adds for lanes past d change nothing.)
+// w and b come from LDS (2 x d floats per block).  One group of four rows per wavefront, 16 rows per block: with two
+// groups and a prefetch (157 VGPRs, 782 blocks at 25 000 rows) the kernel took 40.8 us against 34.5 us for the form above
+// on the same box; this one 29.4 against 31.8 (profiles/epilogue_valu_ab.txt).
+template <int NJ>
+__global__ __launch_bounds__(256) void layernorm_packed_lines_kernel(const float *__restrict__ x, int ldx,
+                                                                     const float *__restrict__ w, const float *__restrict__ b,
+                                                                     float eps, char *__restrict__ packed, int rows, int d,
+                                                                     int fmt) {
+    __shared__ float4 sw[NJ * 16], sb[NJ * 16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, t = lane & 15;
+    const int nv = d >> 2, nj = nv >> 4, nk = d / X3_BK;
+    const int row = (blockIdx.x * 4 + wave) * 4 + g;    // the block's waves write 16 adjacent rows
+    float4 v[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        v[j] = (j < nj && row < rows) ? reinterpret_cast<const float4 *>(x + (size_t)row * ldx)[16 * j + t]
+                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < nv; i += 256) {
+        sw[i] = reinterpret_cast<const float4 *>(w)[i];
+        sb[i] = reinterpret_cast<const float4 *>(b)[i];
+    }
+    __syncthreads();
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int j = 4 * i + m;
+            if (j < NJ && j < nj) s[m] += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+        }
+    const float mean = ((row16_sum(s[0]) + row16_sum(s[1])) + (row16_sum(s[2]) + row16_sum(s[3]))) / (float)d;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int j = 4 * i + m;
+            if (j < NJ && j < nj) {
+                const float a = v[j].x - mean, b2 = v[j].y - mean, c = v[j].z - mean, e = v[j].w - mean;
+                q[m] += (a * a + b2 * b2) + (c * c + e * e);
+            }
+        }
+    const float rstd = 1.0f / sqrtf(((row16_sum(q[0]) + row16_sum(q[1])) + (row16_sum(q[2]) + row16_sum(q[3]))) / (float)d + eps);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        if (j < nj && row < rows) {
+            const int idx = 16 * j + t;
+            const float4 ww = sw[idx], bb = sb[idx];
+            float4 o;
+            o.x = (v[j].x - mean) * rstd * ww.x + bb.x;
+            o.y = (v[j].y - mean) * rstd * ww.y + bb.y;
+            o.z = (v[j].z - mean) * rstd * ww.z + bb.z;
+            o.w = (v[j].w - mean) * rstd * ww.w + bb.w;
+            x3_store_quad(packed, nk, row, idx >> 2, idx & 3, o, fmt);
+        }
+    }
+}
+
 int launch_layernorm_packed(hipStream_t st, const float *x, int ldx, const float *w, const float *b, float eps,
                             void *packed, int rows, int d, int fmt) {
     CAPDEC_CHECK(d % 16 == 0 && d <= 256 * LN_MAXV && ldx % 4 == 0, "layernorm_packed: unsupported width");
     if (rows <= 0) return 0;
-    if (rows >= 16384)      // 4 rows per wavefront once that still leaves >> 256 blocks (25 000 rows: 39.5 -> 37.5 us);
+    if (rows >= 16384 && d % 64 == 0 && d <= 768)      // whole-line stores (12 quads per lane: every width the models here have;
+        hipLaunchKernelGGL(layernorm_packed_lines_kernel<12>, dim3((rows + 15) / 16), dim3(256), 0, st, x, ldx, w, b, eps,   // wider rows keep the form below)
+                           (char *)packed, rows, d, fmt);
+    else if (rows >= 16384)      // 4 rows per wavefront once that still leaves >> 256 blocks (25 000 rows: 39.5 -> 37.5 us);
         hipLaunchKernelGGL(layernorm_packed_kernel<4>, dim3((rows + 15) / 16), dim3(256), 0, st, x, ldx, w, b, eps,
                            (char *)packed, rows, d, fmt);
     else                    // small batches need every block they can get (3125 rows: 9.8 us with 1, 12.7 us with 4)

@@ -183,10 +183,186 @@ __device__ __forceinline__ void epilogue_lds_wave(const f32x16 (&acc)[TI][TJ], f
     }
 }
 
+template <int TI, int TJ> __device__ __forceinline__ void epilogue_slab_fill(const f32x16 (&acc)[TI][TJ], float *slab, int i) {
+    using S = EpiSlab<TJ>;
+    const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
+#pragma unroll
+    for (int j = 0; j < TJ; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4 *>(slab + l32 * S::LD + j * 32 + 8 * g + 4 * half) = acc_quad(acc[i][j], g);
+}
+__device__ __forceinline__ void epilogue_slab_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Section 10 of DESIGN.md: the vector-ALU work between two tiles.  The two walks below produce what epilogue_lds_wave
+// produces -- the same values to the same addresses -- for the cases the decode step runs 24 times per step; what differs
+// is what a lane does per piece besides the arithmetic of its values.
+
+// MODE 1, two-plane output without a packed residual, of a wavefront block that lies wholly inside [0, M) x [0, N) and
+// starts at a multiple of 32 rows (195 of 196 row tiles at 25 000 rows).  A lane's column is the same in every pass: its
+// k-step, its half and its bias are taken once.  Its rows advance by 64 / LPR per pass inside one 128-row block of the
+// plane: the block offset is taken once per 32 rows, the pass offset and the swizzle bit (bit 3 of the row) are constants of
+// the unrolled loop.  No `live` test, no clamped address.  Saturated quads are summed in a register and posted once; a pass
+// in which no lane saturates (every pass of a healthy checkpoint) skips the clamp, which is the identity there.
+template <int TI, int TJ, int ACT>
+__device__ __forceinline__ void epilogue_lds_wave_h2_interior(const f32x16 (&acc)[TI][TJ], float *slab, int row0, int col0,
+                                                              const EpiArgs &a) {
+    using S = EpiSlab<TJ>;
+    using Wk = EpiWalk<TJ, 2>;
+    static_assert(64 % Wk::LPR == 0 && Wk::PASSES * 64 == 32 * Wk::LPR, "one column per lane, whole passes");
+    constexpr int RPP = 64 / Wk::LPR;                              // rows per pass
+    const int lane = threadIdx.x & 63;
+    const int rl0 = lane / Wk::LPR, cq = lane % Wk::LPR;
+    const int col = col0 + cq * 8;
+    const int nk_out = a.N >> 4, ks = col >> 4, hf = (col >> 3) & 1;
+    const bool has_bias = a.bias != nullptr;
+    float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
+    if (has_bias) {
+        b0 = *reinterpret_cast<const float4 *>(a.bias + col);
+        b1 = *reinterpret_cast<const float4 *>(a.bias + col + 4);
+    }
+    const float *sp = slab + rl0 * S::LD + cq * 8;
+    unsigned int nsat = 0;
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+        epilogue_slab_fill<TI, TJ>(acc, slab, i);
+        epilogue_slab_sync();
+        const int rb = row0 + i * 32;                              // a multiple of 32
+        char *pb = a.packed + ((size_t)(rb >> 7) * nk_out + ks) * H2_BLOCK_B + ((rb & 96) + rl0) * X3_ROW_B;
+#pragma unroll
+        for (int p = 0; p < Wk::PASSES; ++p) {
+            float4 v[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                v[q] = *reinterpret_cast<const float4 *>(sp + p * RPP * S::LD + 4 * q);
+                v[q].x *= a.scale; v[q].y *= a.scale; v[q].z *= a.scale; v[q].w *= a.scale;
+                if (has_bias) {
+                    const float4 b = q ? b1 : b0;
+                    v[q].x += b.x; v[q].y += b.y; v[q].z += b.z; v[q].w += b.w;
+                }
+                v[q].x = act_const<ACT>(v[q].x); v[q].y = act_const<ACT>(v[q].y);
+                v[q].z = act_const<ACT>(v[q].z); v[q].w = act_const<ACT>(v[q].w);
+            }
+            const unsigned int sat0 = h2_saturates(v[0]), sat1 = h2_saturates(v[1]);
+            nsat += sat0 + sat1;
+            f16x4 h0, l0, h1, l1;
+            if (__builtin_amdgcn_ballot_w64((sat0 | sat1) != 0u)) {      // wave-uniform; rare by construction
+                split2h<false>(v[0], h0, l0);
+                split2h<false>(v[1], h1, l1);
+            } else {                                                     // nothing to clamp in the whole pass
+                split2h<false, false>(v[0], h0, l0);
+                split2h<false, false>(v[1], h1, l1);
+            }
+            const int sw = ((p * RPP + rl0) >> 3) & 1;             // bit 3 of the row (rb adds multiples of 32)
+            char *pp = pb + p * RPP * X3_ROW_B + ((hf ^ sw) << 4);
+            f16x8 hh, ll;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { hh[e] = h0[e]; hh[4 + e] = h1[e]; ll[e] = l0[e]; ll[4 + e] = l1[e]; }
+            *reinterpret_cast<f16x8 *>(pp) = hh;
+            *reinterpret_cast<f16x8 *>(pp + X3_PLANE_B) = ll;
+        }
+        epilogue_slab_sync();
+    }
+    h2_post_saturated(nsat);
+}
+
+// MODE 2 (qkv scatter) with one column per lane.  Everything that depends on the column alone -- q or K / V, the cache,
+// the head and the offset inside a cached row -- is taken once per tile.  A lane's rows advance by 64 / LPR per piece
+// through the whole tile: one division gives (caption, beam) of its first row, the rest follow by addition.  With a
+// caption map, the lane's TI x PASSES entries are requested BEFORE the transposition (as the bias is) instead of each one
+// in front of its store; entries of rows past M are clamped into the map (loaded, never used).
+template <int TI, int TJ, bool INTERIOR>
+__device__ __forceinline__ void epilogue_lds_wave_qkv(const f32x16 (&acc)[TI][TJ], float *slab, int row0, int col0,
+                                                      const EpiArgs &a) {
+    using S = EpiSlab<TJ>;
+    using Wk = EpiWalk<TJ, 1>;
+    static_assert(64 % Wk::LPR == 0 && Wk::PASSES * 64 == 32 * Wk::LPR, "one column per lane, whole passes");
+    constexpr int RPP = 64 / Wk::LPR, NP = TI * Wk::PASSES;
+    const QkvScatter &sc = *a.sc;
+    const int lane = threadIdx.x & 63;
+    const int rl0 = lane / Wk::LPR, cq = lane % Wk::LPR;
+    const int col = col0 + cq * 4;
+    const bool col_live = INTERIOR || col < a.N;
+    float4 bq = make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool has_bias = a.bias != nullptr;
+    if (has_bias) bq = *reinterpret_cast<const float4 *>(a.bias + (INTERIOR ? col : min(col, a.N - 4)));
+    const bool is_q = col < sc.d, is_v = col >= 2 * sc.d;
+    float *cache = is_v ? sc.vc : sc.kc;
+    const int hc = col - (is_v ? 2 * sc.d : sc.d), head = hc >> 6;
+    const size_t cell = ((size_t)head * sc.ctx + sc.pos) * 64 + (hc & 63);      // inside a cached row
+    const size_t row_el = (size_t)sc.heads * sc.ctx * 64;                        // elements per cached row
+    const int beam = sc.beam, step_q = RPP / beam, step_r = RPP - step_q * beam;
+    const int cap0 = (row0 + rl0) / beam, b0 = (row0 + rl0) - cap0 * beam;
+    int cm[NP];                                                                  // the cache caption of every piece
+    {
+        const int cap_last = (a.M - 1) / beam;
+        int cap = cap0, b = b0;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            cm[k] = sc.cmap ? sc.cmap[INTERIOR ? cap : min(cap, cap_last)] : cap;
+            cap += step_q; b += step_r;
+            if (b >= beam) { b -= beam; ++cap; }
+        }
+    }
+    const float *sp = slab + rl0 * S::LD + cq * 4;
+    int b = b0;
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+        epilogue_slab_fill<TI, TJ>(acc, slab, i);
+        epilogue_slab_sync();
+#pragma unroll
+        for (int p = 0; p < Wk::PASSES; ++p) {
+            const int row = row0 + i * 32 + p * RPP + rl0;
+            const int bcur = b;
+            b += step_r;
+            if (b >= beam) b -= beam;
+            if (!INTERIOR && !(col_live && row < a.M)) continue;
+            float4 v = *reinterpret_cast<const float4 *>(sp + p * RPP * S::LD);
+            v.x *= a.scale; v.y *= a.scale; v.z *= a.scale; v.w *= a.scale;
+            if (has_bias) { v.x += bq.x; v.y += bq.y; v.z += bq.z; v.w += bq.w; }
+            if (is_q) {
+                *reinterpret_cast<float4 *>(a.C + (size_t)row * a.ldc + col) = v;
+            } else {
+                const size_t srow = (size_t)cm[i * Wk::PASSES + p] * beam + bcur;
+                const size_t el = srow * row_el + cell;
+                if (sc.bf16) {
+                    bf16x4 t;
+                    t[0] = (__bf16)v.x; t[1] = (__bf16)v.y; t[2] = (__bf16)v.z; t[3] = (__bf16)v.w;
+                    *reinterpret_cast<bf16x4 *>(reinterpret_cast<__bf16 *>(cache) + el) = t;
+                } else
+                    *reinterpret_cast<float4 *>(cache + el) = v;
+            }
+        }
+        epilogue_slab_sync();
+    }
+}
+
+// wave-uniform: the wavefront's TI x 32 rows and TJ x 32 columns lie inside the matrix and start at a multiple of 32 rows
+template <int TI, int TJ>
+__device__ __forceinline__ bool epilogue_interior(int row0, int col0, const EpiArgs &a) {
+    return (row0 & 31) == 0 && row0 + TI * 32 <= a.M && col0 + TJ * 32 <= a.N;
+}
+
 // the activation code becomes a compile-time constant of the element loops (one switch per tile, not per element)
 template <int TI, int TJ, int MODE, bool AHEAD = false>
 __device__ __forceinline__ void epilogue_lds_dispatch(const f32x16 (&acc)[TI][TJ], float *slab, int row0, int col0,
                                                       const EpiArgs &a) {
+    if constexpr (MODE == 1 && 64 % EpiWalk<TJ, 2>::LPR == 0 && EpiWalk<TJ, 2>::PASSES * 64 == 32 * EpiWalk<TJ, 2>::LPR) {
+        if (a.fmt == PK_F16X2 && !a.resid_pk && epilogue_interior<TI, TJ>(row0, col0, a)) {
+            switch (a.act) {
+                case CAPDEC_ACT_GELU_NEW: epilogue_lds_wave_h2_interior<TI, TJ, CAPDEC_ACT_GELU_NEW>(acc, slab, row0, col0, a); break;
+                case CAPDEC_ACT_QUICK_GELU: epilogue_lds_wave_h2_interior<TI, TJ, CAPDEC_ACT_QUICK_GELU>(acc, slab, row0, col0, a); break;
+                case CAPDEC_ACT_RELU: epilogue_lds_wave_h2_interior<TI, TJ, CAPDEC_ACT_RELU>(acc, slab, row0, col0, a); break;
+                case CAPDEC_ACT_TANH: epilogue_lds_wave_h2_interior<TI, TJ, CAPDEC_ACT_TANH>(acc, slab, row0, col0, a); break;
+                default: epilogue_lds_wave_h2_interior<TI, TJ, CAPDEC_ACT_NONE>(acc, slab, row0, col0, a); break;   // (RESID_RELU acts on a residual only)
+            }
+            return;
+        }
+    }
     switch (a.act) {
         case CAPDEC_ACT_GELU_NEW: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_GELU_NEW, AHEAD>(acc, slab, row0, col0, a); break;
         case CAPDEC_ACT_QUICK_GELU: epilogue_lds_wave<TI, TJ, MODE, CAPDEC_ACT_QUICK_GELU, AHEAD>(acc, slab, row0, col0, a); break;
@@ -206,8 +382,13 @@ __device__ __forceinline__ void epilogue_lds(const f32x16 (&acc)[G::TI][G::TJ], 
     float *slab = reinterpret_cast<float *>(smem + wave * EpiSlab<G::TJ>::BYTES);
     const int row0 = a.m0 + wm * G::TI * 32, col0 = a.n0 + wn * G::TJ * 32;
     if (a.packed) epilogue_lds_dispatch<G::TI, G::TJ, 1>(acc, slab, row0, col0, a);
-    else if (a.sc && a.sc->kc) epilogue_lds_wave<G::TI, G::TJ, 2, CAPDEC_ACT_NONE, AHEAD>(acc, slab, row0, col0, a);
-    else epilogue_lds_dispatch<G::TI, G::TJ, 0, AHEAD>(acc, slab, row0, col0, a);
+    else if (a.sc && a.sc->kc) {
+        if constexpr (AHEAD) {
+            if (epilogue_interior<G::TI, G::TJ>(row0, col0, a)) epilogue_lds_wave_qkv<G::TI, G::TJ, true>(acc, slab, row0, col0, a);
+            else epilogue_lds_wave_qkv<G::TI, G::TJ, false>(acc, slab, row0, col0, a);
+        } else
+            epilogue_lds_wave<G::TI, G::TJ, 2, CAPDEC_ACT_NONE, AHEAD>(acc, slab, row0, col0, a);
+    } else epilogue_lds_dispatch<G::TI, G::TJ, 0, AHEAD>(acc, slab, row0, col0, a);
 }
 
 }  // namespace capdec
