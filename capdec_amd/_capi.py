@@ -161,6 +161,8 @@ SIGNATURES = {
                                             _VP, _VP, _VP, _VP, _VP]),
     "capdec_decode_contrastive": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                             _VP, _VP, _VP]),
+    "capdec_decode_guided": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                       C.c_float, _VP, _VP, _VP, _VP]),
     "capdec_gemm_f32": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                   _VP, C.c_int, C.c_int]),
     "capdec_preprocess_images": (C.c_int, [_VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

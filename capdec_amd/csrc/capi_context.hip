@@ -12,7 +12,7 @@ const char *const kFamilyNames[F_COUNT] = {"gemm_f32", "gemm_f32_lmhead_topk", "
                                            "gemm_bf16x3_lmhead_topk", "gemm_bf16x3p", "gemm_x1",
                                            "gemm_x1_lmhead_topk", "gemm_f16x2p", "gemm_f16x2p_lmhead_topk",
                                            "pack_activations", "lmhead_second_pass", "nearest_topk",
-                                           "contrastive_select"};
+                                           "contrastive_select", "guided"};
 
 int prof_collect(capdec_ctx *c) {
     if (c->prof.recs.empty()) return 0;

@@ -6,6 +6,7 @@
 //                     lm_head, capdec_gemm_f32
 //   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam / sampling decode loop
 //                     (the sampling kernel itself: sample.hip; the logits processors' kernels: process.hip)
+//   guided.hip        capdec_decode_guided: classifier-free guidance on the greedy / beam loop (its combine and mirror kernels)
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   nearest.hip       capdec_nearest_tokens: nearest table rows by cosine similarity (the normalised-wte cache, row blocks)
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
@@ -120,7 +121,7 @@ struct ResNet {
 };
 
 enum Family { F_GEMM = 0, F_LMHEAD, F_ATTN_DEC, F_ATTN_PRE, F_LN, F_EMBED, F_SELECT, F_MAP_ATTN, F_OTHER, F_GEMM_X3,
-              F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_NEAREST, F_CONTRAST, F_COUNT };
+              F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_NEAREST, F_CONTRAST, F_GUIDED, F_COUNT };
 extern const char *const kFamilyNames[F_COUNT];
 constexpr int PROF_SLOTS = 24;   // capdec_profile_get fills at most this many families (engine.py sizes its arrays by it)
 static_assert(F_COUNT <= PROF_SLOTS, "profile arrays too small");
@@ -185,7 +186,7 @@ struct capdec_ctx {
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
     unsigned long long train_drop_seed = 0;  // ... key of the Philox keep-mask stream (counter = element, train step)
     DBuf slogits;          // sampling decode, logits processors: fp32 logits of one row block, [min(rows, tune.sample_rows), ld]
-                           // (decode.hip: lm_head_rows)
+                           // (decode.hip: lm_head_rows; the guided decode keeps a block's partner rows behind it: guided.hip)
     DBuf s_plan, s_rows, s_logit, s_bad;   // capdec_score (score.hip): the call's plan [lens | row offsets | h rows | targets], a
                                            // chunk's scored rows of h [R, d], their label logits [R], first tainted position [nc]
     int stat_score_chunks = 0;             // chunks of the last capdec_score call (capdec_score_chunks)
@@ -372,6 +373,8 @@ int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float in
                  const GreedyState &gs, bool proc, int step, int beam, const int *hist);
 int poll_alive(capdec_ctx *c, int *alive);
 int chunk_captions(capdec_ctx *c, int n, int beam, int ctx, size_t extra_per_cap = 0);
+// ... and the guided decode (guided.hip): ln_f over R rows of h (row stride ldh) + the plain lm_head GEMM -> logits [R, ld]
+int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float *logits, int ld);
 
 // ---- nearest.hip
 void drop_wte_norm(capdec_ctx *c);      // the normalised copy of wte and its planes (wte was reloaded or updated)

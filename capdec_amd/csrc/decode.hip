@@ -154,7 +154,7 @@ int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float 
 
 // ln_f over `R` rows of h (row stride ldh floats, starting at h0) then the plain lm_head GEMM over wte:
 // -> logits fp32 [R, ld]  (the full rows: capdec_gpt2_logits and the sampling decode; greedy / beam never materialise them)
-static int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float *logits, int ld) {
+int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float *logits, int ld) {
     const Gpt2 &g = c->gpt;
     const int d = g.d;
     if (use_packed_a(c, d))   // same operand path as the decode loop's fused lm_head (bf16 mode: bf16 operands)

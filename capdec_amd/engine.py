@@ -632,6 +632,57 @@ class Engine:
                   "capdec_decode_contrastive")
         return (ids, lens, trace) if return_trace else (ids, lens)
 
+    def decode_guided(self, prefix_embed: torch.Tensor, negative_embed: torch.Tensor, guidance_scale: float, stop_id: int,
+                      beam_size: int = 1, entry_length: int = 67, temperature: float = 1.0, alt_stop_id: int = 764, *,
+                      repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                      min_length: Optional[int] = None, logit_bias=None, return_order: bool = False):
+        """classifier-free guidance (capdec_decode_guided; ``guidance_scale`` of ``transformers.generate``): every caption is
+        decoded from ``prefix_embed`` [n, P, d] and, in lock-step with the same tokens, from its negative prefix --
+        ``negative_embed`` [P, d] or [1, P, d] (one for all) or [n, P, d] -- and the next token comes from
+        ``guidance_scale * log_softmax(l_cond) + (1 - guidance_scale) * log_softmax(l_neg)``, which takes the place of the
+        raw logits in front of the processors.  ``beam_size`` 1 -> (ids [n, T], lens [n]) as :meth:`decode_greedy`
+        (``alt_stop_id`` counts there only); 2..8 -> (ids [n, beam, T], lens, scores [n, beam]) sorted like
+        :meth:`decode_beam`'s, plus its order [n, beam] with ``return_order``.  ``guidance_scale`` must be finite and >= 1; 1 is off: the plain call, bit for bit.  The
+        keyword-only processors as in :meth:`decode_greedy`; under guidance they see log-probabilities (all <= 0)."""
+        g = guidance_scale
+        if isinstance(g, bool) or not isinstance(g, (int, float, np.floating, np.integer)) or not (g >= 1 and math.isfinite(g)):
+            raise CapdecError(f"decode_guided: guidance_scale must be a finite number >= 1, got {g!r}")
+        if isinstance(beam_size, bool) or not isinstance(beam_size, (int, np.integer)) or not 1 <= beam_size <= 8:
+            raise CapdecError(f"decode_guided: beam_size must be an integer in 1..8, got {beam_size!r}")
+        if isinstance(entry_length, bool) or not isinstance(entry_length, (int, np.integer)) or entry_length < 1:
+            raise CapdecError(f"decode_guided: entry_length must be a positive integer, got {entry_length!r}")
+        for name, t in (("prefix_embed", prefix_embed), ("negative_embed", negative_embed)):
+            if not isinstance(t, torch.Tensor) or not torch.is_floating_point(t):
+                raise CapdecError(f"decode_guided: {name} must be a floating-point tensor")
+        if prefix_embed.dim() != 3:
+            raise CapdecError(f"decode_guided: prefix_embed must be [n, P, d], got {tuple(prefix_embed.shape)}")
+        n, P, d = (int(s) for s in prefix_embed.shape)
+        neg = negative_embed.unsqueeze(0) if negative_embed.dim() == 2 else negative_embed
+        if neg.dim() != 3 or tuple(neg.shape[1:]) != (P, d) or int(neg.shape[0]) not in (1, n):
+            raise CapdecError(f"decode_guided: negative_embed must be [P, d], [1, P, d] or [n, P, d] = [{n}, {P}, {d}], got "
+                              f"{tuple(negative_embed.shape)}")
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias):
+            out = self._decode_guided(prefix_embed, neg, float(g), stop_id, int(beam_size), int(entry_length), temperature,
+                                      alt_stop_id)
+        return out if return_order or beam_size == 1 else out[:3]
+
+    def _decode_guided(self, prefix_embed, neg, gamma, stop_id, beam, entry_length, temperature, alt_stop_id):
+        p, q = self._dev(prefix_embed), self._dev(neg)
+        n, P, _ = p.shape
+        shape = (n,) if beam == 1 else (n, beam)
+        ids = torch.empty(*shape, entry_length, device=self.device, dtype=torch.int32)
+        lens = torch.empty(*shape, device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, beam, device=self.device, dtype=torch.float32) if beam > 1 else None
+        order = torch.empty(n, beam, device=self.device, dtype=torch.int32) if beam > 1 else None
+        self._sync_stream()
+        self._chk(self.lib.capdec_decode_guided(self._h, p.data_ptr(), q.data_ptr(), int(q.shape[0]), n, P, beam, gamma,
+                                                int(stop_id), int(alt_stop_id), entry_length, float(temperature),
+                                                ids.data_ptr(), lens.data_ptr(),
+                                                scores.data_ptr() if scores is not None else None,
+                                                order.data_ptr() if order is not None else None), "capdec_decode_guided")
+        return (ids, lens) if beam == 1 else (ids, lens, scores, order)
+
     # ------------------------------------------------------------------ scoring
     def score(self,prefix_embed: torch.Tensor, tokens: torch.Tensor, lens=None, ignore_id: int = -1,
               temperature: float = 1.0, return_top1: bool = False):

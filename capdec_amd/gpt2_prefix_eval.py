@@ -6,7 +6,9 @@ into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``
 ``generate_diverse_beam_batch`` are ``generate_beam`` with diverse (group) beam search (``capdec_decode_beam_groups``:
 ``num_beam_groups`` / ``diversity_penalty``), for callers who want beams that differ.  ``generate_samples`` /
 ``generate_samples_batch`` make ``top_p``, ``temperature`` and ``entry_count`` live: nucleus sampling
-(``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178).
+(``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178).  ``generate_guided`` /
+``generate_guided_batch`` decode under classifier-free guidance against a negative prefix (``capdec_decode_guided``:
+``guidance_scale`` of ``transformers.generate``), greedy or beam.
 
 Logits processors (``engine.LogitsProcessors``; the contract: include/capdec.h).  The batched functions take them as
 keyword-only arguments (None: not given); ``generate2`` / ``generate_beam`` keep the reference's signatures and read
@@ -337,6 +339,69 @@ def generate_contrastive(model, tokenizer, tokens=None, prompt=None, embed=None,
     n = int(lens.cpu()[0])
     out = [int(t) for t in ids.cpu().numpy()[0, :n]]
     return tokenizer.decode((prompt_ids or []) + out)
+
+
+# --------------------------------------------------------------------------- classifier-free guidance
+def _negative_prefix(model, embed: torch.Tensor, negative_embed) -> torch.Tensor:
+    """the negative prefix of the guided decode: ``negative_embed`` if given, else the documented default -- the mapper's
+    output for the all-zero CLIP embedding, ``model.clip_project(zeros)``, computed once per call and shared by all captions"""
+    if negative_embed is not None:
+        return negative_embed
+    zeros = torch.zeros(1, model.prefix_dim, device=embed.device, dtype=torch.float32)
+    return model.clip_project(zeros).reshape(1, model.prefix_length, -1)
+
+
+def decode_guided_ids(model: ClipCaptionModel, embed: torch.Tensor, negative_embed, stop_token_index: int,
+                      guidance_scale: float = 1.5, beam_size: int = 1, entry_length: int = 67, temperature: float = 1.,
+                      alt_stop_id: int = ALT_STOP_ID, *, repetition_penalty: Optional[float] = None,
+                      no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None, logit_bias=None):
+    """embed [N, P, d], negative_embed [P, d] / [1, P, d] / [N, P, d] (None: ``model.clip_project(zeros)``) -> the
+    classifier-free-guided decode (``capdec_decode_guided``): (ids [N, T], lens [N]) for ``beam_size`` 1, (ids [N, beam, T],
+    lens [N, beam], scores [N, beam]) best first otherwise"""
+    kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    return model.engine.decode_guided(embed, _negative_prefix(model, embed, negative_embed), guidance_scale, stop_token_index,
+                                      beam_size, entry_length, temperature, alt_stop_id, **kw)
+
+
+def generate_guided_batch(model, tokenizer, embed: torch.Tensor, negative_embed=None, guidance_scale: float = 1.5,
+                          beam_size: int = 1, entry_length: int = 67, stop_token: str = '.', temperature: float = 1., *,
+                          repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                          min_length: Optional[int] = None, logit_bias=None):
+    """``generate2_batch`` (``beam_size`` 1: one text per caption) / ``generate_beam_batch`` (the ``beam_size`` texts per
+    caption, best first) under classifier-free guidance against ``negative_embed`` (None: the mapper's output for the
+    all-zero CLIP embedding)"""
+    stop = tokenizer.encode(stop_token)[0]
+    out = decode_guided_ids(model, embed, negative_embed, stop, guidance_scale, beam_size, entry_length, temperature,
+                            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                            min_length=min_length, logit_bias=logit_bias)
+    ids, lens = out[0].cpu().numpy(), out[1].cpu().numpy()
+    if ids.ndim == 2:
+        return [tokenizer.decode(list(ids[r, :lens[r]])) for r in range(ids.shape[0])]
+    return [[tokenizer.decode(ids[r, b, :int(lens[r, b])]) for b in range(ids.shape[1])] for r in range(ids.shape[0])]
+
+
+def generate_guided(model, tokenizer, tokens=None, prompt=None, embed=None, negative_embed=None, guidance_scale: float = 1.5,
+                    beam_size: int = 1, entry_length=67, temperature=1., stop_token: str = '.'):
+    """``generate2`` (``beam_size`` 1 -> str) / ``generate_beam`` (-> the list of ``beam_size`` texts, best first) under
+    classifier-free guidance: one caption ([1, P, d], tokens or a prompt) against ``negative_embed`` ([P, d] or [1, P, d]; None:
+    the mapper's output for the all-zero CLIP embedding).  Prompt tokens stay in front as in those functions.  (Logits
+    processors: ``model.logits_processors``.)"""
+    model.eval()
+    prefix, prompt_ids = _prefix_from(model, tokenizer, tokens, prompt, embed)
+    if prefix.shape[0] != 1:
+        raise CapdecError("generate_guided takes one caption ([1, P, d]); use generate_guided_batch for [N, P, d]")
+    stop = tokenizer.encode(stop_token)[0]
+    out = decode_guided_ids(model, prefix, negative_embed, stop, guidance_scale, beam_size, entry_length, temperature)
+    ids, lens = out[0].cpu().numpy()[0], out[1].cpu().numpy()[0]
+    if ids.ndim == 1:
+        return tokenizer.decode((prompt_ids or []) + [int(t) for t in ids[:int(lens)]])
+    texts = []
+    for b in range(ids.shape[0]):
+        toks = ids[b, :int(lens[b])]
+        if prompt_ids is not None:      # as generate_beam: the prompt tokens stay in the output, the row is cut at seq_lengths
+            toks = np.concatenate([np.asarray(prompt_ids, dtype=toks.dtype), ids[b]])[:int(lens[b])]
+        texts.append(tokenizer.decode(toks))
+    return texts
 
 
 # --------------------------------------------------------------------------- prefix interpretation and editing

@@ -413,6 +413,38 @@ int capdec_decode_contrastive(capdec_ctx *ctx, const float *d_prefix, int n, int
                               int stop_id, int alt_stop_id, int entry_length,
                               int32_t *d_ids /* [n, T] */, int32_t *d_lens /* [n] */,
                               float *d_trace /* [n, T, 2] or NULL */);
+/* Classifier-free guidance (`guidance_scale` of transformers.generate; Kornblith et al. 2023 for captioning) on the greedy
+ * (beam == 1) and the beam (beam 2..8) decode.  For caption r: p_r = d_prefix[r] [P, d]; q_r = its negative prefix [P, d],
+ * d_neg_prefix[r] (neg_n == n) or d_neg_prefix[0] for every caption (neg_n == 1).  A hypothesis of r after i emitted tokens
+ * t_0..t_{i-1} has two contexts, (p_r, t_0..t_{i-1}) and (q_r, t_0..t_{i-1}): the same tokens, only the prefix differs.
+ * With l and m the raw fp32 lm_head logits [V] of the two contexts and gamma = guidance_scale:
+ *   c_j = l_j - logsumexp(l),  u_j = m_j - logsumexp(m),  g_j = gamma * c_j + (1 - gamma) * u_j
+ * (fp32, every operation rounded on its own, in this form: equal rows give g = c up to rounding).  g takes the place of
+ * the raw logits in everything that follows, in the existing order: the logits processors that are set (steps 1-4 of
+ * capdec_set_logits_processors; the history is the hypothesis's own tokens), the division by the temperature, then the
+ * call's rule -- the arg-max for beam == 1 (stop_id / alt_stop_id as in capdec_decode_greedy; the temperature cannot change
+ * it), log_softmax and capdec_decode_beam's unchanged bookkeeping otherwise (alt_stop_id is ignored there).  Two consequences:
+ *   1. the processors see log-probabilities (all <= 0), not raw logits, as in transformers: repetition_penalty always
+ *      multiplies, so gamma -> 1+ with a repetition penalty is not continuous with gamma == 1;
+ *   2. unlike transformers' beam search, the guided scores are renormalised (log_softmax of g / temperature) before they
+ *      enter the beam sums -- what this library does after its processors anyway.
+ * Both logsumexps and everything else per row have a fixed summation order and one workgroup owns one (cond, neg) row pair
+ * whatever the launch holds: a caption's result does not depend on the batch size, the row blocks, the chunking or the
+ * compaction (capdec_set_batch_invariant's caveat applies to the GEMMs); pad columns of the logits are never touched.
+ * guidance_scale == 1 means off: the call IS capdec_decode_greedy / capdec_decode_beam (no negative rows, bit-identical
+ * results).  Outputs have the shapes and the meaning of capdec_decode_greedy (beam == 1: d_ids [n, T], d_lens [n];
+ * d_scores / d_order unused) and of capdec_decode_beam (d_ids [n, beam, T], d_lens, d_scores [n, beam], d_order [n, beam]
+ * or NULL); limits as for those calls, the negative prefix has the same P.  The call honours the logits processors and
+ * bias, capdec_set_compact, capdec_set_batch_invariant, capdec_set_kv_budget (a caption and its partner always share a
+ * chunk and both count) and the GEMM mode; capdec_decode_stats / _step_rows count rows as launched: both halves.  Every
+ * step materialises the logits of at most 2 * CAPDEC_SAMPLE_ROWS rows.  Errors (capdec_last_error, before any launch): a
+ * guidance_scale that is NaN, infinite or < 1; neg_n other than 1 or n; beam outside 1..8; a context that is too long;
+ * head_dim other than 64. */
+int capdec_decode_guided(capdec_ctx *ctx, const float *d_prefix, const float *d_neg_prefix, int neg_n /* 1 or n */,
+                         int n, int P, int beam /* 1 = greedy, 2..8 = beam */, float guidance_scale,
+                         int stop_id, int alt_stop_id /* greedy only */, int entry_length, float temperature,
+                         int32_t *d_ids, int32_t *d_lens, float *d_scores /* beam */,
+                         int32_t *d_order /* beam, may be NULL */);
 /* Nucleus-sampling decode: the greedy loop with the arg-max replaced by one draw per step.  For a row of logits l, with
  * s = l / (temperature > 0 ? temperature : 1) and p = softmax(s): token j is in the nucleus iff it is the arg-max or the
  * sum of p[i] over all p[i] > p[j] is <= top_p (the filter of reference gpt2_prefix_eval.py:166-175; exactly equal
