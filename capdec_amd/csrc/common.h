@@ -356,6 +356,40 @@ int launch_topk_merge_rows(hipStream_t st, const float *cand_val, const int *can
 // rows src_rows[i], i < *count_dev, of a packed operand [*, K] (PK_F16X2 or a one-plane format) -> rows i of `out`
 int launch_gather_packed_rows(hipStream_t st, const void *packed, int K, const int *src_rows, const int *count_dev,
                               int rows_cap, void *out, int fmt);
+// ---- the sparse lm_head (decode.hip: lm_head_select): no candidates from the first pass; per row the (row, tile) PAIRS
+// whose tile maximum reaches the row's fifth largest are recomputed with k = 5 by a launch grouped by tile, then merged.
+constexpr int LM_SPARSE_SHIFT = 3;
+constexpr int LM_SPARSE_CAP = 1 << LM_SPARSE_SHIFT;        // pairs a row may have (five, plus exact ties at the fifth maximum); more: full second pass
+constexpr int LM_SPARSE_MIN_TILES = 40;  // below that, five tiles of all are no saving
+constexpr int LM_SPARSE_MIN_ROWS = 12288; // rows from which the route pays: +1.5 % at 25 000 rows, -1.1 % at 3125 (its ~13 extra small
+                                          // launches cost ~100 us a step, the first pass saves ~18 ns per row: break-even near 7700 rows;
+                                          // profiles/lm_head_sparse_ab.txt)
+constexpr int LM_HARD_SLICES = 2;       // the full second pass of this route runs in that many slices of its flagged rows
+struct SparseLm {        // device bookkeeping of one step (ints)
+    int *tile_cnt;       // [ntiles]  pairs per column tile -- zeroed by the caller before launch_lm_tile_select
+    int *tile_cur;       // [ntiles]  scatter cursors
+    int *tile_off;       // [ntiles]  where a tile's bucket starts in the pair list
+    int *nblk;           // [1]       blocks of the grouped launch
+    int *slice_cnt;      // [LM_HARD_SLICES]  flagged rows each slice of the full second pass takes
+    int *blk_tab;        // [blocks_cap][3]   (tile, first pair, pairs <= 256)
+    int *row_cnt;        // [rows]    pairs of a row; 0 = the row takes the full second pass
+    int *row_tiles;      // [rows][LM_SPARSE_CAP]  their tiles, ascending
+    int *slot_of;        // [rows * LM_SPARSE_CAP]  the pair list, bucketed by tile: candidate list row * LM_SPARSE_CAP + s of a pair
+    int slice_rows;      // rows per slice of the full second pass
+    static int blocks_cap(int rows, int ntiles) { return (rows * LM_SPARSE_CAP + 255) / 256 + ntiles; }
+};
+// logsumexp [rows], the pairs of every row, the rows that need the full pass instead (flag_rows as launch_topk_merge_k3);
+// then -- three small launches -- the pairs counted per tile, buckets / block table / slice counts, the pairs placed
+int launch_lm_tile_select(hipStream_t st, const float *tile_max, const float *tile_sum, int rows, int ntiles, float *lse,
+                          const SparseLm &s, int *flag_rows, int *flag_count, int *flag_total);
+// the grouped pass (gemm_h2w.hip): block b of blk_tab computes its pairs' rows (slot_of[p] >> slot_shift of Apacked, read in
+// place) against its one column tile, k = 5 candidates of pair p -> lists slot_of[p] of cand_val / cand_idx
+int launch_gemm_h2w_topk_grouped(hipStream_t st, const void *Apacked, const void *Bpacked, const int *nblk_dev,
+                                 const int *blk_tab, const int *slot_of, int slot_shift, int blocks_cap, int N, int K,
+                                 float inv_temp, float *cand_val, int *cand_idx);
+// top 5 of the candidate lists of a row's pairs -> top_val / top_idx [rows, 5] (rows with row_cnt = 0 untouched)
+int launch_lm_sparse_merge(hipStream_t st, const float *cand_val, const int *cand_idx, const int *row_cnt, int rows,
+                           float *top_val, int *top_idx);
 struct BeamState {
     int *tokens = nullptr;      // [ncap, beam, T]
     float *scores = nullptr;    // [ncap, beam]  running SUM of log-probs (reference `scores`)

@@ -36,7 +36,10 @@ struct Tuning {
     bool lmhead_k3 = true;        // CAPDEC_LMHEAD_K3=0: the wide lm_head keeps k candidates per tile (no exact second pass)
     int lmhead_k3_max = 60;       // CAPDEC_LMHEAD_K3_MAX: per mille of the rows taking the second pass above which a decode
                                   //   call goes back to k per tile (checked at the poll points; break-even is ~80)
-    int sample_rows = 2048;       // CAPDEC_SAMPLE_ROWS: rows of fp32 logits the sampling decode (and a decode with logits processors) materialises at a time (2048 rows of
+    int lmhead_sparse = 1;        // CAPDEC_LMHEAD_SPARSE: 0 = the 3-per-tile route where the default (1) keeps no candidates per tile at all
+                                  //   and recomputes, per row, the five tiles that can hold its top 5 (k = 5, wide tile, >= 40 column
+                                  //   tiles, from 12288 rows: LM_SPARSE_MIN_ROWS); 2 = that route from the wide tile's first row (tests)
+    int sample_rows = 2048;      // CAPDEC_SAMPLE_ROWS: rows of fp32 logits the sampling decode (and a decode with logits processors) materialises at a time (2048 rows of
                                   //   GPT-2's vocabulary = 412 MB); a step with more rows loops lm_head + sampler over row blocks
     int score_rows = 16384;       // CAPDEC_SCORE_ROWS: padded activation rows (captions x (prefix + longest caption - 1)) one chunk of
                                   //   capdec_score pushes through the GPT-2 body at a time (16384 rows = 1.2 GB of K / V + 0.4 GB of

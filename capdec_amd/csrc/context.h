@@ -199,6 +199,7 @@ struct capdec_ctx {
     DBuf pbias, pcorr;     // the logit bias [vocab]; a row block's logp shift under top_k (decode.hip: lm_head_rows)
     DBuf lmflag, xpk2;     // fused lm_head with 3 candidates per tile: [count, total, rows...] of the rows whose top 5 need
                            // the exact second pass; their compacted packed A operand (decode.hip: lm_head_select)
+    DBuf lmsp;             // sparse lm_head: a step's SparseLm bookkeeping (common.h)
     DBuf m_hid, m_lin, m_seq, m_x, m_qkv, m_att, m_ff;
     DBuf m_kvc;            // encoder-decoder mapper: keys / values of the cross layers, [n * clip_len, n_layers * 2d]
     DBuf t_idx, t_patch, t_pout, p_desc, p_inter, splitk, absmax;
@@ -291,7 +292,13 @@ int topk_workspace(capdec_ctx *c, int rows, int ntiles, int k, TopkOut *o);
 // allows it (the wide two-plane tile; the one-plane kernel from 2048 rows); *k3 reports whether it did -- the rows the
 // merge then flags need gemm_topk_dev.  The packed modes leave LN(h) in c->xpk.
 int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const float *lnb, float eps, const float *W,
-                 int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3);
+                 int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3, bool no_cand = false);
+// (no_cand: max and sum exp per (row, tile) only, no candidates -- the sparse route of lm_head_select; it asks first whether
+//  a launch of M rows takes the wide two-plane tile, the only kernel with that form: lm_head_wide_tile)
+int lm_head_wide_tile(capdec_ctx *c, const float *W, int M, int N, int K, bool *wide);
+// ... the sparse route's grouped pass (gemm_h2w.hip: gemm_h2w_topk_grouped_kernel) over the pairs of s, rows read from Apk
+int gemm_topk_grouped(capdec_ctx *c, const void *Apk, const float *W, const SparseLm &s, int blocks_cap, int N, int K,
+                      float inv_temp, float *cand_val, int *cand_idx);
 // ... its exact second pass: k = 5 lists for the *m_dev rows of the packed operand Apk (in the format of the mode)
 int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_dev, int N, int K, float inv_temp,
                   const TopkOut &o);

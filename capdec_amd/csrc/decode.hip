@@ -110,11 +110,89 @@ int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv) {
     return stack_body(c, cfg, s, kv);
 }
 
+// The sparse route of lm_head_select (k = 5, the wide two-plane kernel, >= LM_SPARSE_MIN_TILES column tiles): the first pass
+// keeps NO candidates, only max and sum exp per (row, tile), which the logsumexp needs anyway.  A row's top 5 lie in the tiles
+// whose maximum reaches the row's fifth largest tile maximum -- five tiles of 393 unless maxima tie exactly -- so those
+// (row, tile) pairs alone are computed again with the k = 5 epilogue: bucketed by tile, one grouped launch that reads the
+// pairs' packed rows where the LayerNorm left them, one merge per row.  A recomputed logit has the bits of the first pass (same kernel geometry and order), so
+// the result is the k = 5 result.  Rows with more than LM_SPARSE_CAP pairs or a tile maximum that is not finite take the
+// full second pass of the three-candidate route instead, through the same flag list and counters; it runs in
+// LM_HARD_SLICES slices so that its partial lists need room for a fraction of the rows only.
+static int lm_head_sparse(capdec_ctx *c, const float *h0, int ldh, int R, float inv_temp) {
+    const Gpt2 &g = c->gpt;
+    const int d = g.d, nt = gemm_tiles_n(g.vocab), k = 5;
+    const int slice = (R + LM_HARD_SLICES - 1) / LM_HARD_SLICES;
+    const int bcap = SparseLm::blocks_cap(R, nt);
+    CAPDEC_TRY(c->tmax.ensure((size_t)R * nt * 4));
+    CAPDEC_TRY(c->tsum.ensure((size_t)R * nt * 4));
+    CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
+    CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
+    CAPDEC_TRY(c->topi.ensure((size_t)R * k * 4));
+    // candidate lists: one per pair, then (the pairs' merge has run) one per (row of a slice, tile)
+    const size_t lists = std::max((size_t)R * LM_SPARSE_CAP, (size_t)slice * nt);
+    CAPDEC_TRY(c->cval.ensure(lists * k * 4));
+    CAPDEC_TRY(c->cidx.ensure(lists * k * 4));
+    CAPDEC_TRY(c->lmflag.ensure(((size_t)R + 2) * 4));
+    CAPDEC_TRY(c->xpk2.ensure(x3_packed_bytes_host(slice, d)));
+    CAPDEC_TRY(c->lmsp.ensure(((size_t)3 * nt + 1 + LM_HARD_SLICES + 3 * (size_t)bcap + R + 2 * (size_t)R * LM_SPARSE_CAP) * 4));
+    SparseLm s;
+    s.tile_cnt = c->lmsp.as<int>();
+    s.tile_cur = s.tile_cnt + nt;
+    s.tile_off = s.tile_cur + nt;
+    s.nblk = s.tile_off + nt;
+    s.slice_cnt = s.nblk + 1;
+    s.blk_tab = s.slice_cnt + LM_HARD_SLICES;
+    s.row_cnt = s.blk_tab + 3 * (size_t)bcap;
+    s.row_tiles = s.row_cnt + R;
+    s.slot_of = s.row_tiles + (size_t)R * LM_SPARSE_CAP;
+    s.slice_rows = slice;
+    const TopkOut o{c->tmax.as<float>(), c->tsum.as<float>(), c->cval.as<float>(), c->cidx.as<int>()};
+    float *topv = c->topv.as<float>();
+    int *topi = c->topi.as<int>();
+    int *cnt = c->lmflag.as<int>(), *total = cnt + 1, *rows = cnt + 2;
+    bool k3 = false;
+    CAPDEC_TRY(ln_gemm_topk(c, h0, ldh, g.lnfw, g.lnfb, g.eps, g.wte, R, g.vocab, d, k, inv_temp, o, false, &k3, /*no_cand=*/true));
+    {
+        ProfScope ps(c, F_SELECT);
+        CAPDEC_HIP(hipMemsetAsync(cnt, 0, sizeof(int), c->stream));
+        CAPDEC_HIP(hipMemsetAsync(s.tile_cnt, 0, (size_t)nt * sizeof(int), c->stream));
+        CAPDEC_TRY(launch_lm_tile_select(c->stream, o.tile_max, o.tile_sum, R, nt, c->lse.as<float>(), s, rows, cnt, total));
+    }
+    {
+        ProfScope ps(c, F_LMHEAD_2ND);
+        CAPDEC_TRY(gemm_topk_grouped(c, c->xpk.p, g.wte, s, bcap, g.vocab, d, inv_temp, o.cand_val, o.cand_idx));
+    }
+    {
+        ProfScope ps(c, F_SELECT);
+        CAPDEC_TRY(launch_lm_sparse_merge(c->stream, o.cand_val, o.cand_idx, s.row_cnt, R, topv, topi));
+    }
+    // the flagged rows: gather, k = 5 kernel over every tile, merge -- per slice (tile_max / tile_sum and the pairs' lists are
+    // dead by now: their buffers take the slices' partial lists)
+    ProfScope ps(c, F_LMHEAD_2ND);
+    for (int sl = 0; sl < LM_HARD_SLICES && sl * slice < R; ++sl) {
+        const int cap = std::min(slice, R - sl * slice);
+        const int *n_dev = s.slice_cnt + sl, *src = rows + (size_t)sl * slice;
+        CAPDEC_TRY(launch_gather_packed_rows(c->stream, c->xpk.p, d, src, n_dev, cap, c->xpk2.p, pack_fmt(c)));
+        CAPDEC_TRY(gemm_topk_dev(c, c->xpk2.p, g.wte, n_dev, g.vocab, d, inv_temp, o));
+        CAPDEC_TRY(launch_topk_merge_rows(c->stream, o.cand_val, o.cand_idx, n_dev, src, cap, nt, topv, topi));
+    }
+    c->lmflag_live = true;
+    c->k3_rows += R;
+    return 0;
+}
+
 // ln_f over `R` rows of h (row stride ldh floats, starting at h0) then the fused lm_head:
 // -> lse [R], topv/topi [R, k]
 int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp) {
     const Gpt2 &g = c->gpt;
     const int d = g.d, nt = gemm_tiles_n(g.vocab);
+    const bool k3_ok = c->tune.lmhead_k3 && k == 5 && !c->k3_off;
+    const int sparse = c->tune.lmhead_sparse;       // (2: from the wide tile's first row, tests)
+    if (k3_ok && sparse && (sparse >= 2 || R >= LM_SPARSE_MIN_ROWS) && nt >= LM_SPARSE_MIN_TILES && nt <= 1024) {
+        bool wide = false;
+        CAPDEC_TRY(lm_head_wide_tile(c, g.wte, R, g.vocab, d, &wide));
+        if (wide) return lm_head_sparse(c, h0, ldh, R, inv_temp);
+    }
     TopkOut o;
     CAPDEC_TRY(topk_workspace(c, R, nt, k, &o));
     CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
@@ -124,8 +202,7 @@ int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float 
     // still strictly better than the row's fifth: with 393 tiles a rare event) and those rows alone go through the k = 5
     // kernel again, compacted; the result is the k = 5 result.
     bool k3 = false;
-    CAPDEC_TRY(ln_gemm_topk(c, h0, ldh, g.lnfw, g.lnfb, g.eps, g.wte, R, g.vocab, d, k, inv_temp, o,
-                            c->tune.lmhead_k3 && k == 5 && !c->k3_off, &k3));
+    CAPDEC_TRY(ln_gemm_topk(c, h0, ldh, g.lnfw, g.lnfb, g.eps, g.wte, R, g.vocab, d, k, inv_temp, o, k3_ok, &k3));
     if (k3) {
         CAPDEC_TRY(c->lmflag.ensure(((size_t)R + 2) * 4));
         CAPDEC_TRY(c->xpk2.ensure(x3_packed_bytes_host(R, d)));

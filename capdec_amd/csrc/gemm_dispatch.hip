@@ -236,10 +236,21 @@ static bool topk_wide_tile(const capdec_ctx *c, bool wide_ok, int M) {
     return wide_ok && !c->batch_invariant && ((c->tune.lmhead_wide && h2w >= 1 && M >= 2048) || h2w >= 2);
 }
 
+int lm_head_wide_tile(capdec_ctx *c, const float *W, int M, int N, int K, bool *wide) {
+    *wide = false;
+    if (c->gemm_mode != GEMM_F16X2 || !use_packed_a(c, K)) return 0;
+    const void *pl = nullptr;
+    bool wide_ok = false;
+    CAPDEC_TRY(planes_of(c, W, N, K, true, &pl, -1, &wide_ok));
+    *wide = topk_wide_tile(c, wide_ok, M);
+    return 0;
+}
+
 int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const float *lnb, float eps, const float *W,
-                 int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3) {
+                 int M, int N, int K, int k, float inv_temp, const TopkOut &o, bool k3_ok, bool *k3, bool no_cand) {
     const double flops = 2.0 * M * (double)N * K;
     *k3 = false;
+    CAPDEC_CHECK(!no_cand || (c->gemm_mode == GEMM_F16X2 && use_packed_a(c, K)), "ln_gemm_topk: only the wide two-plane kernel runs without candidates");
     if (!use_packed_a(c, K)) {
         CAPDEC_TRY(c->xl.ensure((size_t)M * K * 4));
         float *x = c->xl.as<float>();
@@ -261,9 +272,11 @@ int ln_gemm_topk(capdec_ctx *c, const float *h, int ldh, const float *lnw, const
     if (c->gemm_mode == GEMM_F16X2) {
         ProfScope ps(c, F_LMHEAD_H2, flops);
         if (topk_wide_tile(c, wide_ok, M)) {
+            if (no_cand) return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, 0, inv_temp, o);
             *k3 = k3_ok;
             return launch_gemm_h2w_topk(c->stream, c->xpk.p, pl, M, N, K, *k3 ? 3 : k, inv_temp, o);
         }
+        CAPDEC_CHECK(!no_cand, "ln_gemm_topk: only the wide two-plane kernel runs without candidates");
         return launch_gemm_f16x2p_topk(c->stream, c->xpk.p, pl, M, N, K, k, inv_temp, o, PK_F16X2);
     }
     if (mode_single(c)) {
@@ -281,6 +294,15 @@ int gemm_topk_dev(capdec_ctx *c, const void *Apk, const float *W, const int *m_d
     CAPDEC_TRY(planes_of(c, W, N, K, true, &pl));
     if (mode_single(c)) return launch_gemm_x1_topk_dev(c->stream, Apk, pl, m_dev, N, K, inv_temp, o, pack_fmt(c));
     return launch_gemm_h2w_topk_dev(c->stream, Apk, pl, m_dev, N, K, inv_temp, o);
+}
+
+int gemm_topk_grouped(capdec_ctx *c, const void *Apk, const float *W, const SparseLm &s, int blocks_cap, int N, int K,
+                      float inv_temp, float *cand_val, int *cand_idx) {
+    CAPDEC_CHECK(c->gemm_mode == GEMM_F16X2, "gemm_topk_grouped: two-plane operands only");
+    const void *pl = nullptr;
+    CAPDEC_TRY(planes_of(c, W, N, K, true, &pl));
+    return launch_gemm_h2w_topk_grouped(c->stream, Apk, pl, s.nblk, s.blk_tab, s.slot_of, LM_SPARSE_SHIFT, blocks_cap, N, K, inv_temp,
+                                        cand_val, cand_idx);
 }
 
 // gemm()'s rule for fp32 activations: the packed two-fp16-plane path in the f16x2 and the one-plane modes when K % 64 == 0

@@ -11,10 +11,14 @@ namespace capdec {
 // re-using the ring) and leave as per-(row, 128-column tile) max, sum exp(x - max) and top-k (value, column) -- the
 // arithmetic and the tie rules of epilogue_topk (gemm_epilogue.h), so the merge kernel sees the same partial lists
 // whichever tile height produced them.
-template <class G, int KSEL>
+// KSEL = 0: max and sum exp only (the sparse lm_head's first pass: the candidates come from a later pass over the few tiles
+// that can hold them, decode.hip: lm_head_select) -- the same bits as with any other KSEL.
+// GROUPED (that later pass, gemm_h2w_topk_grouped_kernel): the block's rows are rows m0 .. M-1 of a gathered operand, row
+// `row` of it writes its KSEL candidates to list slot_of[row]; max and sum exp are not written again.
+template <class G, int KSEL, bool GROUPED = false>
 __device__ __forceinline__ void epilogue_topk_w(const f32x16 (&acc)[G::TI][G::TJ], float scale, float *Ct, int M, int N,
                                                 int m0, int n0, int tn, int tiles_n, float *tile_max, float *tile_sum,
-                                                float *cand_val, int *cand_idx) {
+                                                float *cand_val, int *cand_idx, const int *slot_of = nullptr) {
     static_assert(G::BN == 128 && G::NW == 4 && G::SMEM_B >= 128 * CT_LD * 4, "top-k epilogue: 128-column tiles, 4 waves");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / G::WN, wn = wave % G::WN, half = lane >> 5, l32 = lane & 31;
@@ -51,12 +55,17 @@ __device__ __forceinline__ void epilogue_topk_w(const f32x16 (&acc)[G::TI][G::TJ
 #pragma unroll
             for (int j = 0; j < 8; ++j) se += __expf(v[j] - mx);
             se = row16_sum(se);
-            const size_t tbase = (size_t)row * tiles_n + tn;
-            if (row < M && sub == 0) {
-                tile_max[tbase] = mx;
-                tile_sum[tbase] = se;
+            if constexpr (GROUPED) {
+                const size_t tbase = row < M ? (size_t)slot_of[row] : 0;
+                row_tile_topk<KSEL>(v, mx, sub, n0, row < M, tbase, cand_val, cand_idx);
+            } else {
+                const size_t tbase = (size_t)row * tiles_n + tn;
+                if (row < M && sub == 0) {
+                    tile_max[tbase] = mx;
+                    tile_sum[tbase] = se;
+                }
+                row_tile_topk<KSEL>(v, mx, sub, n0, row < M, tbase, cand_val, cand_idx);
             }
-            row_tile_topk<KSEL>(v, mx, sub, n0, row < M, tbase, cand_val, cand_idx);
         }
         __syncthreads();
     }

@@ -84,10 +84,15 @@ __device__ __forceinline__ void w_sched_emit() {
 //                                                          [n0 + wn TJ 32 + j 32 + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)]
 // scaled by 2^11.  chunksA / chunksB = number of 32-row chunks the packed operands hold (rows padded to 128: block tiles
 // past the end re-read the last chunk; the epilogue drops those rows / columns).
-template <class G, bool TR>
+// GATHER (the grouped lm_head pass): row i of the block tile is row a_rows[i] >> a_shift of the packed operand Apk for
+// i < a_n (row 0 beyond: computed and dropped) -- the LDS-DMA takes a global address per lane, so the lane that fills (row
+// l, physical half p) of a 32-row chunk reads logical half p ^ ((l >> 3) & 1) of its source row wherever that row lies
+// (x3_group_offset); the LDS image, and with it everything after the DMA, is that of a contiguous block tile.
+template <class G, bool TR, bool GATHER = false>
 __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, const _Float16 *__restrict__ Bpk, int K,
                                              int tm, int tn, int chunksA, int chunksB, char *smem,
-                                             f32x16 (&acc)[G::TI][G::TJ]) {
+                                             f32x16 (&acc)[G::TI][G::TJ], const int *__restrict__ a_rows = nullptr,
+                                             int a_n = 0, int a_shift = 0) {
     constexpr int TI = G::TI, TJ = G::TJ, NS = G::NS, PPW = G::PPW, SB = G::STAGE_B;
     using SC = WSched<G>;
     const int t = threadIdx.x;
@@ -103,6 +108,13 @@ __device__ __forceinline__ void h2w_mainloop(const _Float16 *__restrict__ Apk, c
     for (int e = 0; e < PPW; ++e) {
         const int p = wave * PPW + e, c = p >> 1, pl = p & 1;
         const bool isA = c < G::CA;
+        if (GATHER && isA) {
+            const int i = c * 32 + (lane >> 1);
+            const int r = i < a_n ? a_rows[i] >> a_shift : 0;
+            src[e] = reinterpret_cast<const char *>(Apk) + (size_t)(r >> 7) * nk * H2_BLOCK_B + pl * X3_PLANE_B +
+                     (r & 127) * X3_ROW_B + (((lane & 1) ^ ((lane >> 4) & 1) ^ ((r >> 3) & 1)) << 4);
+            continue;
+        }
         const int g = isA ? min(tm * G::CA + c, chunksA - 1) : min(tn * G::CB + (c - G::CA), chunksB - 1);
         const char *base = reinterpret_cast<const char *>(isA ? Apk : Bpk);
         src[e] = base + (size_t)(g >> 2) * nk * H2_BLOCK_B + pl * X3_PLANE_B + (g & 3) * 1024 + lane * 16;
@@ -271,6 +283,31 @@ __global__ __launch_bounds__(G::THREADS, G::MINW) void gemm_h2w_topk_dev_kernel(
     }
 }
 
+// The grouped pass of the sparse lm_head (decode.hip: lm_head_select): block b of the table computes up to G::BM (row,
+// tile) pairs of ONE column tile -- blk_tab[3 b ..] = (column tile, first pair of the bucket list, pairs) -- and leaves the
+// k = 5 candidates of pair p in list slot_of[p]; the pair's activation row, slot_of[p] >> slot_shift, is read where the
+// LayerNorm left it (h2w_mainloop: GATHER).  Main loop, plane order, accumulator and scale are those of
+// gemm_h2w_topk_kernel, so a logit recomputed here has the bits the first pass gave it.  A persistent grid walks the
+// *nblk_dev blocks there are.
+template <class G>
+__global__ __launch_bounds__(G::THREADS, G::MINW) void gemm_h2w_topk_grouped_kernel(const _Float16 *__restrict__ Apk,
+                                                                                   const _Float16 *__restrict__ Bpk,
+                                                                                   const int *__restrict__ nblk_dev,
+                                                                                   const int *__restrict__ blk_tab,
+                                                                                   const int *__restrict__ slot_of,
+                                                                                   int slot_shift, int N, int K, float scale,
+                                                                                   float *cand_val, int *cand_idx) {
+    __shared__ __attribute__((aligned(16))) char smem[G::SMEM_B];
+    const int nblk = *nblk_dev;
+    for (int b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const int tn = blk_tab[3 * b], p0 = blk_tab[3 * b + 1], np = blk_tab[3 * b + 2];
+        f32x16 acc[G::TI][G::TJ];
+        h2w_mainloop<G, false, true>(Apk, Bpk, K, 0, tn, 0, ((N + 127) >> 7) * 4, smem, acc, slot_of + p0, np, slot_shift);
+        epilogue_topk_w<G, 5, true>(acc, scale, reinterpret_cast<float *>(smem), p0 + np, N, p0, tn * G::BN, tn, 0, nullptr,
+                                    nullptr, cand_val, cand_idx, slot_of);      // (ends with a barrier: the ring is free again)
+    }
+}
+
 using W256x128 = WGeo<2, 2, 4, 2, 3, 2>;      // 4 waves, 72 KB, two blocks per CU
 // (measured and removed, profiles/r3_gemm_geometries.txt: 128x128 at three blocks per CU, WGeo<2,2,2,2,3,3>, and at two,
 //  WGeo<2,2,2,2,4,2>: +-0 against the round-2 kernel; 256x256 on 8 waves, one block per CU: -4 .. -27 %; 256x256 on 4 waves
@@ -329,6 +366,13 @@ int launch_gemm_h2w_topk(hipStream_t st, const void *Apacked, const void *Bpacke
     const int tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
     dim3 grid(tiles_m * tiles_n), block(G::THREADS);
     const float scale = inv_temp / H2_LO_SCALE;
+    if (k == 0) {      // max and sum exp per (row, tile) only: the sparse lm_head's first pass
+        hipLaunchKernelGGL((gemm_h2w_topk_kernel<G, 0>), grid, block, 0, st, (const _Float16 *)Apacked,
+                           (const _Float16 *)Bpacked, M, N, K, scale, o.tile_max, o.tile_sum, (float *)nullptr, (int *)nullptr,
+                           tiles_m, tiles_n);
+        CAPDEC_HIP(hipGetLastError());
+        return 0;
+    }
     CAPDEC_TRY(with_topk_k(k, "gemm_topk", [&](auto KS) {
         hipLaunchKernelGGL((gemm_h2w_topk_kernel<G, KS>), grid, block, 0, st, (const _Float16 *)Apacked,
                            (const _Float16 *)Bpacked, M, N, K, scale, o.tile_max, o.tile_sum, o.cand_val, o.cand_idx,
@@ -347,6 +391,19 @@ int launch_gemm_h2w_topk_dev(hipStream_t st, const void *Apacked, const void *Bp
     hipLaunchKernelGGL((gemm_h2w_topk_dev_kernel<G, 5>), dim3(512), dim3(G::THREADS), 0, st, (const _Float16 *)Apacked,
                        (const _Float16 *)Bpacked, m_dev, N, K, inv_temp / H2_LO_SCALE, o.tile_max, o.tile_sum, o.cand_val,
                        o.cand_idx, tiles_n);
+    CAPDEC_HIP(hipGetLastError());
+    return 0;
+}
+
+// grouped k = 5 pass: *nblk_dev blocks of blk_tab over pairs whose rows are rows slot_of[p] >> slot_shift of Apacked
+int launch_gemm_h2w_topk_grouped(hipStream_t st, const void *Apacked, const void *Bpacked, const int *nblk_dev,
+                                 const int *blk_tab, const int *slot_of, int slot_shift, int blocks_cap, int N, int K,
+                                 float inv_temp, float *cand_val, int *cand_idx) {
+    CAPDEC_CHECK(nblk_dev && blk_tab && slot_of && N > 0 && K > 0 && K % 64 == 0, "gemm_h2w_topk_grouped: bad argument");
+    using G = W256x128;
+    hipLaunchKernelGGL((gemm_h2w_topk_grouped_kernel<G>), dim3(std::max(1, std::min(blocks_cap, 512))), dim3(G::THREADS), 0, st,
+                       (const _Float16 *)Apacked, (const _Float16 *)Bpacked, nblk_dev, blk_tab, slot_of, slot_shift, N, K,
+                       inv_temp / H2_LO_SCALE, cand_val, cand_idx);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

@@ -121,6 +121,193 @@ int launch_topk_merge_rows(hipStream_t st, const float *cand_val, const int *can
     return 0;
 }
 
+// ---- the sparse lm_head (decode.hip: lm_head_select): the first pass left max and sum exp per (row, tile) and NO candidates.
+// With T5 the fifth largest of a row's tile maxima, every element of the row's top 5 lies in a tile with max >= T5 (an
+// element of any other tile is strictly below five elements, the maxima of five tiles): without ties at T5 five tiles of
+// all.  One wavefront per row, the row's tile maxima in registers (lane l holds tiles l + 64 j): logsumexp as the merge
+// kernels take it; T5 by at most five rounds of "largest value below the last one, and how many tiles hold it"; then the
+// tiles with max >= T5 in ascending order -> row_tiles[row][0 .. row_cnt[row]).  A row with more than LM_SPARSE_CAP such
+// tiles (exact ties at T5) or a tile maximum that is not finite joins flag_rows, as a row of the three-candidate merge does
+// (row_cnt = 0): the full second pass computes it.
+constexpr int LM_SEL_MAXJ = 16;     // tiles per lane: <= 1024 column tiles
+__global__ __launch_bounds__(256) void lm_tile_select_kernel(const float *__restrict__ tile_max, const float *__restrict__ tile_sum,
+                                                             int rows, int ntiles, float *__restrict__ lse,
+                                                             int *__restrict__ row_cnt, int *__restrict__ row_tiles,
+                                                             int *__restrict__ flag_rows, int *__restrict__ flag_count,
+                                                             int *__restrict__ flag_total) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const size_t base = (size_t)row * ntiles;
+    const float l = tile_logsumexp(tile_max + base, tile_sum + base, ntiles, lane);
+    if (lane == 0) lse[row] = l;
+    const int nj = (ntiles + 63) >> 6;
+    float mv[LM_SEL_MAXJ];
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < LM_SEL_MAXJ; ++j) {
+        mv[j] = -INFINITY;
+        if (j < nj) {
+            const int t = lane + 64 * j;
+            if (t < ntiles) {
+                mv[j] = tile_max[base + t];
+                bad |= !(__builtin_fabsf(mv[j]) < INFINITY);
+            }
+        }
+    }
+    float t5 = INFINITY;
+    int have = 0;
+    for (int r = 0; r < 5 && have < 5; ++r) {
+        float lm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < LM_SEL_MAXJ; ++j)
+            if (j < nj) lm = fmaxf(lm, mv[j] < t5 ? mv[j] : -INFINITY);
+        t5 = wave_max(lm);
+#pragma unroll
+        for (int j = 0; j < LM_SEL_MAXJ; ++j)
+            if (j < nj) have += __popcll(__ballot(mv[j] == t5));
+    }
+    if (__any(bad) || have > LM_SPARSE_CAP) {      // (have = tiles with max >= T5 when no maximum is -inf or NaN)
+        if (lane == 0) {
+            row_cnt[row] = 0;
+            flag_rows[atomicAdd(flag_count, 1)] = row;
+            atomicAdd(flag_total, 1);
+        }
+        return;
+    }
+    int pos = 0;
+#pragma unroll
+    for (int j = 0; j < LM_SEL_MAXJ; ++j) {
+        if (j < nj) {
+            const bool sel = mv[j] >= t5;
+            const unsigned long long m = __ballot(sel);
+            if (sel) row_tiles[(size_t)row * LM_SPARSE_CAP + pos + __popcll(m & ((1ull << lane) - 1ull))] = lane + 64 * j;
+            pos += __popcll(m);
+        }
+    }
+    if (lane == 0) row_cnt[row] = have;
+}
+
+// Pairs per tile, and later every pair's place in its tile's bucket: one THREAD per row, a block's 1024 rows first meet in
+// an LDS histogram, so that a tile takes one global integer atomic per block and not one per pair (the first vocabulary
+// tiles collect a large share of all pairs).  PLACE = false: tile_cnt[t] += the block's pairs of tile t.  PLACE = true
+// (after the scan): the block reserves its share of every bucket and writes slot_of[tile_off[t] + place] = row *
+// LM_SPARSE_CAP + s for its pairs.  The order inside a bucket differs from run to run; nothing reads it.
+template <bool PLACE>
+__global__ __launch_bounds__(1024) void lm_pair_bucket_kernel(const int *__restrict__ row_cnt, const int *__restrict__ row_tiles,
+                                                              int rows, int ntiles, int *__restrict__ tile_acc,
+                                                              const int *__restrict__ tile_off, int *__restrict__ slot_of) {
+    __shared__ int hist[1024];
+    const int t = threadIdx.x, row = blockIdx.x * 1024 + t;
+    hist[t] = 0;
+    __syncthreads();
+    const int n = row < rows ? row_cnt[row] : 0;
+    int tile[LM_SPARSE_CAP], place[LM_SPARSE_CAP];
+#pragma unroll
+    for (int s = 0; s < LM_SPARSE_CAP; ++s) {
+        tile[s] = 0;
+        place[s] = 0;
+        if (s < n) {
+            tile[s] = row_tiles[(size_t)row * LM_SPARSE_CAP + s];
+            place[s] = atomicAdd(&hist[tile[s]], 1);
+        }
+    }
+    __syncthreads();
+    if (t < ntiles && hist[t] > 0) {
+        const int b = atomicAdd(tile_acc + t, hist[t]);
+        if (PLACE) hist[t] = tile_off[t] + b;
+    }
+    if (!PLACE) return;
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < LM_SPARSE_CAP; ++s)
+        if (s < n) slot_of[hist[tile[s]] + place[s]] = row * LM_SPARSE_CAP + s;
+}
+
+// One block: the pair counts per tile -> tile_off (where a tile's bucket starts in the pair list), the grouped launch's
+// block table (one entry per 256 pairs of a bucket: tile, first pair, pairs) and its length, cleared cursors for the
+// placement, and the rows each slice of the full second pass takes.
+__global__ __launch_bounds__(1024) void lm_bucket_scan_kernel(const int *__restrict__ tile_cnt, int ntiles, int *__restrict__ tile_cur,
+                                                              int *__restrict__ tile_off, int *__restrict__ nblk,
+                                                              int *__restrict__ blk_tab, const int *__restrict__ flag_count,
+                                                              int *__restrict__ slice_cnt, int slice_rows, int nslices) {
+    __shared__ int s_rows[1024], s_blk[1024];
+    const int t = threadIdx.x;
+    const int c = t < ntiles ? tile_cnt[t] : 0;
+    const int blks = (c + 255) >> 8;
+    s_rows[t] = c;
+    s_blk[t] = blks;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                       // inclusive scan of both
+        const int a = t >= o ? s_rows[t - o] : 0, b = t >= o ? s_blk[t - o] : 0;
+        __syncthreads();
+        s_rows[t] += a;
+        s_blk[t] += b;
+        __syncthreads();
+    }
+    if (t < ntiles) {
+        const int off = s_rows[t] - c, b0 = s_blk[t] - blks;
+        tile_off[t] = off;
+        tile_cur[t] = 0;
+        for (int b = 0; b < blks; ++b) {
+            blk_tab[3 * (b0 + b)] = t;
+            blk_tab[3 * (b0 + b) + 1] = off + 256 * b;
+            blk_tab[3 * (b0 + b) + 2] = min(256, c - 256 * b);
+        }
+    }
+    if (t == 1023) *nblk = s_blk[1023];
+    if (t < nslices) slice_cnt[t] = max(0, min(slice_rows, *flag_count - t * slice_rows));
+}
+
+// The row's top 5 of the (<= LM_SPARSE_CAP x 5) candidates its pairs brought back (list slot row * LM_SPARSE_CAP + s), under
+// the tie rule; whatever order the pairs were computed in.  Rows of the full second pass (row_cnt = 0) are not touched.
+__global__ __launch_bounds__(256) void lm_sparse_merge_kernel(const float *__restrict__ cand_val, const int *__restrict__ cand_idx,
+                                                              const int *__restrict__ row_cnt, int rows,
+                                                              float *__restrict__ top_val, int *__restrict__ top_idx) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int n = row_cnt[row];
+    if (n == 0) return;
+    LaneTopk<1> best;
+    best.clear();
+    if (lane < n * 5) best.push(cand_val[(size_t)row * LM_SPARSE_CAP * 5 + lane], cand_idx[(size_t)row * LM_SPARSE_CAP * 5 + lane]);
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        float gv;
+        int gi;
+        best.pop_best(gv, gi);
+        if (lane == 0) { top_val[(size_t)row * 5 + r] = gv; top_idx[(size_t)row * 5 + r] = gi; }
+    }
+}
+
+// s.tile_cnt zeroed by the caller; leaves lse, the pairs bucketed by tile in s.slot_of, the block table and the slice counts
+int launch_lm_tile_select(hipStream_t st, const float *tile_max, const float *tile_sum, int rows, int ntiles, float *lse,
+                          const SparseLm &s, int *flag_rows, int *flag_count, int *flag_total) {
+    if (rows <= 0) return 0;
+    CAPDEC_CHECK(ntiles >= 5 && ntiles <= 64 * LM_SEL_MAXJ, "lm_tile_select: 5 .. 1024 column tiles");
+    const dim3 rb((rows + 1023) / 1024);
+    hipLaunchKernelGGL(lm_tile_select_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, tile_max, tile_sum, rows, ntiles, lse,
+                       s.row_cnt, s.row_tiles, flag_rows, flag_count, flag_total);
+    hipLaunchKernelGGL(lm_pair_bucket_kernel<false>, rb, dim3(1024), 0, st, s.row_cnt, s.row_tiles, rows, ntiles, s.tile_cnt,
+                       (const int *)nullptr, (int *)nullptr);
+    hipLaunchKernelGGL(lm_bucket_scan_kernel, dim3(1), dim3(1024), 0, st, s.tile_cnt, ntiles, s.tile_cur, s.tile_off, s.nblk,
+                       s.blk_tab, flag_count, s.slice_cnt, s.slice_rows, LM_HARD_SLICES);
+    hipLaunchKernelGGL(lm_pair_bucket_kernel<true>, rb, dim3(1024), 0, st, s.row_cnt, s.row_tiles, rows, ntiles, s.tile_cur,
+                       s.tile_off, s.slot_of);
+    CAPDEC_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_lm_sparse_merge(hipStream_t st, const float *cand_val, const int *cand_idx, const int *row_cnt, int rows,
+                           float *top_val, int *top_idx) {
+    if (rows <= 0) return 0;
+    hipLaunchKernelGGL(lm_sparse_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, cand_val, cand_idx, row_cnt, rows, top_val,
+                       top_idx);
+    CAPDEC_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_topk_merge(hipStream_t st, const float *tile_max, const float *tile_sum, const float *cand_val,
                       const int *cand_idx, int rows, int ntiles, int k, float *lse, float *top_val, int *top_idx) {
     if (rows <= 0) return 0;

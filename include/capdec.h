@@ -594,7 +594,9 @@ int capdec_decode_counters(capdec_ctx *ctx, double *kv_slots_per_position, long 
  * tile, the merge detects every row for which that can have dropped a candidate that matters, and those rows alone are
  * recomputed with 5 per tile (results are identical to keeping 5 everywhere; CAPDEC_LMHEAD_K3=0 does exactly that).  Compare
  * with row_steps of capdec_decode_stats: a checkpoint whose vocabulary clusters its best candidates in one tile pays for
- * the second pass, and this is the number that shows it. */
+ * the second pass, and this is the number that shows it.  (From 12288 rows the fused kernel keeps no candidates at all and
+ * the tiles that can hold a row's 5 best are recomputed instead; the rows counted here are then those whose tile maxima tie
+ * beyond 8 tiles or are not finite -- they take the same second pass.  CAPDEC_LMHEAD_SPARSE=0: 3 per tile at every size.) */
 int capdec_decode_second_pass_rows(capdec_ctx *ctx, long long *rows);
 #ifdef CAPDEC_MEASURE
 /* MEASUREMENT BUILDS ONLY (libcapdec_hip_measure.so, compiled with -DCAPDEC_MEASURE; the shipped library does not export
