@@ -4,9 +4,12 @@
 //   weights.hip       capdec_load_* (uploads; Conv1D transposes; BatchNorm folding)
 //   gemm_dispatch.hip the GEMM planner: operand planes cache, which kernel / split for a projection and for the fused
 //                     lm_head, capdec_gemm_f32
-//   decode.hip        the pre-LN block stack, fused lm_head + selection, the KV-cached greedy / beam / sampling decode loop
-//                     (the sampling kernel itself: sample.hip; the logits processors' kernels: process.hip)
-//   guided.hip        capdec_decode_guided: classifier-free guidance on the greedy / beam loop (its combine and mirror kernels)
+//   decode.hip        the pre-LN block stack, fused lm_head + selection, the one KV-cached step loop (decode_steps; its poll
+//                     schedule: decode_sched.h) and what every decode entry point starts with, the greedy / beam / sampling
+//                     drivers on them (the sampling kernel itself: sample.hip; the logits processors' kernels: process.hip)
+//   guided.hip        capdec_decode_guided: classifier-free guidance, a driver on decode.hip's loop and greedy / beam state
+//                     with partner rows (its combine, mirror and partner-map kernels)
+//   contrastive.hip   capdec_decode_contrastive: contrastive search, a driver on decode.hip's loop (its selection kernels)
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   nearest.hip       capdec_nearest_tokens: nearest table rows by cosine similarity (the normalised-wte cache, row blocks)
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
@@ -20,6 +23,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <utility>
@@ -347,7 +351,7 @@ void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd);
 int gpt2_body(capdec_ctx *c, const StepShape &s, const KvCache &kv);
 int lm_head_select(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp);
 int ensure_kv(capdec_ctx *c, KvCache &kv, int rows, int ctx, int heads = 0, int hd = 0, int layers = 0);
-// The constants of one decode call; the extern "C" entry points fill it, decode_common offsets the pointers per chunk.
+// The constants of one decode call; the extern "C" entry points fill it, chunk_call offsets the pointers per chunk.
 struct DecodeCall {
     int P = 0, beam = 1;
     bool greedy = true;         // the greedy family (arg-max, teacher-forced, sampling): beam == 1
@@ -373,15 +377,50 @@ struct DecodeCall {
     int cap_off = 0;            // index of the chunk's first caption within the call: the Philox counter's caption offset, and
                                 // the offset of the chunk's slice of the per-call K/V-slot statistic (BeamState::kv_stat)
 };
-// ... and what the contrastive search (contrastive.hip) shares with the drivers above: whether the call runs the logits
-// processors, the lm_head route through materialised logits, the alive-count poll and the captions-per-chunk computation
+// ... and what the drivers of decode.hip, guided.hip and contrastive.hip are built from (decode.hip).  An entry point:
+// decode_call_checks (in the groups its own checks sit between), decode_call_begin (the per-call reset, the captions per
+// chunk), then per chunk its driver on chunk_call's constants.
+enum { CK_LOADED = 1, CK_SIZES = 2, CK_CONTEXT = 4, CK_HEAD_DIM = 8, CK_BIAS = 16 };
+int decode_call_checks(capdec_ctx *c, const char *who, int which, int n, int P, int T, long long ctx);
+int decode_call_begin(capdec_ctx *c, int n, int steps0, int kvstat_caps, int rows_per_caption, int ctx, size_t extra_per_cap,
+                      int lm_rows_per_cap, int *chunk);
+DecodeCall chunk_call(const DecodeCall &call, int c0);
+int chunk_captions(capdec_ctx *c, int n, int beam, int ctx, size_t extra_per_cap = 0);
+// A driver: the prefill and its selection, then decode_steps -- the one step loop: alive-count polls, compaction, statistics
+// -- with the body of a step plugged in, then the finalisation.
+struct StepLoop {
+    int nc, first, T;           // captions of the chunk; steps first .. T - 1 (first: 1, or 0 where the prefill selects nothing)
+    int rows_per_caption;       // activation rows per caption: beam, 2 * beam (guided), top_k (contrastive)
+    const uint8_t *done;        // [nc] the captions' done flags
+    int map_slots;              // caption slots of the compaction map: nc, or 2 nc where partners are listed behind
+};
+using AfterCompact = std::function<int(int *cmap, int na)>;
+using StepFn = std::function<int(int i, int na, const int *cmap)>;
+int decode_steps(capdec_ctx *c, const StepLoop &l, const AfterCompact &after_compact, const StepFn &step);
+int poll_alive(capdec_ctx *c, int *alive);
+// ... the KV cache and the greedy or the beam state of a chunk (halves = 2: with the guided decode's partner rows), and the
+// step kernel that advances it
+struct DecodeState {
+    KvCache kv;
+    BeamState bs;
+    GreedyState gs;
+    const int *hist = nullptr;      // the rows' own histories, for the logits processors: ids (greedy) or bs.tokens
+    uint8_t *anc = nullptr;         // bs.anc (nullptr: greedy)
+};
+int decode_state(capdec_ctx *c, int nc, const DecodeCall &a, int halves, DecodeState *s);
+int decode_advance(capdec_ctx *c, const DecodeCall &a, const DecodeState &s, int R, int step, int k, const int *cmap);
+int gpt2_step(capdec_ctx *c, const KvCache &kv, int rows, int beam, int L, const uint8_t *anc, const int *cmap);
+// ... whether the call runs the logits processors; the lm_head route through materialised logits (hn, gamma: the guided
+// decode's partner rows and scale; its combine kernel: guided.hip); ln_f over R rows of h (row stride ldh) + the plain
+// lm_head GEMM -> logits [R, ld]
 bool processors_on(const capdec_ctx *c, bool sampling);
 int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const DecodeCall &a,
-                 const GreedyState &gs, bool proc, int step, int beam, const int *hist);
-int poll_alive(capdec_ctx *c, int *alive);
-int chunk_captions(capdec_ctx *c, int n, int beam, int ctx, size_t extra_per_cap = 0);
-// ... and the guided decode (guided.hip): ln_f over R rows of h (row stride ldh) + the plain lm_head GEMM -> logits [R, ld]
+                 const GreedyState &gs, bool proc, int step, int beam, const int *hist, const float *hn = nullptr,
+                 float gamma = 0.f);
 int lm_head_logits(capdec_ctx *c, const float *h0, int ldh, int R, float *logits, int ld);
+
+// ---- guided.hip
+int launch_guided_combine(hipStream_t st, float *cond, const float *neg, int ld, int rows, int V, float gamma);
 
 // ---- nearest.hip
 void drop_wte_norm(capdec_ctx *c);      // the normalised copy of wte and its planes (wte was reloaded or updated)

@@ -8,7 +8,9 @@
 //   3. contrast_select_kernel: ln_f + normalise of the K rows, max cosine against the `pos` history rows, score, arg-max,
 //      then everything the next step needs -- token, length, done, alive count, anc[all K rows][pos] = winner (the winner's
 //      K/V at `pos` becomes the path's), the history row `pos`, the winner's residual row.
-// The [K, pos] similarities live in registers and LDS only.  Chunking, compaction and the adaptive poll are decode.hip's.
+// The [K, pos] similarities live in registers and LDS only.  The step loop is decode.hip's decode_steps, from step 0 with K
+// rows per caption; after a compaction the lm_head's rows (sel) are gathered again through the new map.  Call checks,
+// per-call reset and chunking are decode.hip's too.
 #include "context.h"
 
 namespace capdec {
@@ -174,7 +176,6 @@ static int contrastive_chunk(capdec_ctx *c, const float *prefix, int nc, const D
     CAPDEC_TRY(c->cs_hist.ensure((size_t)nc * ctx * d * 4));
     CAPDEC_TRY(c->cs_last.ensure((size_t)nc * d * 4));
     CAPDEC_TRY(c->cs_sel.ensure((size_t)nc * d * 4));
-    CAPDEC_TRY(c->cmap.ensure(((size_t)nc + 1) * 4));
     ContrastState s;
     s.ids = a.ids; s.lens = a.lens; s.trace = trace;
     s.done = c->done.as<uint8_t>();
@@ -200,34 +201,11 @@ static int contrastive_chunk(capdec_ctx *c, const float *prefix, int nc, const D
     CAPDEC_TRY(gpt2_body(c, sp, kv));
     { ProfScope ps(c, F_CONTRAST); CAPDEC_TRY(launch_contrast_prefill(c->stream, s, c->h.as<float>(), g.lnfw, g.lnfb, g.eps, nc, P)); }
 
-    // ---- steps 0..T-1 (poll cadence and compaction: decode_chunk)
-    int na = nc, next_poll = 1, backoff = 1, last_alive = nc + 1;
-    const int *cmap = nullptr;
-    for (int t = 0; t < T; ++t) {
-        if (t >= next_poll) {
-            int alive = 0;
-            CAPDEC_TRY(poll_alive(c, &alive));
-            if (alive == 0) break;
-            const int rows_now = alive * K;
-            const int base = rows_now >= 8192 ? 1 : rows_now >= 2048 ? 2 : rows_now >= 512 ? 4 : 8;
-            backoff = alive < last_alive ? 1 : std::min(8, backoff * 2);
-            last_alive = alive;
-            next_poll = t + std::min(8, std::max(base, backoff));
-            if (c->compact && alive <= na - std::max(1, na / 32)) {
-                ProfScope ps(c, F_SELECT);
-                CAPDEC_TRY(launch_compact_alive(c->stream, s.done, nc, c->cmap.as<int>(), c->cmap.as<int>() + nc));
-                na = alive;
-                cmap = c->cmap.as<int>();
-                c->stat_compactions += 1;
-                CAPDEC_TRY(launch_gather_rows(c->stream, s.last, cmap, s.sel, na, d));      // the lm_head's rows follow
-            }
-        }
+    // ---- steps 0..T-1: K rows per caption; after a compaction the lm_head's rows follow the new map
+    const StepLoop loop{nc, 0, T, K, s.done, nc};
+    auto gather_sel = [&](int *cmap, int na) -> int { return launch_gather_rows(c->stream, s.last, cmap, s.sel, na, d); };
+    return decode_steps(c, loop, gather_sel, [&](int t, int na, const int *cmap) -> int {
         const int pos = P + t, arows = na * K;
-        c->stat_steps = std::max(c->stat_steps, t + 1);
-        c->stat_row_steps += arows;
-        if ((int)c->stat_step_rows.size() < t + 1) c->stat_step_rows.resize(t + 1, 0);
-        c->stat_step_rows[t] += arows;
-        CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
         gs.cmap = cmap;
         if (proc) CAPDEC_TRY(lm_head_rows(c, s.sel, d, na, K, 1.0f, a, gs, true, t, 1, a.ids));
         else CAPDEC_TRY(lm_head_select(c, s.sel, d, na, K, 1.0f));
@@ -236,20 +214,11 @@ static int contrastive_chunk(capdec_ctx *c, const float *prefix, int nc, const D
             CAPDEC_TRY(launch_embed_tokens(c->stream, c->topi.as<int>(), g.wte, g.wpe + (size_t)pos * d, c->h.as<float>(),
                                            arows, d));
         }
-        StepShape sd{};
-        sd.prefill = false;
-        sd.rows = arows;
-        sd.beam = K;
-        sd.L = pos + 1;
-        sd.anc = s.anc;
-        sd.anc_stride = ctx;
-        sd.cmap = cmap;
-        CAPDEC_TRY(gpt2_body(c, sd, kv));
+        CAPDEC_TRY(gpt2_step(c, kv, arows, K, pos + 1, s.anc, cmap));
         ProfScope ps(c, F_CONTRAST);
-        CAPDEC_TRY(launch_contrast_select(c->stream, s, c->h.as<float>(), g.lnfw, g.lnfb, g.eps, c->lse.as<float>(),
-                                          c->topv.as<float>(), c->topi.as<int>(), na, K, alpha, t, pos, cmap));
-    }
-    return 0;
+        return launch_contrast_select(c->stream, s, c->h.as<float>(), g.lnfw, g.lnfb, g.eps, c->lse.as<float>(),
+                                      c->topv.as<float>(), c->topi.as<int>(), na, K, alpha, t, pos, cmap);
+    });
 }
 
 }  // namespace capdec
@@ -259,45 +228,27 @@ using namespace capdec;
 extern "C" int capdec_decode_contrastive(capdec_ctx *c, const float *prefix, int n, int P, int top_k, float penalty_alpha,
                                          int stop_id, int alt_stop_id, int entry_length, int32_t *ids, int32_t *lens,
                                          float *trace) {
+    const char *who = "decode_contrastive";
     CAPDEC_CHECK(c && (n == 0 || (prefix && ids && lens)), "decode_contrastive: null argument");
-    CAPDEC_CHECK(c->gpt.loaded, "decode_contrastive: GPT-2 weights not loaded");
+    CAPDEC_TRY(decode_call_checks(c, who, CK_LOADED, n, 0, 0, 0));
     CAPDEC_CHECK(top_k >= 1 && top_k <= 8, "decode_contrastive: top_k must be in 1..8");
     CAPDEC_CHECK(penalty_alpha >= 0.f && penalty_alpha <= 1.f, "decode_contrastive: penalty_alpha must be in [0, 1]");
     const int T = entry_length;
-    CAPDEC_CHECK(n >= 0 && P >= 1 && T >= 1, "decode_contrastive: bad sizes");
-    CAPDEC_CHECK((long long)P + T <= c->gpt.n_pos, "decode_contrastive: prefix + entry_length exceeds n_positions");
-    CAPDEC_CHECK((long long)P + T <= 1024, "decode_contrastive: context > 1024 not supported");
-    CAPDEC_CHECK(c->gpt.d / c->gpt.n_head == 64, "decode_contrastive: head_dim must be 64");
+    CAPDEC_TRY(decode_call_checks(c, who, CK_SIZES | CK_CONTEXT | CK_HEAD_DIM, n, P, T, (long long)P + T));
     CAPDEC_CHECK(c->gpt.vocab >= top_k, "decode_contrastive: vocabulary smaller than top_k");
-    CAPDEC_CHECK(c->proc_bias_n == 0 || c->proc_bias_n == c->gpt.vocab,
-                 "decode_contrastive: the logit bias was set for another vocabulary");
-    CAPDEC_HIP(hipSetDevice(c->device));
-    c->stat_steps = 0;
-    c->stat_compactions = 0;
-    c->stat_chunks = 0;
-    c->stat_row_steps = 0;
-    c->stat_step_rows.clear();
-    c->stat_kv_slots = c->stat_kv_pos = 0.0;
-    c->kvstat_n = 0;
-    if (n == 0) return 0;
+    CAPDEC_TRY(decode_call_checks(c, who, CK_BIAS, n, P, T, 0));
+    // every emitted token is chosen AFTER its own candidate pass: the context is one position longer than the plain decode's,
+    // and step 0 is a loop step.  The history counts against the KV budget; the lm_head sees one row per caption.
     const int ctx = P + T, d = c->gpt.d;
-    const int chunk = chunk_captions(c, n, top_k, ctx, (size_t)ctx * d * 4);       // the history counts against the budget
-    c->stat_chunks = (n + chunk - 1) / chunk;
-    CAPDEC_TRY(c->lmflag.ensure(((size_t)chunk + 2) * 4));      // (lm_head_select's second-pass bookkeeping, as decode_common)
-    CAPDEC_HIP(hipMemsetAsync(c->lmflag.p, 0, 2 * sizeof(int), c->stream));
-    c->lmflag_live = false;
-    c->k3_off = false;
-    c->k3_rows = 0;
-    DecodeCall a;
-    a.P = P; a.stop_id = stop_id; a.alt_stop_id = alt_stop_id; a.T = T;
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int nc = std::min(chunk, n - c0);
-        a.ids = ids + (size_t)c0 * T;
-        a.lens = lens + c0;
-        a.cap_off = c0;
-        CAPDEC_TRY(contrastive_chunk(c, prefix + (size_t)c0 * P * d, nc, a, top_k, penalty_alpha,
-                                     trace ? trace + (size_t)c0 * T * 2 : nullptr));
-    }
+    int chunk = 0;
+    CAPDEC_TRY(decode_call_begin(c, n, 0, 0, top_k, ctx, (size_t)ctx * d * 4, 1, &chunk));
+    if (n == 0) return 0;
+    DecodeCall call;
+    call.P = P; call.stop_id = stop_id; call.alt_stop_id = alt_stop_id; call.T = T;
+    call.ids = ids; call.lens = lens;
+    for (int c0 = 0; c0 < n; c0 += chunk)
+        CAPDEC_TRY(contrastive_chunk(c, prefix + (size_t)c0 * P * d, std::min(chunk, n - c0), chunk_call(call, c0), top_k,
+                                     penalty_alpha, trace ? trace + (size_t)c0 * T * 2 : nullptr));
     CAPDEC_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }

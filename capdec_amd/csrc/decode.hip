@@ -1,10 +1,15 @@
 // The KV-cached batched decode: the pre-LN block stack (GPT-2, and the CLIP towers that run on the same stack), the fused
-// lm_head + candidate selection, the greedy / beam / sampling drivers with finished-caption compaction -- host-side orchestration
-// only: every operation is a launcher of common.h enqueued on the context's stream.  (The mapping networks: mapper.hip.)
-// A call's constants travel in one DecodeCall; every step, the prefill's included, ends in select_and_advance, which picks
-// the lm_head route (lm_head_select: fused, logits never in HBM; lm_head_rows: materialised, for the logits processors and
-// the sampling decode) and then advances the greedy or the beam state.
+// lm_head + candidate selection, the one step loop of every decode (decode_steps: alive-count polls on decode_sched.h's
+// schedule, finished-caption compaction, the statistics) and the greedy / beam / sampling drivers on it -- host-side
+// orchestration only: every operation is a launcher of common.h enqueued on the context's stream.  (The mapping networks:
+// mapper.hip.)  A call's constants travel in one DecodeCall.  A driver is the prefill, the body of a step handed to
+// decode_steps, and the finalisation; the guided decode (guided.hip) and the contrastive search (contrastive.hip) are two
+// more such drivers and start their calls with the same decode_call_checks / decode_call_begin / chunk_call.  Here every
+// step, the prefill's included, ends in select_and_advance, which picks the lm_head route (lm_head_select: fused, logits
+// never in HBM; lm_head_rows: materialised, for the logits processors, the sampling decode and the guided decode) and then
+// advances the greedy or the beam state (decode_advance).
 #include "context.h"
+#include "decode_sched.h"
 
 namespace capdec {
 
@@ -254,14 +259,17 @@ bool processors_on(const capdec_ctx *c, bool sampling) {
 //                 leaves, the step kernels follow unchanged
 //   sampling      top_k where it removes something, the nucleus-sampling kernel (it writes what launch_greedy_step
 //                 writes, into gs), the logp shift under top_k.
+// hn (the guided decode): the rows' partners, same stride -- a block's partner logits go behind the block's own in the
+// scratch, and the combine (guided.hip) writes gamma * log_softmax(own) + (1 - gamma) * log_softmax(partner) over the own
+// rows in front of the processors.
 // hist: the rows' histories [captions, beam, T] -- `ids` or BeamState::tokens; `step` entries of each are read.
 int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float inv_temp, const DecodeCall &a,
-                        const GreedyState &gs, bool proc, int step, int beam, const int *hist) {
-    const int V = c->gpt.vocab, ld = (V + 63) / 64 * 64, blk = std::min(R, std::max(1, c->tune.sample_rows));
+                 const GreedyState &gs, bool proc, int step, int beam, const int *hist, const float *hn, float gamma) {
+    const int V = c->gpt.vocab, ld = pad64(V), blk = std::min(R, std::max(1, c->tune.sample_rows));
     const LogitsProc &p = c->proc;
     const float *bias = c->proc_bias_n > 0 ? c->pbias.as<float>() : nullptr;
     const bool cut = proc && a.sample && p.top_k > 0 && p.top_k < V;
-    CAPDEC_TRY(c->slogits.ensure((size_t)blk * ld * 4));
+    CAPDEC_TRY(c->slogits.ensure((size_t)(hn ? 2 : 1) * blk * ld * 4));
     if (!a.sample) {
         CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
         CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
@@ -269,11 +277,16 @@ int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float in
     } else if (cut && a.logp) {
         CAPDEC_TRY(c->pcorr.ensure((size_t)blk * 4));
     }
-    float *lg = c->slogits.as<float>();
+    float *lg = c->slogits.as<float>(), *lgn = lg + (size_t)blk * ld;
     float *corr = cut && a.logp ? c->pcorr.as<float>() : nullptr;
     for (int r0 = 0; r0 < R; r0 += blk) {
         const int nr = std::min(blk, R - r0);
         CAPDEC_TRY(lm_head_logits(c, h0 + (size_t)r0 * ldh, ldh, nr, lg, ld));
+        if (hn) {
+            CAPDEC_TRY(lm_head_logits(c, hn + (size_t)r0 * ldh, ldh, nr, lgn, ld));
+            ProfScope ps(c, F_GUIDED);
+            CAPDEC_TRY(launch_guided_combine(c->stream, lg, lgn, ld, nr, V, gamma));
+        }
         ProfScope ps(c, F_SELECT);
         if (proc)
             CAPDEC_TRY(launch_logits_process(c->stream, lg, ld, nr, r0, V, gs.cmap, beam, hist, a.T, step, p, bias, a.stop_id,
@@ -342,32 +355,96 @@ int chunk_captions(capdec_ctx *c, int n, int beam, int ctx, size_t extra_per_cap
     return (int)std::min<size_t>(m, (size_t)n);
 }
 
-// ---------------------------------------------------------------------------- decode drivers
-static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const DecodeCall &a) {
-    const Gpt2 &g = c->gpt;
-    const int d = g.d, P = a.P, T = a.T, beam = a.beam;
-    const bool greedy = a.greedy;
-    const int ctx = P + T - 1;
-    const int rows = nc * beam;
-    const int k = (greedy && a.stats) ? 2 : beam;   // candidates kept per row (teacher-forced statistics: top-2)
-    const float inv_temp = 1.0f / (a.temperature > 0.f ? a.temperature : 1.0f);
-    const bool proc = !a.forced && processors_on(c, a.sample);      // (teacher forcing ignores the processors)
-    KvCache kv;
-    CAPDEC_TRY(ensure_kv(c, kv, rows, ctx));
-    kv.fixed_variant = c->batch_invariant;
-    kv.prefix_len = P;
-    CAPDEC_TRY(ensure_body_ws(c, std::max(nc * P, rows), d));
-    CAPDEC_TRY(c->next_tok.ensure((size_t)rows * 4));
+// ---------------------------------------------------------------------------- what every decode entry point shares
+// The checks common to the entry points, `who` in front of every message.  An entry point asks for them in the groups its own
+// checks sit between (`which`: CK_*); ctx: the last position the call reaches + 1.
+int decode_call_checks(capdec_ctx *c, const char *who, int which, int n, int P, int T, long long ctx) {
+    const std::string w = std::string(who) + ": ";
+    if (which & CK_LOADED) CAPDEC_CHECK(c && c->gpt.loaded, w + "GPT-2 weights not loaded");
+    if (which & CK_SIZES) CAPDEC_CHECK(n >= 0 && P >= 1 && T >= 1, w + "bad sizes");
+    if (which & CK_CONTEXT) {
+        CAPDEC_CHECK(ctx <= c->gpt.n_pos, w + "prefix + entry_length exceeds n_positions");
+        // (a context that counts the last token too -- contrastive search -- bounds entry_length with it)
+        CAPDEC_CHECK(ctx <= 1024 && T <= 1024,
+                     w + (ctx == (long long)P + T ? "context > 1024 not supported" : "context or entry_length > 1024 not supported"));
+    }
+    if (which & CK_HEAD_DIM) CAPDEC_CHECK(c->gpt.d / c->gpt.n_head == 64, w + "head_dim must be 64");
+    if (which & CK_BIAS)
+        CAPDEC_CHECK(c->proc_bias_n == 0 || c->proc_bias_n == c->gpt.vocab, w + "the logit bias was set for another vocabulary");
+    return 0;
+}
+
+// The per-call reset and plan: the statistics (steps0: what the prefill's selection counts as -- 1, or 0 where step 0 is a
+// loop step), the K/V-slot counters of kvstat_caps captions (0: greedy), the captions per chunk under the KV budget
+// (chunk_captions) -> *chunk, the lm_head's second-pass bookkeeping ([count, total, rows...], lm_head_select) sized once for
+// the largest step of lm_rows_per_cap rows per caption, total zeroed (0: the fused lm_head never runs, poll_alive has
+// nothing to watch).  n == 0: the reset alone, *chunk = 0.
+int decode_call_begin(capdec_ctx *c, int n, int steps0, int kvstat_caps, int rows_per_caption, int ctx, size_t extra_per_cap,
+                      int lm_rows_per_cap, int *chunk) {
+    CAPDEC_HIP(hipSetDevice(c->device));
+    c->stat_steps = n > 0 ? steps0 : 0;
+    c->stat_compactions = 0;
+    c->stat_chunks = 0;
+    c->stat_row_steps = 0;
+    c->stat_step_rows.clear();
+    c->stat_kv_slots = c->stat_kv_pos = 0.0;
+    c->kvstat_n = 0;
+    *chunk = 0;
+    if (n == 0) return 0;
+    if (kvstat_caps > 0) {
+        CAPDEC_TRY(c->kvstat.ensure((size_t)kvstat_caps * 2 * sizeof(unsigned)));
+        CAPDEC_HIP(hipMemsetAsync(c->kvstat.p, 0, (size_t)kvstat_caps * 2 * sizeof(unsigned), c->stream));
+        c->kvstat_n = kvstat_caps;
+    }
+    *chunk = chunk_captions(c, n, rows_per_caption, ctx, extra_per_cap);
+    c->stat_chunks = (n + *chunk - 1) / *chunk;
+    if (lm_rows_per_cap > 0) {
+        CAPDEC_TRY(c->lmflag.ensure(((size_t)*chunk * lm_rows_per_cap + 2) * 4));
+        CAPDEC_HIP(hipMemsetAsync(c->lmflag.p, 0, 2 * sizeof(int), c->stream));
+    }
+    c->lmflag_live = false;
+    c->k3_off = false;
+    c->k3_rows = 0;
+    return 0;
+}
+
+// a call's constants for the chunk that starts at caption c0
+DecodeCall chunk_call(const DecodeCall &call, int c0) {
+    const int T = call.T, beam = call.beam;
+    DecodeCall a = call;
+    a.ids += (size_t)c0 * beam * T;
+    a.lens += (size_t)c0 * beam;
+    if (a.scores) a.scores += (size_t)c0 * beam;
+    if (a.order) a.order += (size_t)c0 * beam;
+    if (a.forced) a.forced += (size_t)c0 * T;
+    if (a.stats) a.stats += (size_t)c0 * T * 3;
+    if (a.u) a.u += (size_t)c0 * T;
+    if (a.logp) a.logp += (size_t)c0 * T;
+    if (a.glogp) a.glogp += (size_t)c0 * beam;
+    a.cap_off = c0;
+    return a;
+}
+
+// The workspaces and the greedy or the beam state of a chunk of nc captions, zeroed.  halves = 2 (the guided decode): every
+// caption has a partner nc captions further on -- twice the K/V rows, next_tok, ancestor rows and body workspace; the state
+// proper lives with the first half alone.
+int decode_state(capdec_ctx *c, int nc, const DecodeCall &a, int halves, DecodeState *s) {
+    const int T = a.T, ctx = a.P + T - 1, rows = nc * a.beam;
+    CAPDEC_TRY(ensure_kv(c, s->kv, halves * rows, ctx));
+    s->kv.fixed_variant = c->batch_invariant;
+    s->kv.prefix_len = a.P;
+    CAPDEC_TRY(ensure_body_ws(c, halves * std::max(nc * a.P, rows), c->gpt.d));
+    CAPDEC_TRY(c->next_tok.ensure((size_t)halves * rows * 4));
     CAPDEC_TRY(c->alive.ensure(sizeof(int)));
     CAPDEC_TRY(c->done.ensure((size_t)rows));
-    BeamState bs;
-    GreedyState gs;
-    if (!greedy) {
+    BeamState &bs = s->bs;
+    GreedyState &gs = s->gs;
+    if (!a.greedy) {
         CAPDEC_TRY(c->tokens.ensure((size_t)rows * T * 4));
         CAPDEC_TRY(c->scores.ensure((size_t)rows * 4));
         CAPDEC_TRY(c->seq.ensure((size_t)rows * 4));
         CAPDEC_TRY(c->stopped.ensure((size_t)rows));
-        CAPDEC_TRY(c->anc.ensure((size_t)rows * ctx));
+        CAPDEC_TRY(c->anc.ensure((size_t)halves * rows * ctx));
         bs.tokens = c->tokens.as<int>();
         bs.scores = c->scores.as<float>();
         bs.seq = c->seq.as<float>();
@@ -376,16 +453,15 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
         bs.anc = c->anc.as<uint8_t>();
         bs.next_tok = c->next_tok.as<int>();
         bs.alive_count = c->alive.as<int>();
-        bs.diverge = c->diverge;
         if (a.groups > 0) {
             CAPDEC_TRY(c->glogp.ensure((size_t)rows * 4));
             bs.logp = c->glogp.as<float>();
         }
-        // (distinct-K/V-slot statistic: this chunk's slice of the per-call array decode_common zeroed; nothing is read back
-        //  here -- capdec_decode_counters sums it when somebody asks)
+        // (distinct-K/V-slot statistic: this chunk's slice of the per-call array decode_call_begin zeroed; nothing is read
+        //  back here -- capdec_decode_counters sums it when somebody asks)
         bs.kv_stat = c->kvstat.p ? c->kvstat.as<unsigned>() + (size_t)a.cap_off * 2 : nullptr;
         CAPDEC_HIP(hipMemsetAsync(bs.tokens, 0, (size_t)rows * T * 4, c->stream));
-        CAPDEC_HIP(hipMemsetAsync(bs.anc, 0, (size_t)rows * ctx, c->stream));
+        CAPDEC_HIP(hipMemsetAsync(bs.anc, 0, (size_t)halves * rows * ctx, c->stream));
     } else {
         gs.ids = a.ids;
         gs.lens = a.lens;
@@ -402,29 +478,101 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
     }
     CAPDEC_HIP(hipMemsetAsync(c->done.p, 0, (size_t)rows, c->stream));
     CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
-    const int *hist = greedy ? a.ids : bs.tokens;       // the rows' own histories, for the logits processors
+    s->hist = a.greedy ? a.ids : bs.tokens;
+    s->anc = a.greedy ? nullptr : bs.anc;
+    return 0;
+}
+
+// The step kernel of the decode over what the lm_head left for the R rows (c->lse / c->topv / c->topi, k per row): greedy,
+// or the beam / group-beam bookkeeping -- its first form at step 0, where a caption is one row.
+int decode_advance(capdec_ctx *c, const DecodeCall &a, const DecodeState &s, int R, int step, int k, const int *cmap) {
+    const int P = a.P, T = a.T, beam = a.beam, ctx = P + T - 1, V = c->gpt.vocab;
+    ProfScope ps(c, F_SELECT);
+    const float *lse = c->lse.as<float>(), *topv = c->topv.as<float>();
+    const int *topi = c->topi.as<int>();
+    if (a.greedy) return launch_greedy_step(c->stream, s.gs, topi, R, step, k, a.forced, topv, lse, a.stats);
+    if (a.groups > 0) {
+        if (step == 0)
+            return launch_group_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, a.groups, a.diversity, k, T, ctx, P, a.stop_id);
+        return launch_group_beam_step(c->stream, s.bs, lse, topv, topi, R / beam, beam, a.groups, a.diversity, k, T, ctx, step,
+                                      P + step - 1, V, a.stop_id, cmap);
+    }
+    if (step == 0) return launch_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, k, T, ctx, P, a.stop_id);
+    return launch_beam_step(c->stream, s.bs, lse, topv, topi, R / beam, beam, k, T, ctx, step, P + step - 1, V, a.stop_id, cmap);
+}
+
+// GPT-2's blocks over the `rows` activation rows of one decode step at context length L (c->h in place)
+int gpt2_step(capdec_ctx *c, const KvCache &kv, int rows, int beam, int L, const uint8_t *anc, const int *cmap) {
+    StepShape sd{};
+    sd.prefill = false;
+    sd.rows = rows;
+    sd.beam = beam;
+    sd.L = L;
+    sd.anc = anc;
+    sd.anc_stride = kv.ctx;
+    sd.cmap = cmap;
+    return gpt2_body(c, sd, kv);
+}
+
+// ---------------------------------------------------------------------------- the step loop
+// Steps l.first .. l.T - 1 of a chunk of l.nc captions, each l.rows_per_caption activation rows: everything between "the
+// first selection has run" and "every caption is done or T is reached".  Finished captions (l.done: stop token on every
+// beam) are dropped from the batch at the poll points (decode_sched.h says when): the compaction map lists the na captions
+// still generating, the activations of a step are the rows of those captions only, while KV cache / ancestor table / state
+// keep their original rows.  The map has l.map_slots slots, the device-side count behind them.  The drivers plug in
+//   after_compact(cmap, na)   what else has to follow a new map (may be empty)
+//   step(i, na, cmap)         the body of step i over the na captions of cmap (nullptr: all of them, in order)
+int decode_steps(capdec_ctx *c, const StepLoop &l, const AfterCompact &after_compact, const StepFn &step) {
+    CAPDEC_TRY(c->cmap.ensure(((size_t)l.map_slots + 1) * 4));
+    PollSchedule sched(l.nc);
+    int na = l.nc;
+    const int *cmap = nullptr;
+    for (int i = l.first; i < l.T; ++i) {
+        if (sched.due(i)) {
+            int alive = 0;
+            CAPDEC_TRY(poll_alive(c, &alive));
+            if (alive == 0) break;
+            sched.polled(i, alive, l.rows_per_caption);
+            if (c->compact && compaction_pays(na, alive)) {
+                ProfScope ps(c, F_SELECT);
+                int *m = c->cmap.as<int>();
+                CAPDEC_TRY(launch_compact_alive(c->stream, l.done, l.nc, m, m + l.map_slots));
+                na = alive;
+                cmap = m;
+                c->stat_compactions += 1;
+                if (after_compact) CAPDEC_TRY(after_compact(m, na));
+            }
+        }
+        const int arows = na * l.rows_per_caption, s = i - l.first;
+        c->stat_steps = std::max(c->stat_steps, i + 1);
+        c->stat_row_steps += arows;
+        if ((int)c->stat_step_rows.size() <= s) c->stat_step_rows.resize(s + 1, 0);     // (chunks of one call add up step by step)
+        c->stat_step_rows[s] += arows;
+        CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
+        CAPDEC_TRY(step(i, na, cmap));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- the plain drivers: greedy, beam, sampling
+static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const DecodeCall &a) {
+    const Gpt2 &g = c->gpt;
+    const int d = g.d, P = a.P, T = a.T, beam = a.beam;
+    const int k = (a.greedy && a.stats) ? 2 : beam;   // candidates kept per row (teacher-forced statistics: top-2)
+    const float inv_temp = 1.0f / (a.temperature > 0.f ? a.temperature : 1.0f);
+    const bool proc = !a.forced && processors_on(c, a.sample);      // (teacher forcing ignores the processors)
+    DecodeState s;
+    CAPDEC_TRY(decode_state(c, nc, a, 1, &s));
+    s.bs.diverge = c->diverge;
 
     // Select and advance: the lm_head route of this call over the R rows of h at h0 (row stride ldh), then the step
     // kernel of the decode.  hbeam: rows per caption for the history lookup; cmap: the compaction in force.
     auto select_and_advance = [&](const float *h0, int ldh, int R, int step, int hbeam, const int *cmap) -> int {
-        gs.cmap = cmap;
-        if (proc || a.sample) CAPDEC_TRY(lm_head_rows(c, h0, ldh, R, k, inv_temp, a, gs, proc, step, hbeam, hist));
+        s.gs.cmap = cmap;
+        if (proc || a.sample) CAPDEC_TRY(lm_head_rows(c, h0, ldh, R, k, inv_temp, a, s.gs, proc, step, hbeam, s.hist));
         else CAPDEC_TRY(lm_head_select(c, h0, ldh, R, k, inv_temp));
         if (a.sample) return 0;                         // (the sampling kernel has advanced the state)
-        ProfScope ps(c, F_SELECT);
-        const float *lse = c->lse.as<float>(), *topv = c->topv.as<float>();
-        const int *topi = c->topi.as<int>();
-        if (greedy) return launch_greedy_step(c->stream, gs, topi, R, step, k, a.forced, topv, lse, a.stats);
-        if (a.groups > 0) {
-            if (step == 0)
-                return launch_group_beam_init(c->stream, bs, lse, topv, topi, R, beam, a.groups, a.diversity, k, T, ctx, P,
-                                              a.stop_id);
-            return launch_group_beam_step(c->stream, bs, lse, topv, topi, R / beam, beam, a.groups, a.diversity, k, T, ctx, step,
-                                          P + step - 1, g.vocab, a.stop_id, cmap);
-        }
-        if (step == 0) return launch_beam_init(c->stream, bs, lse, topv, topi, R, beam, k, T, ctx, P, a.stop_id);
-        return launch_beam_step(c->stream, bs, lse, topv, topi, R / beam, beam, k, T, ctx, step, P + step - 1, g.vocab,
-                                a.stop_id, cmap);
+        return decode_advance(c, a, s, R, step, k, cmap);
     };
 
     // ---- step 0: prefill the prefix (positions 0..P-1), logits of the last prefix row
@@ -434,126 +582,42 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
     sp.ncap = nc;
     sp.P = P;
     sp.beam = beam;
-    CAPDEC_TRY(gpt2_body(c, sp, kv));
+    CAPDEC_TRY(gpt2_body(c, sp, s.kv));
     // (one row per caption and an empty history: nothing is read through `hist` yet)
     CAPDEC_TRY(select_and_advance(c->h.as<float>() + (size_t)(P - 1) * d, P * d, nc, 0, 1, nullptr));
-    // ---- steps 1..T-1: one token per row per step.  Finished captions (stop token on every beam) are dropped from
-    // the batch at the poll points: `cmap` lists the captions still generating, the activations of a step are the
-    // na * beam rows of those captions only, while KV cache / ancestor table / beam state keep their original rows.
-    // Poll cadence: a poll drains the stream (a 4-byte copy + a synchronisation: ~150 us of idle GPU by the time the host has
-    // woken up and refilled the queue).  While captions ARE finishing a poll pays for itself -- every step that still carries
-    // finished captions costs more: a step of >= 8192 rows takes >= 8 ms, one of ~3000 rows ~4 ms (round 6, captions that
-    // stop after ~11 tokens: with a poll every 8 steps 25 000 rows were launched for 8 steps while 40 % of them had
-    // finished; 519 k row-steps against 427 k alive) -- so the base interval is 1 step at >= 8192 rows, 2 at >= 2048, 4 at
-    // >= 512, 8 below.  While NOTHING finishes (the synthetic headline weights never emit the stop id) every poll is pure
-    // loss: each poll that finds no finished caption doubles the interval (up to 8), the first one that does resets it.
-    int na = nc, next_poll = 1, backoff = 1, last_alive = nc + 1;      // (+ 1: the first poll never backs off)
-    const int *cmap = nullptr;
-    CAPDEC_TRY(c->cmap.ensure(((size_t)nc + 1) * 4));
-    for (int i = 1; i < T; ++i) {
-        if (i >= next_poll) {
-            int alive = 0;
-            CAPDEC_TRY(poll_alive(c, &alive));
-            if (alive == 0) break;
-            const int rows_now = alive * beam;
-            const int base = rows_now >= 8192 ? 1 : rows_now >= 2048 ? 2 : rows_now >= 512 ? 4 : 8;
-            backoff = alive < last_alive ? 1 : std::min(8, backoff * 2);
-            last_alive = alive;
-            next_poll = i + std::min(8, std::max(base, backoff));
-            if (c->compact && alive <= na - std::max(1, na / 32)) {
-                ProfScope ps(c, F_SELECT);
-                CAPDEC_TRY(launch_compact_alive(c->stream, c->done.as<uint8_t>(), nc, c->cmap.as<int>(),
-                                                c->cmap.as<int>() + nc));
-                na = alive;
-                cmap = c->cmap.as<int>();
-                c->stat_compactions += 1;
-            }
-        }
+    // ---- steps 1..T-1: one token per row per step
+    const StepLoop loop{nc, 1, T, beam, c->done.as<uint8_t>(), nc};
+    CAPDEC_TRY(decode_steps(c, loop, nullptr, [&](int i, int na, const int *cmap) -> int {
         const int pos = P + i - 1;   // position of the token fed this step
         const int arows = na * beam;
-        c->stat_steps = std::max(c->stat_steps, i + 1);
-        c->stat_row_steps += arows;
-        if ((int)c->stat_step_rows.size() < i) c->stat_step_rows.resize(i, 0);     // (chunks of one call add up step by step)
-        c->stat_step_rows[i - 1] += arows;
-        CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
         {
             ProfScope ps(c, F_EMBED);
             CAPDEC_TRY(launch_embed_tokens(c->stream, c->next_tok.as<int>(), g.wte, g.wpe + (size_t)pos * d,
                                            c->h.as<float>(), arows, d, cmap, beam));
         }
-        StepShape sd{};
-        sd.prefill = false;
-        sd.rows = arows;
-        sd.beam = beam;
-        sd.L = pos + 1;
-        sd.anc = greedy ? nullptr : bs.anc;
-        sd.anc_stride = ctx;
-        sd.cmap = cmap;
-        CAPDEC_TRY(gpt2_body(c, sd, kv));
-        CAPDEC_TRY(select_and_advance(c->h.as<float>(), d, arows, i, beam, cmap));
-    }
-    if (!greedy) {
+        CAPDEC_TRY(gpt2_step(c, s.kv, arows, beam, pos + 1, s.anc, cmap));
+        return select_and_advance(c->h.as<float>(), d, arows, i, beam, cmap);
+    }));
+    if (!a.greedy) {
         ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_beam_finalize(c->stream, bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
-        if (a.glogp) CAPDEC_TRY(launch_group_beam_logp(c->stream, bs, nc, beam, a.order, a.glogp));
+        CAPDEC_TRY(launch_beam_finalize(c->stream, s.bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
+        if (a.glogp) CAPDEC_TRY(launch_group_beam_logp(c->stream, s.bs, nc, beam, a.order, a.glogp));
     }
     return 0;
 }
 
 static int decode_common(capdec_ctx *c, const float *prefix, int n, const DecodeCall &call) {
-    const int P = call.P, T = call.T, beam = call.beam;
-    const bool greedy = call.greedy;
-    const int *forced = call.forced;
-    CAPDEC_CHECK(c && c->gpt.loaded, "decode: GPT-2 weights not loaded");
-    CAPDEC_CHECK(n >= 0 && P >= 1 && T >= 1, "decode: bad sizes");
-    CAPDEC_CHECK(P + T - 1 <= c->gpt.n_pos, "decode: prefix + entry_length exceeds n_positions");
-    CAPDEC_CHECK(P + T - 1 <= 1024 && T <= 1024, "decode: context or entry_length > 1024 not supported");
+    const int P = call.P, T = call.T, beam = call.beam, ctx = P + T - 1;
+    CAPDEC_TRY(decode_call_checks(c, "decode", CK_LOADED | CK_SIZES | CK_CONTEXT, n, P, T, (long long)P + T - 1));
     CAPDEC_CHECK(beam >= 1 && beam <= 8, "decode: beam size must be in 1..8");
-    CAPDEC_CHECK(c->gpt.d / c->gpt.n_head == 64, "decode: head_dim must be 64");
-    CAPDEC_CHECK(forced || c->proc_bias_n == 0 || c->proc_bias_n == c->gpt.vocab,
-                 "decode: the logit bias was set for another vocabulary");
-    CAPDEC_HIP(hipSetDevice(c->device));
-    c->stat_steps = n > 0 ? 1 : 0;
-    c->stat_compactions = 0;
-    c->stat_chunks = 0;
-    c->stat_row_steps = 0;
-    c->stat_step_rows.clear();
-    c->stat_kv_slots = c->stat_kv_pos = 0.0;
-    c->kvstat_n = 0;
-    if (n == 0) return 0;
-    if (!greedy) {
-        CAPDEC_TRY(c->kvstat.ensure((size_t)n * 2 * sizeof(unsigned)));
-        CAPDEC_HIP(hipMemsetAsync(c->kvstat.p, 0, (size_t)n * 2 * sizeof(unsigned), c->stream));
-        c->kvstat_n = n;
-    }
-    const int ctx = P + T - 1;
-    const int chunk = chunk_captions(c, n, beam, ctx);
-    c->stat_chunks = (n + chunk - 1) / chunk;
-    // lm_head second-pass bookkeeping ([count, total, rows...], lm_head_select): sized once for the largest step, total zeroed
-    CAPDEC_TRY(c->lmflag.ensure(((size_t)std::min(chunk, n) * beam + 2) * 4));
-    CAPDEC_HIP(hipMemsetAsync(c->lmflag.p, 0, 2 * sizeof(int), c->stream));
-    c->lmflag_live = false;
-    c->k3_off = false;
-    c->k3_rows = 0;
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int nc = std::min(chunk, n - c0);
-        DecodeCall a = call;
-        a.ids += (size_t)c0 * beam * T;
-        a.lens += (size_t)c0 * beam;
-        if (a.scores) a.scores += (size_t)c0 * beam;
-        if (a.order) a.order += (size_t)c0 * beam;
-        if (a.forced) a.forced += (size_t)c0 * T;
-        if (a.stats) a.stats += (size_t)c0 * T * 3;
-        if (a.u) a.u += (size_t)c0 * T;
-        if (a.logp) a.logp += (size_t)c0 * T;
-        if (a.glogp) a.glogp += (size_t)c0 * beam;
-        a.cap_off = c0;
-        CAPDEC_TRY(decode_chunk(c, prefix + (size_t)c0 * P * c->gpt.d, nc, a));
-    }
-    CAPDEC_HIP(hipStreamSynchronize(c->stream));
+    CAPDEC_TRY(decode_call_checks(c, "decode", CK_HEAD_DIM | (call.forced ? 0 : CK_BIAS), n, P, T, ctx));
+    int chunk = 0;
+    CAPDEC_TRY(decode_call_begin(c, n, 1, call.greedy ? 0 : n, beam, ctx, 0, beam, &chunk));
+    for (int c0 = 0; c0 < n; c0 += chunk)
+        CAPDEC_TRY(decode_chunk(c, prefix + (size_t)c0 * P * c->gpt.d, std::min(chunk, n - c0), chunk_call(call, c0)));
+    if (n > 0) CAPDEC_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
-
 
 }  // namespace capdec
 

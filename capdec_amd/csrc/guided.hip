@@ -4,12 +4,15 @@
 // nc + j -- through the unchanged embedding, body, KV cache and ancestor-table attention.  A step is
 //   1. the body over the 2 * na * beam activation rows: the alive captions, then their partners (the compaction map lists
 //      them in that order);
-//   2. per block of cond rows: the materialised logits of the block and of its partner block (lm_head_logits, twice),
-//      guided_combine_kernel (g = gamma * log_softmax(cond) + (1 - gamma) * log_softmax(neg), written over the cond rows),
-//      the logits processors and the one-pass selection on the cond rows (process.hip);
-//   3. the greedy / beam step kernel of select.hip on the na * beam cond rows: the state lives with the cond half only;
+//   2. lm_head_rows (decode.hip) with the partner rows -- per block of cond rows: the materialised logits of the block and
+//      of its partner block, guided_combine_kernel (g = gamma * log_softmax(cond) + (1 - gamma) * log_softmax(neg), written
+//      over the cond rows), the logits processors and the one-pass selection on the cond rows (process.hip);
+//   3. decode_advance: the greedy / beam step kernel of select.hip on the na * beam cond rows -- the state (decode_state
+//      with two halves) lives with the cond half only;
 //   4. guided_mirror_kernel: the partner rows get their captions' next tokens and, for beam, the re-ordered ancestor rows.
-// Chunking, compaction and the adaptive poll are decode.hip's (decode_chunk); the plain path is not touched.
+// The step loop is decode.hip's decode_steps: 2 * beam rows per caption, a compaction map of 2 nc slots, and the partner map
+// as what follows a compaction.  Call checks, per-call reset and chunking are decode.hip's too; this file keeps the four
+// kernels, the prefill of both halves and the body of a step.
 #include "context.h"
 #include "row_select.h"
 
@@ -114,6 +117,8 @@ __global__ void guided_embed_neg_kernel(const float *__restrict__ neg, size_t ca
     reinterpret_cast<float4 *>(h)[i] = make_float4(a.x + w.x, a.y + w.y, a.z + w.z, a.w + w.w);
 }
 
+}  // namespace
+
 int launch_guided_combine(hipStream_t st, float *cond, const float *neg, int ld, int rows, int V, float gamma) {
     if (rows <= 0) return 0;
     CAPDEC_CHECK(ld >= V && ld % 4 == 0 && (((uintptr_t)cond | (uintptr_t)neg) & 15) == 0, "guided_combine: bad geometry");
@@ -121,6 +126,8 @@ int launch_guided_combine(hipStream_t st, float *cond, const float *neg, int ld,
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
+
+namespace {
 
 int launch_guided_mirror(hipStream_t st, int *next_tok, uint8_t *anc, int nact, int ncap, int beam, int ctx, int npos,
                          const int *cmap) {
@@ -131,104 +138,26 @@ int launch_guided_mirror(hipStream_t st, int *next_tok, uint8_t *anc, int nact, 
     return 0;
 }
 
-// One step's selection over R cond rows of h at hc and their partners at hn (row stride ldh): lm_head_rows of decode.hip
-// with the partner block's logits next to every cond block's and the combine in front of the processors.  The logits
-// scratch holds a block of both.
-int guided_rows(capdec_ctx *c, const float *hc, const float *hn, int ldh, int R, int k, float inv_temp, float gamma,
-                const DecodeCall &a, const int *cmap, bool proc, int step, int beam, const int *hist) {
-    const int V = c->gpt.vocab, ld = pad64(V), blk = std::min(R, std::max(1, c->tune.sample_rows));
-    const float *bias = c->proc_bias_n > 0 ? c->pbias.as<float>() : nullptr;
-    CAPDEC_TRY(c->slogits.ensure((size_t)2 * blk * ld * 4));
-    CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
-    CAPDEC_TRY(c->topv.ensure((size_t)R * k * 4));
-    CAPDEC_TRY(c->topi.ensure((size_t)R * k * 4));
-    float *lg = c->slogits.as<float>(), *ln = lg + (size_t)blk * ld;
-    for (int r0 = 0; r0 < R; r0 += blk) {
-        const int nr = std::min(blk, R - r0);
-        CAPDEC_TRY(lm_head_logits(c, hc + (size_t)r0 * ldh, ldh, nr, lg, ld));
-        CAPDEC_TRY(lm_head_logits(c, hn + (size_t)r0 * ldh, ldh, nr, ln, ld));
-        { ProfScope ps(c, F_GUIDED); CAPDEC_TRY(launch_guided_combine(c->stream, lg, ln, ld, nr, V, gamma)); }
-        ProfScope ps(c, F_SELECT);
-        if (proc)
-            CAPDEC_TRY(launch_logits_process(c->stream, lg, ld, nr, r0, V, cmap, beam, hist, a.T, step, c->proc, bias, a.stop_id,
-                                             a.alt_stop_id));
-        CAPDEC_TRY(launch_logits_select(c->stream, lg, ld, nr, V, k, inv_temp, c->lse.as<float>() + r0,
-                                        c->topv.as<float>() + (size_t)r0 * k, c->topi.as<int>() + (size_t)r0 * k));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- the driver: decode_chunk's loop over both halves
+// ---------------------------------------------------------------------------- the driver: both halves through decode_steps
 int guided_chunk(capdec_ctx *c, const float *prefix, const float *neg, size_t neg_stride, int nc, const DecodeCall &a,
                  float gamma) {
     const Gpt2 &g = c->gpt;
     const int d = g.d, P = a.P, T = a.T, beam = a.beam, ctx = P + T - 1;
-    const bool greedy = a.greedy;
-    const int rows = nc * beam, k = beam;           // cond rows; candidates kept per row
+    const int k = beam;                             // candidates kept per cond row
     const float inv_temp = 1.0f / (a.temperature > 0.f ? a.temperature : 1.0f);
     const bool proc = processors_on(c, false);
-    KvCache kv;
-    CAPDEC_TRY(ensure_kv(c, kv, 2 * rows, ctx));
-    kv.fixed_variant = c->batch_invariant;
-    kv.prefix_len = P;
-    CAPDEC_TRY(ensure_body_ws(c, 2 * std::max(nc * P, rows), d));
-    CAPDEC_TRY(c->next_tok.ensure((size_t)2 * rows * 4));
-    CAPDEC_TRY(c->alive.ensure(sizeof(int)));
-    CAPDEC_TRY(c->done.ensure((size_t)rows));
-    CAPDEC_TRY(c->cmap.ensure(((size_t)2 * nc + 1) * 4));
-    BeamState bs;
-    GreedyState gs;
-    if (!greedy) {
-        CAPDEC_TRY(c->tokens.ensure((size_t)rows * T * 4));
-        CAPDEC_TRY(c->scores.ensure((size_t)rows * 4));
-        CAPDEC_TRY(c->seq.ensure((size_t)rows * 4));
-        CAPDEC_TRY(c->stopped.ensure((size_t)rows));
-        CAPDEC_TRY(c->anc.ensure((size_t)2 * rows * ctx));
-        bs.tokens = c->tokens.as<int>();
-        bs.scores = c->scores.as<float>();
-        bs.seq = c->seq.as<float>();
-        bs.stopped = c->stopped.as<uint8_t>();
-        bs.done = c->done.as<uint8_t>();
-        bs.anc = c->anc.as<uint8_t>();
-        bs.next_tok = c->next_tok.as<int>();
-        bs.alive_count = c->alive.as<int>();
-        bs.kv_stat = c->kvstat.p ? c->kvstat.as<unsigned>() + (size_t)a.cap_off * 2 : nullptr;
-        CAPDEC_HIP(hipMemsetAsync(bs.tokens, 0, (size_t)rows * T * 4, c->stream));
-        CAPDEC_HIP(hipMemsetAsync(bs.anc, 0, (size_t)2 * rows * ctx, c->stream));
-    } else {
-        gs.ids = a.ids;
-        gs.lens = a.lens;
-        gs.done = c->done.as<uint8_t>();
-        gs.next_tok = c->next_tok.as<int>();
-        gs.alive_count = c->alive.as<int>();
-        gs.T = T;
-        gs.stop_id = a.stop_id;
-        gs.alt_stop_id = a.alt_stop_id;
-        CAPDEC_HIP(hipMemsetAsync(a.ids, 0, (size_t)nc * T * 4, c->stream));
-        CAPDEC_HIP(hipMemsetAsync(a.lens, 0, (size_t)nc * 4, c->stream));
-    }
-    CAPDEC_HIP(hipMemsetAsync(c->done.p, 0, (size_t)rows, c->stream));
-    CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
-    const int *hist = greedy ? a.ids : bs.tokens;
-    uint8_t *anc = greedy ? nullptr : bs.anc;
+    DecodeState s;
+    CAPDEC_TRY(decode_state(c, nc, a, 2, &s));
 
     // the guided selection over R cond rows (partners at hn), the step kernel of the decode on the cond half, then the mirror:
     // ncap_act captions are in the batch, npos ancestor positions are valid after the step
     auto select_and_advance = [&](const float *hc, const float *hn, int ldh, int R, int step, int hbeam, const int *cmap,
                                   int ncap_act, int npos) -> int {
-        gs.cmap = cmap;
-        CAPDEC_TRY(guided_rows(c, hc, hn, ldh, R, k, inv_temp, gamma, a, cmap, proc, step, hbeam, hist));
-        {
-            ProfScope ps(c, F_SELECT);
-            const float *lse = c->lse.as<float>(), *topv = c->topv.as<float>();
-            const int *topi = c->topi.as<int>();
-            if (greedy) CAPDEC_TRY(launch_greedy_step(c->stream, gs, topi, R, step, k));
-            else if (step == 0) CAPDEC_TRY(launch_beam_init(c->stream, bs, lse, topv, topi, R, beam, k, T, ctx, P, a.stop_id));
-            else CAPDEC_TRY(launch_beam_step(c->stream, bs, lse, topv, topi, R / beam, beam, k, T, ctx, step, P + step - 1, g.vocab,
-                                             a.stop_id, cmap));
-        }
+        s.gs.cmap = cmap;
+        CAPDEC_TRY(lm_head_rows(c, hc, ldh, R, k, inv_temp, a, s.gs, proc, step, hbeam, s.hist, hn, gamma));
+        CAPDEC_TRY(decode_advance(c, a, s, R, step, k, cmap));
         ProfScope ps(c, F_GUIDED);
-        return launch_guided_mirror(c->stream, c->next_tok.as<int>(), anc, ncap_act, nc, beam, ctx, npos, cmap);
+        return launch_guided_mirror(c->stream, c->next_tok.as<int>(), s.anc, ncap_act, nc, beam, ctx, npos, cmap);
     };
 
     // ---- step 0: prefill both prefixes (captions 0..nc-1 and their partners nc..2nc-1), logits of the last prefix rows
@@ -246,59 +175,31 @@ int guided_chunk(capdec_ctx *c, const float *prefix, const float *neg, size_t ne
     sp.ncap = 2 * nc;
     sp.P = P;
     sp.beam = beam;
-    CAPDEC_TRY(gpt2_body(c, sp, kv));
+    CAPDEC_TRY(gpt2_body(c, sp, s.kv));
     CAPDEC_TRY(select_and_advance(h + (size_t)(P - 1) * d, h + ((size_t)nc * P + P - 1) * d, P * d, nc, 0, 1, nullptr, nc, 0));
 
-    // ---- steps 1..T-1 (poll cadence and compaction: decode_chunk; rows are counted as launched, both halves)
-    int na = nc, next_poll = 1, backoff = 1, last_alive = nc + 1;
-    const int *cmap = nullptr;
-    for (int i = 1; i < T; ++i) {
-        if (i >= next_poll) {
-            int alive = 0;
-            CAPDEC_TRY(poll_alive(c, &alive));
-            if (alive == 0) break;
-            const int rows_now = 2 * alive * beam;
-            const int base = rows_now >= 8192 ? 1 : rows_now >= 2048 ? 2 : rows_now >= 512 ? 4 : 8;
-            backoff = alive < last_alive ? 1 : std::min(8, backoff * 2);
-            last_alive = alive;
-            next_poll = i + std::min(8, std::max(base, backoff));
-            if (c->compact && alive <= na - std::max(1, na / 32)) {
-                ProfScope ps(c, F_SELECT);
-                int *m = c->cmap.as<int>();
-                CAPDEC_TRY(launch_compact_alive(c->stream, c->done.as<uint8_t>(), nc, m, m + 2 * nc));
-                na = alive;
-                hipLaunchKernelGGL(guided_partner_map_kernel, dim3((na + 255) / 256), dim3(256), 0, c->stream, m, na, nc);
-                CAPDEC_HIP(hipGetLastError());
-                cmap = m;
-                c->stat_compactions += 1;
-            }
-        }
+    // ---- steps 1..T-1: 2 * beam rows per caption (rows are counted as launched, both halves); a new compaction map gets
+    // the partners of its captions listed behind them
+    const StepLoop loop{nc, 1, T, 2 * beam, c->done.as<uint8_t>(), 2 * nc};
+    auto partners = [&](int *cmap, int na) -> int {
+        hipLaunchKernelGGL(guided_partner_map_kernel, dim3((na + 255) / 256), dim3(256), 0, c->stream, cmap, na, nc);
+        CAPDEC_HIP(hipGetLastError());
+        return 0;
+    };
+    CAPDEC_TRY(decode_steps(c, loop, partners, [&](int i, int na, const int *cmap) -> int {
         const int pos = P + i - 1;   // position of the token fed this step
         const int arows = na * beam; // cond rows; the step launches 2 * arows
-        c->stat_steps = std::max(c->stat_steps, i + 1);
-        c->stat_row_steps += 2 * arows;
-        if ((int)c->stat_step_rows.size() < i) c->stat_step_rows.resize(i, 0);
-        c->stat_step_rows[i - 1] += 2 * arows;
-        CAPDEC_HIP(hipMemsetAsync(c->alive.p, 0, sizeof(int), c->stream));
         {
             ProfScope ps(c, F_EMBED);
             CAPDEC_TRY(launch_embed_tokens(c->stream, c->next_tok.as<int>(), g.wte, g.wpe + (size_t)pos * d, h, 2 * arows, d,
                                            cmap, beam));
         }
-        StepShape sd{};
-        sd.prefill = false;
-        sd.rows = 2 * arows;
-        sd.beam = beam;
-        sd.L = pos + 1;
-        sd.anc = anc;
-        sd.anc_stride = ctx;
-        sd.cmap = cmap;
-        CAPDEC_TRY(gpt2_body(c, sd, kv));
-        CAPDEC_TRY(select_and_advance(h, h + (size_t)arows * d, d, arows, i, beam, cmap, na, pos + 1));
-    }
-    if (!greedy) {
+        CAPDEC_TRY(gpt2_step(c, s.kv, 2 * arows, beam, pos + 1, s.anc, cmap));
+        return select_and_advance(h, h + (size_t)arows * d, d, arows, i, beam, cmap, na, pos + 1);
+    }));
+    if (!a.greedy) {
         ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_beam_finalize(c->stream, bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
+        CAPDEC_TRY(launch_beam_finalize(c->stream, s.bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
     }
     return 0;
 }
@@ -321,50 +222,25 @@ extern "C" int capdec_decode_guided(capdec_ctx *c, const float *prefix, const fl
     if (guidance_scale == 1.0f)         // off: the plain call, no negative rows
         return beam == 1 ? capdec_decode_greedy(c, prefix, n, P, stop_id, alt_stop_id, T, ids, lens)
                          : capdec_decode_beam(c, prefix, n, P, beam, stop_id, T, temperature, ids, lens, scores, order);
-    CAPDEC_CHECK(c->gpt.loaded, "decode_guided: GPT-2 weights not loaded");
-    CAPDEC_CHECK(P >= 1 && T >= 1, "decode_guided: bad sizes");
-    CAPDEC_CHECK((long long)P + T - 1 <= c->gpt.n_pos, "decode_guided: prefix + entry_length exceeds n_positions");
-    CAPDEC_CHECK((long long)P + T - 1 <= 1024 && T <= 1024, "decode_guided: context or entry_length > 1024 not supported");
-    CAPDEC_CHECK(c->gpt.d / c->gpt.n_head == 64, "decode_guided: head_dim must be 64");
+    const char *who = "decode_guided";
+    CAPDEC_TRY(decode_call_checks(c, who, CK_LOADED | CK_SIZES | CK_CONTEXT | CK_HEAD_DIM, n, P, T, (long long)P + T - 1));
     CAPDEC_CHECK(c->gpt.vocab >= beam, "decode_guided: vocabulary smaller than the beam");
-    CAPDEC_CHECK(c->proc_bias_n == 0 || c->proc_bias_n == c->gpt.vocab,
-                 "decode_guided: the logit bias was set for another vocabulary");
-    CAPDEC_HIP(hipSetDevice(c->device));
-    c->stat_steps = n > 0 ? 1 : 0;
-    c->stat_compactions = 0;
-    c->stat_chunks = 0;
-    c->stat_row_steps = 0;
-    c->stat_step_rows.clear();
-    c->stat_kv_slots = c->stat_kv_pos = 0.0;
-    c->kvstat_n = 0;
-    if (n == 0) return 0;
+    CAPDEC_TRY(decode_call_checks(c, who, CK_BIAS, n, P, T, 0));
     const int d = c->gpt.d, ctx = P + T - 1;
-    if (beam > 1) {
-        CAPDEC_TRY(c->kvstat.ensure((size_t)n * 2 * sizeof(unsigned)));
-        CAPDEC_HIP(hipMemsetAsync(c->kvstat.p, 0, (size_t)n * 2 * sizeof(unsigned), c->stream));
-        c->kvstat_n = n;
-    }
-    // a caption and its partner share a chunk: the partner's K/V counts against the budget as much again
+    // a caption and its partner share a chunk: the partner's K/V counts against the budget as much again.  (The fused
+    // lm_head never runs here.)
     const size_t kv_per_cap = (size_t)beam * ctx * d * 2 * (c->gemm_mode == GEMM_BF16 ? 2 : 4) * c->gpt.n_layer;
-    const int chunk = chunk_captions(c, n, beam, ctx, kv_per_cap);
-    c->stat_chunks = (n + chunk - 1) / chunk;
-    c->lmflag_live = false;             // (the fused lm_head's second pass never runs here: poll_alive has nothing to watch)
-    c->k3_off = false;
-    c->k3_rows = 0;
-    DecodeCall a;
-    a.P = P; a.beam = beam; a.greedy = beam == 1; a.stop_id = stop_id; a.alt_stop_id = beam == 1 ? alt_stop_id : -1;
-    a.T = T; a.temperature = temperature;
+    int chunk = 0;
+    CAPDEC_TRY(decode_call_begin(c, n, 1, beam > 1 ? n : 0, beam, ctx, kv_per_cap, 0, &chunk));
+    if (n == 0) return 0;
+    DecodeCall call;
+    call.P = P; call.beam = beam; call.greedy = beam == 1; call.stop_id = stop_id; call.alt_stop_id = beam == 1 ? alt_stop_id : -1;
+    call.T = T; call.temperature = temperature;
+    call.ids = ids; call.lens = lens; call.scores = scores; call.order = order;
     const size_t neg_stride = neg_n == 1 ? 0 : (size_t)P * d;
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int nc = std::min(chunk, n - c0);
-        a.ids = ids + (size_t)c0 * beam * T;
-        a.lens = lens + (size_t)c0 * beam;
-        a.scores = scores ? scores + (size_t)c0 * beam : nullptr;
-        a.order = order ? order + (size_t)c0 * beam : nullptr;
-        a.cap_off = c0;
-        CAPDEC_TRY(guided_chunk(c, prefix + (size_t)c0 * P * d, neg_prefix + (size_t)c0 * neg_stride, neg_stride, nc, a,
-                                guidance_scale));
-    }
+    for (int c0 = 0; c0 < n; c0 += chunk)
+        CAPDEC_TRY(guided_chunk(c, prefix + (size_t)c0 * P * d, neg_prefix + (size_t)c0 * neg_stride, neg_stride,
+                                std::min(chunk, n - c0), chunk_call(call, c0), guidance_scale));
     CAPDEC_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -29,7 +29,7 @@ namespace capdec {
 namespace {
 
 constexpr int PRC_THREADS = 256, PRC_WAVES = PRC_THREADS / WAVE;
-constexpr int PRC_HIST_MAX = 1024;      // entry_length <= 1024 (decode_common)
+constexpr int PRC_HIST_MAX = 1024;      // entry_length <= 1024 (decode_call_checks)
 constexpr int TOPK_THREADS = 1024, TOPK_WAVES = TOPK_THREADS / WAVE;
 
 // history row of logits row r of a block: activation row row0 + r of the step, exactly as greedy_step_kernel (beam == 1)
