@@ -155,6 +155,8 @@ SIGNATURES = {
     "capdec_score": (C.c_int, [_VP, _VP, _VP, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP, _VP]),
     "capdec_score_chunks": (C.c_int, [_VP, C.POINTER(C.c_int)]),
     "capdec_nearest_tokens": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
+    "capdec_embed_moments": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP]),
+    "capdec_group_distances": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, c_int_p, C.c_int, _VP]),
     "capdec_decode_beam": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP,
                                      _VP, _VP]),
     "capdec_decode_beam_groups": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float,

@@ -12,6 +12,7 @@
 //   contrastive.hip   capdec_decode_contrastive: contrastive search, a driver on decode.hip's loop (its selection kernels)
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   nearest.hip       capdec_nearest_tokens: nearest table rows by cosine similarity (the normalised-wte cache, row blocks)
+//   gap_stats.hip     capdec_embed_moments, capdec_group_distances: modality offset and paraphrase spread, fp64 sums
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
 //                     forward share (tlayer_self_front / tlayer_tail)
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
@@ -198,6 +199,7 @@ struct capdec_ctx {
     bool wte_n_valid = false;              // [vocab, d] -- built on first use, its operand planes cached by planes_of like a weight's;
                                            // dropped with the wte it was made from (drop_wte_norm)
     DBuf n_tab, n_bad;                     // ... a caller's table normalised for one call; [table flag | one flag per row of a block]
+    DBuf gap_ws, gap_ws2, gap_off;         // gap_stats.hip: fp64 partial sums per slab and their folds; [flag | group offsets]
     capdec::LogitsProc proc;               // capdec_set_logits_processors (defaults: every processor off)
     int proc_bias_n = 0;                   // capdec_set_logit_bias: entries of `pbias` (0 = no bias)
     DBuf pbias, pcorr;     // the logit bias [vocab]; a row block's logp shift under top_k (decode.hip: lm_head_rows)

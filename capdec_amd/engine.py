@@ -754,6 +754,62 @@ class Engine:
         ids = ids.view(*lead, int(k))
         return (ids, sims.view(*lead, int(k))) if return_sims else ids
 
+    # ------------------------------------------------------------------ noise variance and modality offset
+    MOMENT_ROWS = ("mean_a", "mean_b", "mean_diff", "std_a", "std_b", "std_diff", "absmean_diff")
+
+    def embed_moments(self, a: torch.Tensor, b: Optional[torch.Tensor] = None, normalize: bool = True,
+                      return_pair: bool = False) -> Dict[str, torch.Tensor]:
+        """column moments of the paired embeddings ``a`` (images) and ``b`` (texts), both [n, dim], every row first divided
+        by its L2 norm unless ``normalize`` is off (capdec_embed_moments; the contract: include/capdec.h) -> fp32 [dim]
+        tensors ``mean_a, mean_b, mean_diff`` (= mean of b - a), ``std_a, std_b, std_diff`` (unbiased), ``absmean_diff``,
+        and with ``return_pair`` ``pair`` [n, 2] = (||b_i - a_i||_2, ||b_i - a_i||_inf).  Without ``b`` only ``mean_a`` and
+        ``std_a`` are computed; the others are 0."""
+        if a.dim() != 2 or (b is not None and tuple(b.shape) != tuple(a.shape)):
+            raise CapdecError("embed_moments: a and b must both be [n, dim]")
+        if return_pair and b is None:
+            raise CapdecError("embed_moments: return_pair needs b")
+        n, dim = int(a.shape[0]), int(a.shape[1])
+        xa = self._dev(a)
+        xb = self._dev(b) if b is not None else None
+        stats = torch.empty(7, dim, device=self.device, dtype=torch.float32)
+        pair = torch.empty(n, 2, device=self.device, dtype=torch.float32) if return_pair else None
+        self._sync_stream()
+        self._chk(self.lib.capdec_embed_moments(self._h, xa.data_ptr() if n else None, xb.data_ptr() if xb is not None and n else None,
+                                                n, dim, int(bool(normalize)), stats.data_ptr(),
+                                                pair.data_ptr() if pair is not None and n else None), "capdec_embed_moments")
+        out = {name: stats[i] for i, name in enumerate(self.MOMENT_ROWS)}
+        if return_pair:
+            out["pair"] = pair
+        return out
+
+    def group_distances(self, x: torch.Tensor, offsets, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """distances inside groups of rows of ``x`` [rows, W] (capdec_group_distances; the contract: include/capdec.h): group
+        k is the rows ``index[offsets[k]:offsets[k + 1]]`` (``index`` None: those row numbers themselves), 1 to 8 rows each;
+        ``offsets`` is a host vector [groups + 1].  -> fp32 [groups, 8]: pair L1 / (W c), pair L2 / (W c), pair L-inf / c, max
+        pair L2 / sqrt(W), mean L2 to the group's centre, mean L-inf to it, c = g (g - 1) / 2, g."""
+        if x.dim() != 2:
+            raise CapdecError("group_distances: x must be [rows, W]")
+        raw = (offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)).reshape(-1)
+        if raw.shape[0] < 1:
+            raise CapdecError("group_distances: offsets must have groups + 1 entries")
+        if not np.issubdtype(raw.dtype, np.integer) or int(raw.min()) < -2 ** 31 or int(raw.max()) >= 2 ** 31:
+            raise CapdecError("group_distances: offsets must be integers that fit 32 bits")      # (astype would wrap them)
+        off = np.ascontiguousarray(raw.astype(np.int32))
+        groups = int(off.shape[0]) - 1
+        idx = None
+        if index is not None:
+            idx = self._dev(index.reshape(-1), torch.int32)
+            if groups and int(idx.shape[0]) < int(off[-1]):
+                raise CapdecError(f"group_distances: offsets end at {int(off[-1])} but index has {int(idx.shape[0])} entries")
+        xs = self._dev(x)
+        out = torch.empty(groups, 8, device=self.device, dtype=torch.float32)
+        self._sync_stream()
+        self._chk(self.lib.capdec_group_distances(self._h, xs.data_ptr() if xs.numel() else None, int(xs.shape[0]), int(xs.shape[1]),
+                                                  idx.data_ptr() if idx is not None and idx.numel() else None,
+                                                  off.ctypes.data_as(_capi.c_int_p), groups,
+                                                  out.data_ptr() if groups else None), "capdec_group_distances")
+        return out
+
     # ------------------------------------------------------------------ caption-shard communicator (RCCL through the C ABI)
     def comm_unique_id(self) -> bytes:
         """rank 0: the 128-byte communicator id every rank passes to :meth:`comm_init`"""

@@ -2,15 +2,23 @@
 (:194-234,300-301): embeddings -> normalise (+ modality offset) -> ``clip_project`` ->
 ``generate_beam`` / ``generate2`` -> ``{"caption": text.lower(), "image_id": ...}``.
 ``generate_beam`` / ``generate2`` are re-exported here because the reference imports them
-into this module (:13) and BASELINE.json's north_star names them under it."""
+into this module (:13) and BASELINE.json's north_star names them under it.
+
+The distance ablations of the reference (``--ablation_dist``: :18-95 and :235-251; ``--ablation_image_dist``: :240-247) are here
+too, under its names: ``count_ready_parphrased_embeddings``, ``calc_distances_of_ready_embeddings``, and their batched forms
+``paraphrase_distances``, ``paraphrase_distance_ablation``, ``image_text_distance`` and ``estimate_noise_variance``.  The
+pair loops run in ``Engine.group_distances`` (capdec_group_distances: one block per image); host numpy only sees the
+[groups, 8] result."""
 from __future__ import annotations
 
 import json
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import distributed as cdist
+from .engine import Engine, get_engine
 from .gpt2_prefix import ClipCaptionModel, MappingType  # noqa: F401
 from .gpt2_prefix_eval import (decode_beam_ids, decode_greedy_ids, generate2, generate2_batch,  # noqa: F401
                                generate_beam, generate_beam_batch)
@@ -208,3 +216,138 @@ def make_preds_from_captions(data: Sequence[Dict], clip_model, model: ClipCaptio
         with open(out_path, 'w') as outfile:
             json.dump(new_data, outfile)
     return new_data
+
+
+# ---------------------------------------------------------------------------- distance ablations
+def count_ready_parphrased_embeddings(embeddings_dict):
+    """reference :18-24: how many images have all five of their captions' embeddings"""
+    ready = 0
+    for img_id in embeddings_dict.keys():
+        if embeddings_dict[img_id] is not None:
+            if len(embeddings_dict[img_id]) == 5:
+                ready += 1
+    return ready
+
+
+def _group_by_image(image_ids):
+    """rows grouped by image id in order of first appearance (the insertion order of the reference's dict), a group's rows
+    in input order -> (index int32 [N], offsets int32 [groups + 1], the ids)"""
+    if hasattr(image_ids, "tolist"):        # a tensor or an array: its elements would hash by identity, one group per row
+        image_ids = image_ids.tolist()
+    rows: Dict = {}
+    for r, i in enumerate(image_ids):
+        rows.setdefault(i, []).append(r)
+    index = np.array([r for v in rows.values() for r in v], np.int32)
+    offsets = np.concatenate([[0], np.cumsum([len(v) for v in rows.values()])]).astype(np.int32)
+    return index, offsets, list(rows)
+
+
+def paraphrase_distances(prefix_embed: torch.Tensor, clip_embed: torch.Tensor, image_ids: Sequence,
+                         engine: Optional[Engine] = None):
+    """The batched ``--ablation_dist``: row r of ``prefix_embed`` [N, W1] (a caption's mapped prefix, flattened) and of
+    ``clip_embed`` [N, W2] (its CLIP embedding) belongs to image ``image_ids[r]``.  -> (prefix [groups, 8], clip [groups, 8],
+    ids): per image, in order of first appearance, the columns of ``Engine.group_distances`` as host numpy.  The rows are
+    grouped through an index, never gathered."""
+    if len(image_ids) != prefix_embed.shape[0] or len(image_ids) != clip_embed.shape[0]:
+        raise ValueError(f"paraphrase_distances: {len(image_ids)} image ids but {prefix_embed.shape[0]} prefix rows and "
+                         f"{clip_embed.shape[0]} CLIP rows")
+    eng = engine or get_engine()
+    index, offsets, ids = _group_by_image(image_ids)
+    idx = torch.tensor(index, dtype=torch.int32, device=eng.device)
+    pre = eng.group_distances(prefix_embed.reshape(prefix_embed.shape[0], -1), offsets, idx).cpu().numpy()
+    clp = eng.group_distances(clip_embed.reshape(clip_embed.shape[0], -1), offsets, idx).cpu().numpy()
+    return pre, clp, ids
+
+
+def _print_distances(pre: np.ndarray, clp: np.ndarray):
+    """reference :59-88 on the per-image columns: the pair statistics over the images with exactly five captions, the
+    to-centre statistics over every image"""
+    five = clp[:, 7] == 5
+    distances, distances_l2 = pre[five, 0].astype(np.float64), pre[five, 1].astype(np.float64)
+    distances_clip, distances_l2_clip = clp[five, 0].astype(np.float64), clp[five, 1].astype(np.float64)
+    max_distances_l1, maxoutof5 = clp[five, 2].astype(np.float64), clp[five, 3].astype(np.float64)
+    distances_l2_from_center, max_distances_l1_from_center = clp[:, 4].astype(np.float64), clp[:, 5].astype(np.float64)
+    print(
+        f"\n\n\n Average noremlised L1 between 5 annotations of same image MAPPER: {np.array(distances).mean()}, STD: {np.array(distances).std()}")
+    print(
+        f"\n\n\n Average noremlised L2 between 5 annotations of same image MAPPER: {np.array(distances_l2).mean()}, STD: {np.array(distances_l2).std()}")
+    print(
+        f"\n\n\n Average noremlised L1 between 5 annotations of same image CLIP: {np.array(distances_clip).mean()}, STD: {np.array(distances_clip).std()}")
+    print(
+        f"\n\n\n Average noremlised L2 between 5 annotations of same image CLIP: {np.array(distances_l2_clip).mean()}, STD: {np.array(distances_l2_clip).std()}")
+    print(
+        f"\n\n\n Mean L2 between 5 annotations of same image CLIP to their center: {np.array(distances_l2_from_center).mean()}, STD: {np.array(distances_l2_from_center).std()}")
+    print(
+        f"\n\n\n Max (per-entry) L1 between 5 annotations of same image CLIP to their center: {np.array(max_distances_l1_from_center).mean()}, STD: {np.array(max_distances_l1_from_center).std()}")
+    print(
+        f"\n\n\n Max (per-entry) L1 between 5 annotations of same image CLIP: {np.array(max_distances_l1).mean()}, STD: {np.array(max_distances_l1).std()}")
+    print(
+        f"\n\n\n Taking max out of the 10 L2 between 5 annotations of same image CLIP: {np.array(maxoutof5).mean()}")
+    return (list(distances), list(distances_l2), list(distances_clip), list(distances_l2_clip), list(max_distances_l1))
+
+
+def calc_distances_of_ready_embeddings(embeddings_dict, out_file='embeddings_distances.pkl'):
+    """reference :32-95.  ``embeddings_dict``: image id -> list of ``(prefix_embed, clip_embed)`` arrays, one per caption
+    (at most eight per image).  Prints the reference's eight lines and returns its ``(distances, distances_l2,
+    distances_clip, distances_l2_clip, data_size)``; with an ``out_file`` it also writes the reference's pickle
+    (``distances_clip``, ``distances_l2_clip``, ``max_distances_l1``).  One deviation: it then RETURNS -- the reference calls
+    ``exit(0)`` there."""
+    ids = [i for i in embeddings_dict.keys() for _ in embeddings_dict[i]]
+    pairs = [p for i in embeddings_dict.keys() for p in embeddings_dict[i]]
+    if not pairs:
+        raise ValueError("calc_distances_of_ready_embeddings: no embeddings")
+    prefix = torch.tensor(np.stack([np.asarray(p[0], np.float32).reshape(-1) for p in pairs]))
+    clip_e = torch.tensor(np.stack([np.asarray(p[1], np.float32).reshape(-1) for p in pairs]))
+    pre, clp, groups = paraphrase_distances(prefix, clip_e, ids)
+    distances, distances_l2, distances_clip, distances_l2_clip, max_distances_l1 = _print_distances(pre, clp)
+    data_size = len(groups)
+    if out_file is not None:
+        import pickle
+        with open(out_file, 'wb') as f:
+            pickle.dump(({"distances_clip": distances_clip, "distances_l2_clip": distances_l2_clip, "max_distances_l1": max_distances_l1}), f)
+        print(f"Saved distances to {out_file} and finished")
+    return distances, distances_l2, distances_clip, distances_l2_clip, data_size
+
+
+def paraphrase_distance_ablation(data: Sequence[Dict], clip_model, model: ClipCaptionModel, tokenize=None,
+                                 dont_normalize_prefix: bool = False, modality_offset: Optional[torch.Tensor] = None,
+                                 text_batch: int = 2048):
+    """The ``--ablation_dist`` run of the reference on its text-input data (``dataset_mode`` 5; :215-228, :235-239) as one
+    batch: ``data[i]`` = {"image_id", "caption"}; captions -> ``clip_model.encode_text`` -> normalise (+ modality offset) ->
+    ``model.clip_project`` -> the distances among each image's prefixes and among its CLIP embeddings.  Nothing passes
+    through the host in between.  -> what ``paraphrase_distances`` returns."""
+    if tokenize is None:
+        from .clip import tokenize
+    feats = []
+    for b0 in range(0, len(data), max(1, text_batch)):
+        feats.append(clip_model.encode_text(tokenize([d["caption"] for d in data[b0:b0 + max(1, text_batch)]])).float())
+    if not feats:
+        raise ValueError("paraphrase_distance_ablation: no captions")
+    eng = model.engine
+    prefix = eng.normalize_prefix(torch.cat(feats), normalize=not dont_normalize_prefix, offset=modality_offset)
+    prefix_embed = model.clip_project(prefix).reshape(prefix.shape[0], -1)
+    return paraphrase_distances(prefix_embed, prefix, [d["image_id"] for d in data], eng)
+
+
+def image_text_distance(image_embeddings: torch.Tensor, text_embeddings: torch.Tensor, engine: Optional[Engine] = None) -> float:
+    """the ``--ablation_image_dist`` number (reference :240-247 and its final average): the mean over the rows of the L2
+    distance between the normalised image embedding and the normalised embedding of its caption"""
+    pair = (engine or get_engine()).embed_moments(image_embeddings, text_embeddings, normalize=True, return_pair=True)["pair"]
+    return float(pair.cpu().numpy()[:, 0].astype(np.float64).mean())
+
+
+def estimate_noise_variance(text_embeddings: torch.Tensor, image_ids: Sequence, normalize: bool = True,
+                            engine: Optional[Engine] = None) -> float:
+    """The quantity ``--noise_variance 0.016`` of the reference's README stands for: over the images with at least two
+    captions, the mean of the per-entry maximum distance between the CLIP text embeddings of captions that describe the same
+    image, averaged over the image's pairs -- the reference's "Max (per-entry) L1 between 5 annotations of same image CLIP"
+    (:55, :65, :86), here for any 2 to 8 captions per image.  ``text_embeddings`` [N, D]; ``image_ids[r]`` the image of row
+    r; ``normalize``: divide every row by its L2 norm first, as the reference's inference path does (:221-222)."""
+    eng = engine or get_engine()
+    x = eng.normalize_prefix(text_embeddings, normalize=True) if normalize else text_embeddings
+    index, offsets, _ = _group_by_image(image_ids)
+    out = eng.group_distances(x, offsets, torch.tensor(index, dtype=torch.int32, device=eng.device)).cpu().numpy()
+    many = out[:, 7] >= 2
+    if not many.any():
+        raise ValueError("estimate_noise_variance: no image has two captions")
+    return float(out[many, 2].astype(np.float64).mean())

@@ -552,6 +552,63 @@ int capdec_score_chunks(capdec_ctx *ctx, int *chunks);
 int capdec_nearest_tokens(capdec_ctx *ctx, const float *d_x /* [rows, d] */, int rows, int d,
                           const float *d_table /* [table_rows, d] or NULL = wte */, int table_rows,
                           int k, int32_t *d_ids /* [rows, k] */, float *d_sims /* [rows, k] or NULL */);
+/* ---- noise variance and modality offset from embeddings -------------------------------- */
+/* Column moments of two sets of embeddings, paired row by row: what reference others/modality_offset_calculator.py
+ * (get_centers_info, get_variance_info) computes with fp32 torch on the host, and the per-row image-text distance that
+ * predictions_runner.py's --ablation_image_dist averages.  With normalize != 0 every row is first divided by its L2 norm
+ * (x /= torch.norm(x, dim=1, keepdim=True)).  Rows of d_stats [7, dim]:
+ *   0, 1     column means of a and of b
+ *   2        column mean of b - a: offset_to_add_in_inference (the training offset is its negative)
+ *   3, 4, 5  unbiased column standard deviations (torch.std, divisor n - 1) of a, b and b - a
+ *   6        column mean of |b - a|
+ * d_pair[i] (may be NULL) = (||b_i - a_i||_2, ||b_i - a_i||_inf) of the (normalised) rows.  d_b == NULL: rows 0 and 3 only,
+ * the other rows are set to 0, and d_pair must be NULL.
+ *   - Every sum -- row norms, column sums, sums of squares -- is taken in fp64; the outputs are the fp32 roundings.
+ *   - Deterministic, no floating-point atomics: rows are split into slabs of a fixed 64 rows, each block writes its slab's
+ *     fp64 sums to a workspace of the context, and these are added in slab order (32 consecutive partials at a time, level
+ *     by level).  Two calls on the same input return the same bits; a row's d_pair does not depend on n.
+ *   - Every input row is read from global memory twice, once by the norm pass and once by the column pass of the same
+ *     block.  With several 160-330 KB slabs live per CU the second read is NOT known to hit L2 or the Infinity Cache;
+ *     HBM traffic was not measured and may be up to twice the input.
+ *   - The deviations come from the sums and the sums of squares, (sum x^2 - (sum x)^2 / n) / (n - 1) in fp64: about
+ *     1e-16 (mean / std)^2 of relative error in the variance.  That is nothing for embeddings; a column whose std is below
+ *     about 1e-5 of its |mean| loses its digits, and a constant column may return a tiny non-zero std where torch returns 0
+ *     (a negative variance is returned as 0).
+ *   - Limits, each refused with capdec_last_error and the context left usable: n >= 1 (with n == 1 the standard deviations
+ *     are NaN, as in torch); dim a multiple of 4, at most 1024.  d_a and d_b are 16-byte aligned.
+ *   - A zero row under normalize gives NaN, and NaN / inf propagate, exactly where the torch expressions give them: through
+ *     every statistic that row's side enters and through that row's d_pair.  No address depends on a value.
+ *   - The call enqueues on the context's stream and synchronises before it returns.
+ * (Added without a new ABI number, like capdec_nearest_tokens.) */
+int capdec_embed_moments(capdec_ctx *ctx, const float *d_a /* [n, dim] images */,
+                         const float *d_b /* [n, dim] texts, or NULL */, int n, int dim, int normalize,
+                         float *d_stats /* [7, dim] */, float *d_pair /* [n, 2] or NULL */);
+/* Distances inside groups of rows: reference predictions_runner.py calc_distances_of_ready_embeddings (:32-95) for every
+ * image's captions at once.  Group k is the rows d_index[h_offsets[k] .. h_offsets[k + 1]) of d_x (d_index == NULL: those row
+ * numbers themselves), so the caller groups by image id without a gather.  Per group of g rows with c = g (g - 1) / 2 pairs,
+ * d_out[k, 0..8) (columns 0-3 over the pair differences x_i - x_j; m = the group's mean row):
+ *   0  sum ||x_i - x_j||_1 / (W c)
+ *   1  sum ||x_i - x_j||_2 / (W c)      (the reference's own normalisation, kept although its comment calls it wrong)
+ *   2  sum ||x_i - x_j||_inf / c        (its mean over the images is what --noise_variance stands for)
+ *   3  max over the pairs of ||x_i - x_j||_2 / sqrt(W)
+ *   4  mean over the rows of ||x_i - m||_2
+ *   5  mean over the rows of ||x_i - m||_inf
+ *   6  c          7  g
+ * g == 1: columns 0-3 and c are 0, and so are the to-centre columns.
+ *   - One block per group walks the columns once; sums of |d| and d^2 are taken in fp64, maxima in fp32 (the fp32 rounding of
+ *     an exact difference: column 2 of a two-row group is bit-exact); the square roots and divisions are fp64, the outputs
+ *     their fp32 roundings.  A NaN propagates into every column it enters.
+ *   - Limits, each refused with capdec_last_error before the group kernel is launched, the context left usable:
+ *     1 <= g <= 8 (h_offsets ascends strictly, from a value >= 0); W a positive multiple of 4; groups >= 0 (groups == 0
+ *     succeeds and touches nothing); every index in [0, rows) -- d_index is checked by a small kernel whose flag the call
+ *     reads first; without d_index, h_offsets[groups] <= rows.  No row outside the array is ever read.  d_x is 16-byte
+ *     aligned.
+ *   - The call enqueues on the context's stream and synchronises before it returns.
+ * (Added without a new ABI number, like capdec_nearest_tokens.) */
+int capdec_group_distances(capdec_ctx *ctx, const float *d_x /* [rows, W] */, int rows, int W,
+                           const int32_t *d_index /* [h_offsets[groups]] row numbers, or NULL = identity */,
+                           const int32_t *h_offsets /* HOST [groups + 1], ascending */, int groups,
+                           float *d_out /* [groups, 8] */);
 /* Image preprocessing in front of capdec_clip_encode_image: the `preprocess` transform clip.load returns
  * (reference predictions_runner.py:212, embeddings_generator.py:72) = Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
  * ToTensor -> Normalize(mean, std); stretch != 0 = clip_transform_full (predictions_runner.py:116-122): Resize((n_px,
