@@ -13,6 +13,7 @@
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   nearest.hip       capdec_nearest_tokens: nearest table rows by cosine similarity (the normalised-wte cache, row blocks)
 //   gap_stats.hip     capdec_embed_moments, capdec_group_distances: modality offset and paraphrase spread, fp64 sums
+//   bridger.hip       capdec_bridger_*: the supervised modality bridger (an MLP trained with MSE and SGD with momentum), fp32
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
 //                     forward share (tlayer_self_front / tlayer_tail)
 //   train_*.hip       the train step (train.h): step, mapping networks, shared backward pieces, optimizer + C entry points
@@ -125,6 +126,22 @@ struct ResNet {
     std::vector<void *> owned;
 };
 
+// The supervised modality bridger (bridger.hip): L Linear layers in nn.Linear layout with ReLU between them, the momentum
+// buffers of torch.optim.SGD, the activations the last train step saved, and the loss scalars.
+constexpr int BRIDGER_MAX_LAYERS = 16, BRIDGER_MAX_WIDTH = 1024, BRIDGER_MAX_BATCH = 64;
+struct BridgerScalars { float last; int pad; double sum; long long steps; double eval_sum; long long eval_batches; };
+struct Bridger {
+    bool loaded = false;
+    int L = 0, dims[BRIDGER_MAX_LAYERS + 1] = {0};
+    float *w[BRIDGER_MAX_LAYERS] = {nullptr}, *b[BRIDGER_MAX_LAYERS] = {nullptr};       // W_l [dims[l+1], dims[l]], b_l [dims[l+1]]
+    float *vw[BRIDGER_MAX_LAYERS] = {nullptr}, *vb[BRIDGER_MAX_LAYERS] = {nullptr};     // their momentum buffers (0 at load)
+    float *act[BRIDGER_MAX_LAYERS] = {nullptr};      // [BRIDGER_MAX_BATCH, dims[l+1]]: post-activation of the last train step
+    float *dy[2] = {nullptr, nullptr};               // [BRIDGER_MAX_BATCH, widest]: the gradient flowing down, two in turn
+    BridgerScalars *scal = nullptr;                  // device
+    int last_batch = 0;                              // rows of the last train step (0: none since the load)
+    std::vector<void *> owned;
+};
+
 enum Family { F_GEMM = 0, F_LMHEAD, F_ATTN_DEC, F_ATTN_PRE, F_LN, F_EMBED, F_SELECT, F_MAP_ATTN, F_OTHER, F_GEMM_X3,
               F_LMHEAD_X3, F_GEMM_X3P, F_GEMM_BF16P, F_LMHEAD_BF16, F_GEMM_H2P, F_LMHEAD_H2, F_PACK, F_LMHEAD_2ND, F_NEAREST, F_CONTRAST, F_GUIDED, F_COUNT };
 extern const char *const kFamilyNames[F_COUNT];
@@ -199,6 +216,8 @@ struct capdec_ctx {
     bool wte_n_valid = false;              // [vocab, d] -- built on first use, its operand planes cached by planes_of like a weight's;
                                            // dropped with the wte it was made from (drop_wte_norm)
     DBuf n_tab, n_bad;                     // ... a caller's table normalised for one call; [table flag | one flag per row of a block]
+    capdec::Bridger bridger;               // bridger.hip: at most one supervised modality bridger
+    DBuf br_f0, br_f1, br_ev;              // ... capdec_bridger_forward / _eval: activations of n rows, two in turn; a loss per batch
     DBuf gap_ws, gap_ws2, gap_off;         // gap_stats.hip: fp64 partial sums per slab and their folds; [flag | group offsets]
     capdec::LogitsProc proc;               // capdec_set_logits_processors (defaults: every processor off)
     int proc_bias_n = 0;                   // capdec_set_logit_bias: entries of `pbias` (0 = no bias)

@@ -810,6 +810,136 @@ class Engine:
                                                   out.data_ptr() if groups else None), "capdec_group_distances")
         return out
 
+    # ------------------------------------------------------------------ supervised modality bridger (bridger.hip)
+    BRIDGER_MAX_LAYERS, BRIDGER_MAX_WIDTH, BRIDGER_MAX_BATCH = 16, 1024, 64
+
+    def _bridger_dims(self, what: str) -> Tuple[int, ...]:
+        dims = getattr(self, "bridger", None)
+        if dims is None:
+            raise CapdecError(f"{what}: no bridger is loaded (bridger_load)")
+        return dims
+
+    def _bridger_rows(self, what: str, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> int:
+        dims = self._bridger_dims(what)
+        if x.dim() != 2 or int(x.shape[1]) != dims[0]:
+            raise CapdecError(f"{what}: x must be [n, {dims[0]}], got {tuple(x.shape)}")
+        if y is not None and tuple(y.shape) != (int(x.shape[0]), dims[-1]):
+            raise CapdecError(f"{what}: y must be [{int(x.shape[0])}, {dims[-1]}], got {tuple(y.shape)}")
+        return int(x.shape[0])
+
+    def _bridger_batch(self, what: str, batch) -> int:
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= self.BRIDGER_MAX_BATCH:
+            raise CapdecError(f"{what}: batch must be an integer in 1..{self.BRIDGER_MAX_BATCH}, got {batch!r}")
+        return int(batch)
+
+    def bridger_load(self, weights, biases):
+        """load the supervised modality bridger (capdec_bridger_load; the contract: include/capdec.h): ``weights[l]`` is
+        ``[dims[l + 1], dims[l]]`` (nn.Linear layout), ``biases[l]`` ``[dims[l + 1]]``; ReLU follows every layer but the last.
+        1 to 16 layers, every width a multiple of 4 in 4..1024.  The momentum buffers and the loss scalars start at zero."""
+        weights, biases = list(weights), list(biases)
+        L = len(weights)
+        if not 1 <= L <= self.BRIDGER_MAX_LAYERS or len(biases) != L:
+            raise CapdecError(f"bridger_load: 1 to {self.BRIDGER_MAX_LAYERS} layers, one bias per weight (got {L} weights, "
+                              f"{len(biases)} biases)")
+        if any(w.dim() != 2 for w in weights):
+            raise CapdecError("bridger_load: every weight must be [out, in]")
+        dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
+        for l, (w, b) in enumerate(zip(weights, biases)):
+            if int(w.shape[1]) != dims[l] or tuple(b.shape) != (dims[l + 1],):
+                raise CapdecError(f"bridger_load: layer {l} must be a [{dims[l + 1]}, {dims[l]}] weight with a [{dims[l + 1]}] "
+                                  f"bias, got {tuple(w.shape)} and {tuple(b.shape)}")
+        for d in dims:
+            if d % 4 or not 4 <= d <= self.BRIDGER_MAX_WIDTH:
+                raise CapdecError(f"bridger_load: every width must be a multiple of 4 in 4..{self.BRIDGER_MAX_WIDTH}, got {d}")
+        keep = [_f32(w) for w in weights] + [_f32(b) for b in biases]
+        ptr = lambda ts: (_capi.c_float_p * L)(*[t.ctypes.data_as(_capi.c_float_p) for t in ts])      # noqa: E731
+        self.bridger = None
+        self._chk(self.lib.capdec_bridger_load(self._h, L, (C.c_int32 * (L + 1))(*dims), ptr(keep[:L]), ptr(keep[L:])),
+                  "capdec_bridger_load")
+        self.bridger = tuple(dims)
+
+    def bridger_forward(self, x: torch.Tensor) -> torch.Tensor:
+        """the bridger applied to ``x`` [n, dims[0]] -> fp32 [n, dims[L]] on the device; a row's result does not depend on n"""
+        n = self._bridger_rows("bridger_forward", x)
+        xs = self._dev(x)
+        out = torch.empty(n, self.bridger[-1], device=self.device, dtype=torch.float32)
+        if n:
+            self._sync_stream()
+            self._chk(self.lib.capdec_bridger_forward(self._h, xs.data_ptr(), n, out.data_ptr()), "capdec_bridger_forward")
+        return out
+
+    def bridger_train_step(self, x: torch.Tensor, y: torch.Tensor, lr: float = 0.001, momentum: float = 0.9,
+                           return_loss: bool = True) -> Optional[float]:
+        """one step of MSELoss + SGD with momentum on the batch (x [batch, dims[0]], y [batch, dims[L]], batch 1..64) ->
+        the step's loss; ``return_loss=False`` only enqueues (read :meth:`bridger_loss` later)"""
+        n = self._bridger_rows("bridger_train_step", x, y)
+        self._bridger_batch("bridger_train_step", n)
+        xs, ys = self._dev(x), self._dev(y)
+        loss = C.c_float(0.0)
+        self._sync_stream()
+        self._chk(self.lib.capdec_bridger_train_step(self._h, xs.data_ptr(), ys.data_ptr(), n, float(lr), float(momentum),
+                                                     C.byref(loss) if return_loss else None), "capdec_bridger_train_step")
+        if not return_loss:
+            self._bridger_keep = (xs, ys)                # the enqueued kernels still read them
+            return None
+        return float(loss.value)
+
+    def bridger_train_epoch(self, x: torch.Tensor, y: torch.Tensor, batch: int = 32, lr: float = 0.001, momentum: float = 0.9):
+        """one pass over the rows in consecutive batches of ``batch`` (the last may be short), every step enqueued from C;
+        the epoch's loss is ``sum / steps`` of :meth:`bridger_loss`"""
+        n = self._bridger_rows("bridger_train_epoch", x, y)
+        batch = self._bridger_batch("bridger_train_epoch", batch)
+        if n == 0:
+            return
+        xs, ys = self._dev(x), self._dev(y)
+        self._sync_stream()
+        self._chk(self.lib.capdec_bridger_train_epoch(self._h, xs.data_ptr(), ys.data_ptr(), n, batch, float(lr), float(momentum)),
+                  "capdec_bridger_train_epoch")
+        self._bridger_keep = (xs, ys)                    # the enqueued kernels still read them
+
+    def bridger_eval(self, x: torch.Tensor, y: torch.Tensor, batch: int = 32) -> Tuple[float, int]:
+        """(sum of the MSE losses of the consecutive batches of ``batch`` rows, number of batches) without an update"""
+        n = self._bridger_rows("bridger_eval", x, y)
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise CapdecError(f"bridger_eval: batch must be an integer >= 1, got {batch!r}")
+        total, count = C.c_double(0.0), C.c_longlong(0)
+        if n:
+            xs, ys = self._dev(x), self._dev(y)
+            self._sync_stream()
+            self._chk(self.lib.capdec_bridger_eval(self._h, xs.data_ptr(), ys.data_ptr(), n, int(batch), C.byref(total),
+                                                   C.byref(count)), "capdec_bridger_eval")
+        return float(total.value), int(count.value)
+
+    def bridger_loss(self, reset: bool = False) -> Tuple[float, float, int]:
+        """(loss of the last step, fp64 sum of the steps' losses since the load or the last reset, number of those steps)"""
+        self._bridger_dims("bridger_loss")
+        last, total, n = C.c_float(0.0), C.c_double(0.0), C.c_longlong(0)
+        self._chk(self.lib.capdec_bridger_loss(self._h, C.byref(last), C.byref(total), C.byref(n), int(bool(reset))),
+                  "capdec_bridger_loss")
+        return float(last.value), float(total.value), int(n.value)
+
+    def bridger_get(self, kind: int, which: int, batch: Optional[int] = None) -> torch.Tensor:
+        """kind 0: parameter ``which`` (2 l = weight of layer l, 2 l + 1 = its bias); kind 1: its momentum buffer; kind 2:
+        activation ``which`` of the last train step, [batch, dims[which + 1]] (post-ReLU for hidden layers, L - 1 = the
+        output) -- ``batch`` is that step's row count"""
+        dims = self._bridger_dims("bridger_get")
+        L = len(dims) - 1
+        if kind in (0, 1):
+            if not 0 <= which < 2 * L:
+                raise CapdecError(f"bridger_get: which must be in [0, {2 * L}), got {which}")
+            l = which // 2
+            shape = (dims[l + 1], dims[l]) if which % 2 == 0 else (dims[l + 1],)
+        elif kind == 2:
+            if not 0 <= which < L:
+                raise CapdecError(f"bridger_get: activation must be in [0, {L}), got {which}")
+            shape = (self._bridger_batch("bridger_get", batch), dims[which + 1])
+        else:
+            raise CapdecError(f"bridger_get: kind must be 0 (parameter), 1 (momentum buffer) or 2 (activation), got {kind!r}")
+        out = torch.empty(*shape, device=self.device, dtype=torch.float32)
+        self._sync_stream()
+        self._chk(self.lib.capdec_bridger_get(self._h, int(kind), int(which), out.data_ptr(), out.numel()), "capdec_bridger_get")
+        return out
+
     # ------------------------------------------------------------------ caption-shard communicator (RCCL through the C ABI)
     def comm_unique_id(self) -> bytes:
         """rank 0: the 128-byte communicator id every rank passes to :meth:`comm_init`"""

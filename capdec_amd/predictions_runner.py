@@ -70,11 +70,15 @@ def _given(**kw) -> Dict:
 
 
 def prefix_from_embeddings(model: ClipCaptionModel, embeddings: torch.Tensor, dont_normalize_prefix: bool = False,
-                           modality_offset: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """reference :221-228 for a batch: ``prefix / prefix.norm(2,-1)``; ``+ offset``;
+                           modality_offset: Optional[torch.Tensor] = None, *, modality_bridger=None) -> torch.Tensor:
+    """reference :221-228 for a batch: ``prefix / prefix.norm(2,-1)``; ``+ offset``; with ``modality_bridger`` (the callable
+    of ``supervised_embedding_bridger.get_map_to_text_space_using_modality_bridger`` or its ``MLP``; --modality_bridger)
+    ``prefix = modality_bridger(prefix)``, NOT normalised again (:227 computes the quotient and drops it);
     ``clip_project(prefix).reshape(N, P, -1)``."""
     eng = model.engine
     x = eng.normalize_prefix(embeddings, normalize=not dont_normalize_prefix, offset=modality_offset)
+    if modality_bridger is not None:
+        x = modality_bridger(x)
     return model.clip_project(x).reshape(x.shape[0], model.prefix_length, -1)
 
 
@@ -82,14 +86,15 @@ def caption_ids(model: ClipCaptionModel, embeddings: torch.Tensor, stop_token_in
                 beam_size: int = 5, entry_length: int = 67, dont_normalize_prefix: bool = False,
                 modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1, *,
                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                min_length: Optional[int] = None, logit_bias=None):
+                min_length: Optional[int] = None, logit_bias=None, modality_bridger=None):
     """The whole device-side path for this rank's shard of ``embeddings`` [N, D].
     Returns (ids [n_local, T] int32 of the best caption, lens [n_local]) and, for beam, the
     mean-log-prob score of the best beam.  The keyword-only logits processors (None: ``model.logits_processors``'s) are
     those of ``decode_beam_ids`` / ``decode_greedy_ids``."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     lo, hi = cdist.shard_bounds(embeddings.shape[0], rank, world)
-    pe = prefix_from_embeddings(model, embeddings[lo:hi], dont_normalize_prefix, modality_offset)
+    pe = prefix_from_embeddings(model, embeddings[lo:hi], dont_normalize_prefix, modality_offset,
+                                **_given(modality_bridger=modality_bridger))
     if beam:
         ids, lens, scores, _ = decode_beam_ids(model, pe, stop_token_index, beam_size, entry_length, **pk)
         return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
@@ -102,11 +107,13 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
                dont_normalize_prefix: bool = False, modality_offset: Optional[torch.Tensor] = None,
                rank: int = 0, world: int = 1, timer: Optional[Timer] = None, *,
                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-               min_length: Optional[int] = None, logit_bias=None) -> List[Dict]:
-    """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  Writes the
+               min_length: Optional[int] = None, logit_bias=None, modality_bridger=None) -> List[Dict]:
+    """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  ``modality_bridger`` (--modality_bridger): see
+    ``prefix_from_embeddings``.  Writes the
     reference's predictions JSON (``[{"caption": lower-cased text, "image_id": id}]``, :260-261,
     :301) -- the whole list, not only every 99th flush."""
-    pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias,
+                modality_bridger=modality_bridger)
     cdist.check_world(rank, world)
     if len(data) != embeddings.shape[0]:
         raise ValueError(f"make_preds: {len(data)} data entries but {embeddings.shape[0]} embeddings")
@@ -136,7 +143,7 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
                            entry_length: int = 67, dont_normalize_prefix: bool = False,
                            modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
                            image_batch: int = 256, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                           min_length: Optional[int] = None, logit_bias=None) -> List[Dict]:
+                           min_length: Optional[int] = None, logit_bias=None, modality_bridger=None) -> List[Dict]:
     """The image half of the reference loop in front of ``make_preds`` (:156-161, :207-220): ``images[i]`` is what
     ``Image.open(filename).convert("RGB")`` gave for ``data[i]`` (a PIL image or a uint8 [H, W, 3] array), or ``None``
     for a file the reference would skip (:207-210: the entry is left out of the output).  ``preprocess`` and
@@ -165,7 +172,8 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
     T = entry_length
     if feats:
         ids, lens, _ = caption_ids(model, torch.cat(feats), stop, beam, 5, T, dont_normalize_prefix, modality_offset,
-                                   **_given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias))
+                                   **_given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias,
+                                            modality_bridger=modality_bridger))
     else:                              # an empty shard (more ranks than images) still takes part in the gather
         dev = next(model.parameters()).device
         ids, lens = torch.zeros(0, T, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)

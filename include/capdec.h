@@ -609,6 +609,49 @@ int capdec_group_distances(capdec_ctx *ctx, const float *d_x /* [rows, W] */, in
                            const int32_t *d_index /* [h_offsets[groups]] row numbers, or NULL = identity */,
                            const int32_t *h_offsets /* HOST [groups + 1], ascending */, int groups,
                            float *d_out /* [groups, 8] */);
+/* ---- supervised modality bridger ------------------------------------------------------- */
+/* Reference others/supervised_embedding_bridger.py: an MLP that maps an image embedding to its caption's text embedding,
+ * trained with nn.MSELoss and torch.optim.SGD(momentum) on pairs, applied between the normalisation / offset and clip_project
+ * (predictions_runner.py --modality_bridger).  A context owns at most one bridger: L Linear layers in nn.Linear layout,
+ * W_l [dims[l + 1], dims[l]] and b_l [dims[l + 1]], ReLU after every layer but the last.  capdec_bridger_load copies the
+ * host tensors, zeroes the momentum buffers and the loss scalars, and replaces a bridger loaded before.
+ *   - Limits, each refused with capdec_last_error and the context left usable: 1 <= L <= 16; every width a multiple of 4 in
+ *     4..1024; train batch 1..64; every call but the load needs a loaded bridger.  Device pointers are 16-byte aligned,
+ *     and d_out does not overlap d_x.
+ *   - Arithmetic is fp32 with fp32 accumulation.  An output of a layer is four chains of FMAs over the layer's inputs (by
+ *     index mod 4, each in index order), added in a fixed order, whatever n is and wherever the row sits: capdec_bridger_forward, _train_step and _eval give a row the same
+ *     bits.  No floating-point atomics anywhere: the same call from the same state gives the same bits.
+ *   - NaN / inf in the inputs propagate as IEEE arithmetic propagates them; there is no guard (torch has none).
+ * capdec_bridger_forward: d_out = MLP(d_x) for n rows (n == 0 succeeds and touches nothing); synchronises.
+ * capdec_bridger_train_step: the reference's loop body (:144-153) -- forward, MSELoss over the batch * dims[L] outputs (the
+ *   squared differences summed in fp64 in a fixed order, the loss rounded to fp32), backward, and the update of
+ *   torch.optim.SGD with dampening 0, no Nesterov, no weight decay: v = momentum * v + g, p -= lr * v (v is 0 after a load:
+ *   torch's buf = grad on the first step).  The ReLU derivative is h > 0 on the saved post-activation (0 at 0, as torch).
+ *   The weight gradient is never stored: after the first step from a load the momentum buffer IS the gradient, afterwards
+ *   g_k = v_k - momentum * v_(k-1).  lr == 0 is legal (the weights stay, v moves).  loss == NULL only enqueues; otherwise
+ *   the call waits and returns the step's loss.  2 L + 1 launches.
+ * capdec_bridger_train_epoch: the unshuffled, not-drop_last DataLoader over n device-resident rows -- consecutive slices of
+ *   `batch` rows, the last one possibly short -- enqueued without a host round trip; bit for bit that sequence of
+ *   capdec_bridger_train_step calls.  It does not wait for the device.
+ * capdec_bridger_loss: like capdec_train_loss -- the last step's loss, the fp64 sum of the steps' fp32 losses and their
+ *   number since the load or the last reset (the epoch's train_loss is sum / steps); waits for the device.
+ * capdec_bridger_eval: the validation loop (:165-177) -- the forward over all n rows, MSELoss per consecutive slice of
+ *   `batch` >= 1 rows (the last possibly short), the fp64 sum of those fp32 losses in order and their count; synchronises.
+ * capdec_bridger_get copies to d_out (device, n floats, which must be the tensor's size): kind 0 a parameter, kind 1 its
+ *   momentum buffer (which = 2 l the weight, 2 l + 1 the bias); kind 2 activation `which` of the last train step,
+ *   [batch, dims[which + 1]], post-ReLU for hidden layers, which = L - 1 the output.
+ * (Added without a new ABI number, like capdec_nearest_tokens.) */
+int capdec_bridger_load(capdec_ctx *ctx, int num_layers, const int *h_dims /* HOST [L + 1] */,
+                        const float *const *h_w /* HOST [L] pointers to host tensors */, const float *const *h_b);
+int capdec_bridger_forward(capdec_ctx *ctx, const float *d_x /* [n, dims[0]] */, int n, float *d_out /* [n, dims[L]] */);
+int capdec_bridger_train_step(capdec_ctx *ctx, const float *d_x /* [batch, dims[0]] */, const float *d_y /* [batch, dims[L]] */,
+                              int batch, float lr, float momentum, float *loss /* host, or NULL */);
+int capdec_bridger_train_epoch(capdec_ctx *ctx, const float *d_x /* [n, dims[0]] */, const float *d_y /* [n, dims[L]] */, int n,
+                               int batch, float lr, float momentum);
+int capdec_bridger_eval(capdec_ctx *ctx, const float *d_x, const float *d_y, int n, int batch, double *loss_sum,
+                        long long *batches);
+int capdec_bridger_loss(capdec_ctx *ctx, float *last, double *sum, long long *steps, int reset);
+int capdec_bridger_get(capdec_ctx *ctx, int kind, int which, float *d_out, size_t n);
 /* Image preprocessing in front of capdec_clip_encode_image: the `preprocess` transform clip.load returns
  * (reference predictions_runner.py:212, embeddings_generator.py:72) = Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
  * ToTensor -> Normalize(mean, std); stretch != 0 = clip_transform_full (predictions_runner.py:116-122): Resize((n_px,
