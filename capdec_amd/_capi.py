@@ -122,6 +122,7 @@ SIGNATURES = {
     "capdec_train_get": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),
     "capdec_train_reset": (C.c_int, [_VP]),
     "capdec_train_set_scope": (C.c_int, [_VP, C.c_int]),
+    "capdec_train_set_encdec": (C.c_int, [_VP, C.c_int]),
     "capdec_train_loss": (C.c_int, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
     "capdec_train_set_dropout": (C.c_int, [_VP, C.c_float, C.c_uint64]),
     "capdec_train_set_dropout_masks": (C.c_int, [_VP, _VP, C.c_size_t]),

@@ -78,7 +78,7 @@ struct TMapLayer {
     bool fused = false;
 };
 struct Mapper {
-    int kind = 0;   // 0 none, 1 mlp, 2 transformer, 3 transformer encoder-decoder (inference only)
+    int kind = 0;   // 0 none, 1 mlp, 2 transformer, 3 transformer encoder-decoder (trained only after capdec_train_set_encdec)
     int D = 0, P = 0, d = 768;
     // mlp
     int hidden = 0;
@@ -205,6 +205,7 @@ struct capdec_ctx {
                                      // the chosen candidate's residual row by caption and by compact activation row [captions, d]
     capdec::TrainState *train = nullptr;     // created by the first capdec_train_step, freed by train_release
     int train_scope = 0;                     // capdec_train_set_scope: survives capdec_train_reset and weight reloads
+    int train_encdec = 0;                    // capdec_train_set_encdec: the encoder-decoder mapper trains (off: it is refused); survives like the scope
     float train_drop_p = 0.f;                // capdec_train_set_dropout: GPT-2's dropout probability in scope 1 (0 = off)
     unsigned long long train_drop_seed = 0;  // ... key of the Philox keep-mask stream (counter = element, train step)
     DBuf slogits;          // sampling decode, logits processors: fp32 logits of one row block, [min(rows, tune.sample_rows), ld]

@@ -10,8 +10,9 @@
 // the factor 1 / (count LS) is applied where a gradient is consumed (AdamW, capdec_train_get): the GEMM operands then sit
 // in the range where the two-fp16-plane format is fp32-accurate, whatever the number of scored labels.
 //
-// Both mapping networks: the MLP (gpt2_prefix.py:114-126) and the TransformerMapper (transformer_mapper.py:113-127: every
-// one of its 3 + 12 n_layers tensors).  Structure: the forward keeps every activation the backward needs
+// All three mapping networks: the MLP (gpt2_prefix.py:114-126), the TransformerMapper (transformer_mapper.py:113-127: every
+// one of its 3 + 12 n_layers tensors) and -- once capdec_train_set_encdec asks for it -- the encoder-decoder mapper
+// (:130-145: 3 + 36 n_layers tensors).  Structure: the forward keeps every activation the backward needs
 // (fp32, per layer: block input, qkv, attention output, mid-block residual, c_fc pre-activation: 30 KB per token and
 // layer -- 1.2 GB for the reference's default batch of 34 captions x (40 + ~20) positions x 12 layers); the backward is
 // dX-only through GPT-2 (its weights are frozen: no weight gradients, no optimizer state for 124 M parameters) on the
@@ -25,7 +26,7 @@
 // Translation units (round 6: one 1500-line file until then):
 //   train_step.hip    the step itself -- GPT-2 forward with saved activations, loss, backward -- with the kernels only it uses
 //                     (GELU, the dropouts, embedding / loss-row maps, cross-entropy); capdec_train_step
-//   train_mapper.hip  both mapping networks: forward with saved activations (the TransformerMapper's layers run the shared
+//   train_mapper.hip  the mapping networks: forward with saved activations (the TransformerMapper's layers run the shared
 //                     layer forward of mapper.hip, context.h: tlayer_self_front / tlayer_tail), backward
 //   train_ops.hip     what the two share: LayerNorm / attention backward, the block-form attention, transposes, column sums,
 //                     the dX / dW products
@@ -65,6 +66,17 @@ template <int HD> struct AttnBlk {
 };
 // the block kernels when a head's tiles fit the CU's LDS (S <= 128), the per-query wavefront kernels otherwise
 constexpr size_t ATTN_BLK_LDS_MAX = 150 * 1024;
+// rectangular form (the encoder-decoder mapper: Sq queries against Sk keys of another tensor): K / V tiles [Sk][LD] that
+// Q / dO [Sq][LD] replace in phase 2, P and dS [Sq][Sk + 1], per wavefront a query, a dO row and a score row.  No
+// wavefront fallback: a shape fits when Sq, Sk <= ATTN_RECT_MAX_S and bwd_bytes <= ATTN_BLK_LDS_MAX
+constexpr int ATTN_RECT_MAX_S = 128;
+template <int HD> struct AttnRect {
+    static constexpr int LD = HD + 1;
+    static size_t bwd_bytes(int Sq, int Sk) {
+        return ((size_t)2 * std::max(Sq, Sk) * LD + (size_t)2 * Sq * (Sk + 1) + ATTN_BLK_NW * (2 * HD + Sk)) * sizeof(float);
+    }
+    static bool fits(int Sq, int Sk) { return Sq <= ATTN_RECT_MAX_S && Sk <= ATTN_RECT_MAX_S && bwd_bytes(Sq, Sk) <= ATTN_BLK_LDS_MAX; }
+};
 
 // ---------------------------------------------------------------------------------------------- workspace
 // One trainable tensor: where it lives and where its gradient / AdamW moments sit in the three arenas (same offset in each)
@@ -77,6 +89,13 @@ struct Slot {
 enum TMapSlot { TM_LIN_W = 0, TM_LIN_B, TM_PREFIX_CONST, TM_LAYER0 };
 enum TLayerSlot { TL_N1W = 0, TL_N1B, TL_WQ, TL_WKV, TL_WPROJ, TL_BPROJ, TL_N2W, TL_N2B, TL_WFC1, TL_BFC1, TL_WFC2, TL_BFC2, TL_COUNT };
 inline int tlayer_slot(int layer, TLayerSlot s) { return TM_LAYER0 + TL_COUNT * layer + s; }
+// The encoder-decoder mapper's slots, in the key order of the reference module's state_dict(): prefix_const, TL_COUNT per
+// ref_encoder layer (L of them), TL_COUNT per prefix_decoder layer (2 L), linear.weight, linear.bias
+constexpr int ED_PREFIX_CONST = 0;
+inline int ed_enc_slot(int layer, TLayerSlot s) { return 1 + TL_COUNT * layer + s; }
+inline int ed_dec_slot(int L, int layer, TLayerSlot s) { return 1 + TL_COUNT * (L + layer) + s; }
+inline int ed_lin_w_slot(int L) { return 1 + TL_COUNT * 3 * L; }
+inline int ed_lin_b_slot(int L) { return 2 + TL_COUNT * 3 * L; }
 
 struct TrainState {
     // transposed copies of the frozen GPT-2 weights: the "[N, K]" operand of dX = dY W^T (= the checkpoint's own Conv1D
@@ -106,6 +125,12 @@ struct TrainState {
     DBuf hid, dhid;                          // MLP mapper: tanh output, its gradient
     DBuf t_lin, t_seq, t_a1, t_qkv, t_att, t_mid, t_a2, t_r;      // TransformerMapper: per-layer saved activations
     DBuf t_ds, t_ds2, t_da, t_dr, t_dqkv, t_datt, t_dlin;         // ... gradient scratch
+    // encoder-decoder mapper: its encoder keeps the TransformerMapper's buffers (at width enc_dim); per decoder layer the
+    // block input, norm1 output, queries, attention output, mid residual, norm2 output, relu(fc1); keys | values of the self
+    // layers; the stacked keys | values of the cross layers [B C, L 2d] -- and the gradients of the last two, of `ref`
+    DBuf d_seq, d_a1, d_q, d_att, d_mid, d_a2, d_r, d_kv, d_kvc;
+    DBuf d_dkv, d_dkvc, d_dref;
+    size_t ed_cross_off = 0;                 // arena offset of the stacked cross to_keys_values gradient [L 2d, enc_dim]
     long long step = 0;                      // train steps run with apply_update (the mask stream's counter; the AdamW
                                              // update counter lives on the device: StepScalars::updates)
     bool have_grads = false;
@@ -121,7 +146,7 @@ struct TrainState {
                         &dh, &dh2, &da, &dqkv, &datt, &dfc, &dhfl, &lse, &dsum, &dy, &tA, &tB, &wT, &lnstat, &hid, &dhid,
                         &dmask, &dinj, &ytmp, &dtmp,
                         &t_lin, &t_seq, &t_a1, &t_qkv, &t_att, &t_mid, &t_a2, &t_r, &t_ds, &t_ds2, &t_da, &t_dr, &t_dqkv,
-                        &t_datt, &t_dlin};
+                        &t_datt, &t_dlin, &d_seq, &d_a1, &d_q, &d_att, &d_mid, &d_a2, &d_r, &d_kv, &d_kvc, &d_dkv, &d_dkvc, &d_dref};
         for (DBuf *b : bufs) b->release();
         step = 0;
         have_grads = false;
@@ -142,9 +167,11 @@ int transpose_pad(capdec_ctx *c, const float *src, int rows, int cols, float *ds
 int gemm_fp32(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, float *C, int ldc, int M, int N, int K,
               bool static_weight = false);
 int ln_bwd(capdec_ctx *c, const float *x, const float *w, const float *dy, const float *add, float *dx, int rows, int d, float eps,
-           float *gw = nullptr, float *gb = nullptr);
+           float *gw = nullptr, float *gb = nullptr, bool ordered = false);
 int linear_dx(capdec_ctx *c, TrainState &t, const float *dy, const float *W, float *dx, int M, int out, int in);
-int linear_dw(capdec_ctx *c, TrainState &t, const float *dy, const float *x, int rows, int out, int in, float *gW, float *gb);
+// ordered: the bias / LayerNorm-parameter sums run in one fixed order (one block walks every row), not as atomic partial sums
+int linear_dw(capdec_ctx *c, TrainState &t, const float *dy, const float *x, int rows, int out, int in, float *gW, float *gb,
+              bool ordered = false);
 // attention of the step's sequences on fused qkv activations [B S, 3 d]; (hd, causal) = (96, false): the TransformerMapper,
 // (64, true): GPT-2.  mask: GPT-2's attn_dropout keep bytes [B, H, S, S] (nullptr: none), inv_keep = 1 / (1 - p).
 // The block-per-(sample, head) kernels when a head's tiles fit the CU's LDS (and CAPDEC_TRAIN_ATTN_BLK allows), the
@@ -153,10 +180,17 @@ int train_attn_fwd(capdec_ctx *c, const float *qkv, float *out, int B, int S, in
                    const uint8_t *mask, float inv_keep);
 int train_attn_bwd(capdec_ctx *c, TrainState &t, const float *qkv, const float *dout, float *dqkv, int B, int S, int heads, int hd,
                    bool causal, float scale, const uint8_t *mask, float inv_keep);
+// rectangular attention backward (no mask, no dropout; hd 96: the decoder, 64: the encoder): caption b's Sq query rows at
+// q + b Sq ldq, its Sk key / value rows at k / v + b Sk ldkv, head h at columns h hd; dout [B Sq, heads hd]; dq / dk / dv laid
+// out like q / k / v at their own pointers and strides.  The caller has checked AttnRect<hd>::fits(Sq, Sk)
+int train_attn_rect_bwd(capdec_ctx *c, const float *q, int ldq, const float *k, const float *v, int ldkv, const float *dout,
+                        float *dq, int lddq, float *dk, float *dv, int lddkv, int B, int Sq, int Sk, int heads, int hd, float scale);
 
 // ---- train_mapper.hip
 int mapper_forward_saved(capdec_ctx *c, TrainState &t, const float *x, int B, float *pe);
 int mapper_backward(capdec_ctx *c, TrainState &t, const float *x, const float *dy, int B);
+// the encoder-decoder mapper's three attention shapes against the LDS rule above: refused before the first launch
+int encdec_train_fits(capdec_ctx *c);
 
 // ---- train_optim.hip
 int build_slots(capdec_ctx *c, TrainState &t);

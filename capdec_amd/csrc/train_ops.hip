@@ -57,12 +57,13 @@ __global__ void transpose_pad_kernel(const float *__restrict__ src, int rows, in
     }
 }
 // out[j] += sum over rows of x[r][j]: block (x, y) sums rows [64 y, 64 y + 64) of 256 columns and adds its partial sum
-// atomically (`out` is zeroed by the caller: the gradient arena is cleared once per step)
+// atomically (`out` is zeroed by the caller: the gradient arena is cleared once per step).  rpb = rows per block: COLSUM_ROWS,
+// or all of them -- one add per column, so the sum has a fixed order (the encoder-decoder mapper's gradients repeat bit for bit)
 constexpr int COLSUM_ROWS = 64;
-__global__ void colsum_kernel(const float *__restrict__ x, int rows, int n, float *__restrict__ out) {
+__global__ void colsum_kernel(const float *__restrict__ x, int rows, int n, float *__restrict__ out, int rpb) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    const int r0 = blockIdx.y * COLSUM_ROWS, r1 = min(rows, r0 + COLSUM_ROWS);
+    const int r0 = blockIdx.y * rpb, r1 = min(rows, r0 + rpb);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     int r = r0;
     for (; r + 3 < r1; r += 4) {
@@ -112,13 +113,14 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_kernel(const float *__restrict_
     if (stats && lane == 0) stats[row] = make_float2(mu, rstd);
 }
 // the LayerNorm's own gradients: gw[c] += sum_r dy[r, c] (x[r, c] - mean_r) rstd_r, gb[c] += sum_r dy[r, c].  Block (x, y):
-// 64 columns x rows [128 y, 128 y + 128), four row lanes per column reduced through LDS, one atomic add per column
+// 64 columns x rows [rpb y, rpb y + rpb) (rpb = 128, or every row: a fixed summation order), four row lanes per column reduced
+// through LDS, one atomic add per column
 __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float *__restrict__ x, const float *__restrict__ dy,
                                                             const float2 *__restrict__ stats, int rows, int d,
-                                                            float *__restrict__ gw, float *__restrict__ gb) {
+                                                            float *__restrict__ gw, float *__restrict__ gb, int rpb) {
     __shared__ float sw[4][64], sb[4][64];
     const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
-    const int r0 = blockIdx.y * 128, r1 = min(rows, r0 + 128);
+    const int r0 = blockIdx.y * rpb, r1 = min(rows, r0 + rpb);
     float a = 0.f, b = 0.f;
     if (c < d)
         for (int r = r0 + rl; r < r1; r += 4) {
@@ -481,7 +483,113 @@ __global__ __launch_bounds__(64 * ATTN_BLK_NW) void attn_blk_bwd_kernel(const fl
             }
     }
 }
+// Rectangular backward (the encoder-decoder mapper): Sq queries of one tensor against Sk keys / values of another, every
+// operand and result at a pointer and row stride of its own -- the cross layers' keys and values are column blocks of the
+// stacked [B C, L 2d] buffer.  No mask, no dropout, no atomics: each dq / dk / dv element is one thread's sum in loop order.
+// LDS: A, Bm [max(Sq, Sk)][LD], P, dS [Sq][Sk + 1], [NW][HD] x 2, [NW][Sk]  (AttnRect<HD>::bwd_bytes);  Sk <= 128
+template <int HD>
+__global__ __launch_bounds__(64 * ATTN_BLK_NW) void attn_rect_bwd_kernel(const float *__restrict__ q, int ldq, const float *__restrict__ k,
+                                                                        const float *__restrict__ v, int ldkv,
+                                                                        const float *__restrict__ dout, float *__restrict__ dq, int lddq,
+                                                                        float *__restrict__ dk, float *__restrict__ dv, int lddkv,
+                                                                        int Sq, int Sk, int heads, float scale) {
+    constexpr int LD = HD + 1, NE = (HD + 63) / 64, NW = ATTN_BLK_NW;
+    extern __shared__ float sh[];
+    const int SP = Sk + 1, SM = Sq > Sk ? Sq : Sk;
+    float *A = sh, *Bm = A + SM * LD, *P = Bm + SM * LD, *dS = P + Sq * SP, *qb = dS + Sq * SP, *gb = qb + NW * HD,
+          *sb = gb + NW * HD;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bh = blockIdx.x, h = bh % heads, b = bh / heads, d = heads * HD;
+    const float *qbase = q + (size_t)b * Sq * ldq + h * HD, *kbase = k + (size_t)b * Sk * ldkv + h * HD,
+                *vbase = v + (size_t)b * Sk * ldkv + h * HD, *gbase = dout + (size_t)b * Sq * d + h * HD;
+    attn_blk_stage<HD>(A, kbase, ldkv, Sk);                         // K
+    attn_blk_stage<HD>(Bm, vbase, ldkv, Sk);                        // V
+    __syncthreads();
+    float *qw = qb + wave * HD, *g = gb + wave * HD, *ds = sb + wave * Sk;
+    // ---- phase 1: one query per wavefront pass
+    for (int i = wave; i < Sq; i += NW) {
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            if (lane + 64 * e < HD) {
+                qw[lane + 64 * e] = qbase[(size_t)i * ldq + lane + 64 * e] * scale;
+                g[lane + 64 * e] = gbase[(size_t)i * d + lane + 64 * e];
+            }
+        ATTN_WAVE_SYNC()
+        float sc[2], dp[2], mx = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int j = lane + 64 * r;
+            float a = -INFINITY, t = 0.f;
+            if (j < Sk) {
+                a = dot_lds<HD>(qw, A + j * LD);
+                t = dot_lds<HD>(g, Bm + j * LD);
+            }
+            sc[r] = a;
+            dp[r] = t;
+            mx = fmaxf(mx, sc[r]);
+        }
+        mx = wave_max(mx);
+        float l = 0.f;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) { sc[r] = lane + 64 * r < Sk ? expf(sc[r] - mx) : 0.f; l += sc[r]; }
+        const float inv = 1.0f / wave_sum(l);
+        float D = 0.f;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) { sc[r] *= inv; D += sc[r] * dp[r]; }
+        D = wave_sum(D);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int j = lane + 64 * r;
+            if (j < Sk) {
+                const float w = sc[r] * (dp[r] - D);
+                ds[j] = w;
+                dS[i * SP + j] = w;
+                P[i * SP + j] = sc[r];
+            }
+        }
+        ATTN_WAVE_SYNC()
+        float acc[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) acc[e] = 0.f;
+        wsum_rows<HD>(ds, 1, A, 0, Sk, lane, acc);
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            if (lane + 64 * e < HD) dq[((size_t)b * Sq + i) * lddq + h * HD + lane + 64 * e] = acc[e] * scale;
+    }
+    __syncthreads();
+    // ---- phase 2: Q and dO take the place of K and V; one key per wavefront pass
+    attn_blk_stage<HD>(A, qbase, ldq, Sq);                          // Q
+    attn_blk_stage<HD>(Bm, gbase, d, Sq);                           // dO
+    __syncthreads();
+    for (int j = wave; j < Sk; j += NW) {
+        float ak[NE], av[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) ak[e] = av[e] = 0.f;
+        wsum_rows<HD>(dS + j, SP, A, 0, Sq, lane, ak);              // column j of dS against the rows of Q
+        wsum_rows<HD>(P + j, SP, Bm, 0, Sq, lane, av);              // column j of P against the rows of dO
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            if (lane + 64 * e < HD) {
+                dk[((size_t)b * Sk + j) * lddkv + h * HD + lane + 64 * e] = ak[e] * scale;
+                dv[((size_t)b * Sk + j) * lddkv + h * HD + lane + 64 * e] = av[e];
+            }
+    }
+}
 #undef ATTN_WAVE_SYNC
+template <int HD>
+static int attn_rect_bwd(hipStream_t st, const float *q, int ldq, const float *k, const float *v, int ldkv, const float *dout, float *dq,
+                         int lddq, float *dk, float *dv, int lddkv, int B, int Sq, int Sk, int heads, float scale) {
+    static bool attr = false;
+    if (!attr) {
+        CAPDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_rect_bwd_kernel<HD>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_BLK_LDS_MAX));
+        attr = true;
+    }
+    hipLaunchKernelGGL((attn_rect_bwd_kernel<HD>), dim3(B * heads), dim3(64 * ATTN_BLK_NW), AttnRect<HD>::bwd_bytes(Sq, Sk), st, q, ldq, k, v,
+                       ldkv, dout, dq, lddq, dk, dv, lddkv, Sq, Sk, heads, scale);
+    CAPDEC_HIP(hipGetLastError());
+    return 0;
+}
 template <int HD, bool CAUSAL>
 static int attn_blk_fwd(hipStream_t st, const float *qkv, float *out, int B, int S, int heads, float scale, const uint8_t *mask,
                         float inv_keep) {
@@ -533,17 +641,22 @@ int gemm_fp32(capdec_ctx *c, const float *A, int lda, const float *Bt, int ldb, 
 }
 
 int ln_bwd(capdec_ctx *c, const float *x, const float *w, const float *dy, const float *add, float *dx, int rows,
-                  int d, float eps, float *gw, float *gb) {
-    CAPDEC_CHECK(d == 768, "train: LayerNorm backward is instantiated for d = 768");
+                  int d, float eps, float *gw, float *gb, bool ordered) {
+    CAPDEC_CHECK(d == 768 || d == 512, "train: LayerNorm backward is instantiated for d = 768 and d = 512");
     float2 *stats = nullptr;
     if (gw) {
         CAPDEC_TRY(c->train->lnstat.ensure((size_t)rows * sizeof(float2)));
         stats = c->train->lnstat.as<float2>();
     }
-    hipLaunchKernelGGL(ln_bwd_dx_kernel<12>, dim3((rows + 3) / 4), dim3(256), 0, c->stream, x, w, dy, add, dx, rows, eps, stats);
-    if (gw)
-        hipLaunchKernelGGL(ln_param_grad_kernel, dim3((d + 63) / 64, (rows + 127) / 128), dim3(256), 0, c->stream, x, dy, stats, rows,
-                           d, gw, gb);
+    if (d == 768)
+        hipLaunchKernelGGL(ln_bwd_dx_kernel<12>, dim3((rows + 3) / 4), dim3(256), 0, c->stream, x, w, dy, add, dx, rows, eps, stats);
+    else
+        hipLaunchKernelGGL(ln_bwd_dx_kernel<8>, dim3((rows + 3) / 4), dim3(256), 0, c->stream, x, w, dy, add, dx, rows, eps, stats);
+    if (gw) {
+        const int rpb = ordered ? rows : 128;
+        hipLaunchKernelGGL(ln_param_grad_kernel, dim3((d + 63) / 64, (rows + rpb - 1) / rpb), dim3(256), 0, c->stream, x, dy, stats, rows,
+                           d, gw, gb, rpb);
+    }
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -555,7 +668,7 @@ int linear_dx(capdec_ctx *c, TrainState &t, const float *dy, const float *W, flo
 }
 // dW = dY^T X ([out, in]; dY [rows, out], X [rows, in]; the GEMM's K = rows, zero-padded to a multiple of 32), db = colsum(dY)
 int linear_dw(capdec_ctx *c, TrainState &t, const float *dy, const float *x, int rows, int out, int in, float *gW,
-                     float *gb) {
+                     float *gb, bool ordered) {
     if (c->tune.train_f16x2 && in % 4 == 0) {
         // both operands packed transposed from their row-major form: no fp32 transposed copies (a "TN" operand loader)
         CAPDEC_TRY(gemm_tn(c, dy, out, x, in, rows, out, in, gW, in));
@@ -567,9 +680,10 @@ int linear_dw(capdec_ctx *c, TrainState &t, const float *dy, const float *x, int
         CAPDEC_TRY(transpose_pad(c, x, rows, in, t.tB.as<float>(), Kp));
         CAPDEC_TRY(gemm_fp32(c, t.tA.as<float>(), Kp, t.tB.as<float>(), Kp, gW, in, out, in, Kp));
     }
-    if (gb)
-        hipLaunchKernelGGL(colsum_kernel, dim3((out + 255) / 256, (rows + COLSUM_ROWS - 1) / COLSUM_ROWS), dim3(256), 0, c->stream,
-                           dy, rows, out, gb);
+    if (gb) {
+        const int rpb = ordered ? rows : COLSUM_ROWS;
+        hipLaunchKernelGGL(colsum_kernel, dim3((out + 255) / 256, (rows + rpb - 1) / rpb), dim3(256), 0, c->stream, dy, rows, out, gb, rpb);
+    }
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -616,6 +730,15 @@ int train_attn_bwd(capdec_ctx *c, TrainState &t, const float *qkv, const float *
                        t.dsum.as<float>(), nbh, S, heads, scale, mask, inv_keep);
     CAPDEC_HIP(hipGetLastError());
     return 0;
+}
+
+int train_attn_rect_bwd(capdec_ctx *c, const float *q, int ldq, const float *k, const float *v, int ldkv, const float *dout,
+                        float *dq, int lddq, float *dk, float *dv, int lddkv, int B, int Sq, int Sk, int heads, int hd, float scale) {
+    CAPDEC_CHECK(hd == 96 || hd == 64, "train: the rectangular attention backward is instantiated for heads of 96 and of 64");
+    CAPDEC_CHECK(Sq >= 1 && Sk >= 1 && (hd == 96 ? AttnRect<96>::fits(Sq, Sk) : AttnRect<64>::fits(Sq, Sk)),
+                 "train: rectangular attention backward beyond its LDS rule");
+    if (hd == 96) return attn_rect_bwd<96>(c->stream, q, ldq, k, v, ldkv, dout, dq, lddq, dk, dv, lddkv, B, Sq, Sk, heads, scale);
+    return attn_rect_bwd<64>(c->stream, q, ldq, k, v, ldkv, dout, dq, lddq, dk, dv, lddkv, B, Sq, Sk, heads, scale);
 }
 
 }  // namespace capdec

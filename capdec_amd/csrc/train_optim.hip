@@ -54,7 +54,10 @@ void train_release(capdec_ctx *c) {
 
 // Slot order (capdec.h: capdec_train_get).  MLP: model.0.weight, model.0.bias, model.2.weight, model.2.bias.
 // TransformerMapper: TMapSlot, then TLayerSlot per layer (train.h); to_queries and to_keys_values are the adjacent halves of
-// the fused [3d, d] projection on the device, so TL_WQ's gradient is also where the fused matrix's begins
+// the fused [3d, d] projection on the device, so TL_WQ's gradient is also where the fused matrix's begins.
+// Encoder-decoder mapper: the reference module's state_dict() order (train.h: ed_*_slot) -- its encoder layers are fused in
+// the same way; a cross layer's to_keys_values is its rows of Mapper::wkv_cross, and the L of them keep that adjacency in the
+// arenas (TrainState::ed_cross_off), so one product with the stacked d (keys | values) fills all their gradients
 int build_slots(capdec_ctx *c, TrainState &t) {
     if (!t.slots.empty()) return 0;
     Mapper &m = c->map;
@@ -71,6 +74,21 @@ int build_slots(capdec_ctx *c, TrainState &t) {
     if (m.kind == 1) {
         const size_t O = (size_t)m.P * d;
         add(m.w1, (size_t)m.hidden * m.D); add(m.b1, m.hidden); add(m.w2, O * m.hidden); add(m.b2, O);
+    } else if (m.kind == 3) {
+        const size_t E = m.enc_dim, L = m.n_layers;
+        t.ed_cross_off = 0;
+        t.n_params = L * 2 * d * E;               // the stacked cross to_keys_values come first in the arenas
+        add(m.prefix_const, (size_t)m.P * d);
+        auto add_layer = [&](TMapLayer &l, size_t w, size_t hid, size_t ref, long cross) {
+            add(l.n1w, w); add(l.n1b, w); add(l.wq, w * w);
+            if (cross >= 0) t.slots.push_back(Slot{l.wkv, 2 * w * ref, t.ed_cross_off + (size_t)cross * 2 * w * ref});
+            else add(l.wkv, 2 * w * ref);
+            add(l.wproj, w * w); add(l.bproj, w); add(l.n2w, w); add(l.n2b, w);
+            add(l.wfc1, hid * w); add(l.bfc1, hid); add(l.wfc2, w * hid); add(l.bfc2, w);
+        };
+        for (TMapLayer &l : m.layers) add_layer(l, E, m.enc_hidden, E, -1);
+        for (size_t i = 0; i < m.dec.size(); ++i) add_layer(m.dec[i], d, m.mlp_hidden, i % 2 == 0 ? E : d, i % 2 == 0 ? (long)(i / 2) : -1);
+        add(m.lin_w, (size_t)m.clip_len * E * m.D); add(m.lin_b, (size_t)m.clip_len * E);
     } else {
         const size_t hid = m.mlp_hidden;
         struct { float *p; size_t n; } head[TM_LAYER0], s[TL_COUNT];
@@ -179,6 +197,7 @@ int train_apply_update(capdec_ctx *c, TrainState &t, float lr, float b1, float b
                        t.G.as<float>(), t.Mo.as<float>(), t.Vo.as<float>(), sc, b1, b2, eps, lr * weight_decay);
     CAPDEC_HIP(hipGetLastError());
     t.step += 1;
+    if (c->map.kind == 3) drop_planes_of(c, c->map.wkv_cross);       // (the stacked GEMM's operand: also the first cross layer's slot)
     for (const Slot &sl : t.slots) {
         drop_planes_of(c, sl.p);      // inference must never see planes packed from old values
         if (sl.p == c->gpt.wte) drop_wte_norm(c);      // ... nor capdec_nearest_tokens the unit rows of the old wte
@@ -200,8 +219,8 @@ extern "C" {
 
 int capdec_train_get(capdec_ctx *c, int kind, int which, float *d_out, size_t n) {
     CAPDEC_CHECK(c && d_out, "train_get: null argument");
-    CAPDEC_CHECK(c->map.kind != 3, "train_get: the encoder-decoder mapper is inference-only");
-    CAPDEC_CHECK(c->gpt.loaded && (c->map.kind == 1 || c->map.kind == 2), "train_get: needs GPT-2 weights and a mapper");
+    CAPDEC_CHECK(c->map.kind != 3 || c->train_encdec, "train_get: the encoder-decoder mapper is inference-only");
+    CAPDEC_CHECK(c->gpt.loaded && c->map.kind >= 1 && c->map.kind <= 3, "train_get: needs GPT-2 weights and a mapper");
     CAPDEC_CHECK(kind == 0 || kind == 1, "train_get: kind must be 0 (parameter) or 1 (gradient)");
     CAPDEC_HIP(hipSetDevice(c->device));
     TrainState &t = train_state(c);
@@ -230,6 +249,13 @@ int capdec_train_set_scope(capdec_ctx *c, int train_gpt) {
     if (c->train_scope == train_gpt && (!c->train || c->train->train_gpt == (train_gpt != 0))) return 0;
     c->train_scope = train_gpt;             // (kept by capdec_train_reset and by weight reloads)
     train_release(c);                       // another parameter set: new slots, fresh optimizer state
+    return 0;
+}
+
+int capdec_train_set_encdec(capdec_ctx *c, int on) {
+    CAPDEC_CHECK(c, "null context");
+    CAPDEC_CHECK(on == 0 || on == 1, "train_set_encdec: 0 (the encoder-decoder mapper is refused) or 1 (it trains)");
+    c->train_encdec = on;                   // (kept by capdec_train_reset and by weight reloads, like the scope)
     return 0;
 }
 

@@ -208,12 +208,13 @@ static int train_step(capdec_ctx *c, const float *prefix, const int *tokens, int
                       float eps, float weight_decay, int apply_update, float *loss_host) {
     const Gpt2 &g = c->gpt;
     Mapper &m = c->map;
-    CAPDEC_CHECK(m.kind != 3, "train_step: the encoder-decoder mapper is inference-only");
-    CAPDEC_CHECK(g.loaded && (m.kind == 1 || m.kind == 2), "train_step: needs GPT-2 weights and a mapper");
+    CAPDEC_CHECK(m.kind != 3 || c->train_encdec, "train_step: the encoder-decoder mapper is inference-only");
+    CAPDEC_CHECK(g.loaded && m.kind >= 1 && m.kind <= 3, "train_step: needs GPT-2 weights and a mapper");
     CAPDEC_CHECK(g.d == 768 && g.d / g.n_head == 64 && m.d == g.d, "train_step: d = 768, head_dim = 64");
     const int d = g.d, P = m.P, S = P + L, R = B * S, Rl = B * L, O = P * d, D = m.D;
     CAPDEC_CHECK(B >= 1 && L >= 1 && S <= 256 && S <= g.n_pos, "train_step: bad batch geometry (prefix_length + L <= 256)");
     CAPDEC_CHECK(D % 32 == 0 && O % 32 == 0, "train_step: mapper dims must be multiples of 32");
+    if (m.kind == 3) CAPDEC_TRY(encdec_train_fits(c));
     if (!c->train) { c->train = new TrainState(); c->train->train_gpt = c->train_scope != 0; }
     TrainState &t = *c->train;
     CAPDEC_TRY(prepare_backward_weights(c, t));

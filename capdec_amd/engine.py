@@ -1053,6 +1053,12 @@ class Engine:
         """the mapper's trainable tensors in the order capdec_train_get indexes them (names as in ``clip_project.state_dict()``)"""
         if mapping == "mlp":
             return ["model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias"]
+        if mapping == "transformer_decoder":      # the key order of the reference module's state_dict()
+            names = ["prefix_const"]
+            for stack, count in (("ref_encoder", num_layers), ("prefix_decoder", 2 * num_layers)):
+                for i in range(count):
+                    names += [f"{stack}.layers.{i}.{key}" for key in _capi.TMAPPER_LAYER_KEYS]
+            return names + ["linear.weight", "linear.bias"]
         names = ["linear.weight", "linear.bias", "prefix_const"]
         for i in range(num_layers):
             names += [f"transformer.layers.{i}.{key}" for key in _capi.TMAPPER_LAYER_KEYS]
@@ -1138,6 +1144,11 @@ class Engine:
         """False: the mapper only, GPT-2 frozen and in eval mode (--only_prefix); True: GPT-2 as well (the reference's
         default run; dropout per train_set_dropout)"""
         self._chk(self.lib.capdec_train_set_scope(self._h, int(bool(train_gpt))), "train_set_scope")
+
+    def train_set_encdec(self, on: bool):
+        """True: the encoder-decoder mapper trains (capdec_train_set_encdec); False, the default: train_step refuses it.  A
+        context setting like the scope; without effect on the other two mappers"""
+        self._chk(self.lib.capdec_train_set_encdec(self._h, int(bool(on))), "train_set_encdec")
 
     def train_reset(self):
         """a fresh optimizer: drops the AdamW moments and the step count (scope and dropout setting stay)"""

@@ -7,7 +7,8 @@ Same names, constructor arguments and attribute surface (``.clip_project``, ``.g
 forward pass of the reference's train step (:145-155; train.py:251-260) -- logits and loss, inference
 only: backward and the optimiser are outside this path.
 All three mapping types run: ``MappingType.TransformerDecoder`` builds ``transformer_mapper.TransformerEncoderDecoder``
-(:169-171), for inference (``capdec_amd.train.train_step`` refuses it).
+(:169-171); ``capdec_amd.train.train_step`` refuses it until ``model.clip_project.requires_grad_()`` asks for its training.
+``train`` (:219-261) is the reference's own loop for all three mapping types.
 """
 from __future__ import annotations
 
@@ -187,7 +188,7 @@ class ClipCaptionModel(_HipModule):
         elif mapping_type == MappingType.MLP:
             self.clip_project = MLP((prefix_dim, (self.gpt_embedding_size * prefix_length) // 2,
                                      self.gpt_embedding_size * prefix_length), _owner=self)
-        else:       # MappingType.TransformerDecoder (reference gpt2_prefix.py:169-171); inference only
+        else:       # MappingType.TransformerDecoder (reference gpt2_prefix.py:169-171); trained after requires_grad_()
             self.clip_project = transformer_mapper.TransformerEncoderDecoder(prefix_dim, self.gpt_embedding_size,
                                                                              prefix_length, clip_length, num_layers,
                                                                              _owner=self)
@@ -216,10 +217,10 @@ class ClipCaptionModel(_HipModule):
 
     def _mapper_shapes(self):
         """ordered {name: shape} of the mapper's trainable tensors, in the device's slot order"""
-        if self.mapping_type == MappingType.TransformerDecoder:
+        if self.mapping_type == MappingType.TransformerDecoder and not self.clip_project._requires_grad:
             raise CapdecError("train_step: the encoder-decoder mapper is inference-only")
-        mlp = self.mapping_type == MappingType.MLP
-        names = Engine.train_tensor_names("mlp" if mlp else "transformer", self.num_layers)
+        kind = {MappingType.MLP: "mlp", MappingType.TransformerDecoder: "transformer_decoder"}.get(self.mapping_type, "transformer")
+        names = Engine.train_tensor_names(kind, self.num_layers)
         sd = self.clip_project._sd
         missing = [n for n in names if n not in sd]
         if missing or len(names) != len(sd):
@@ -267,6 +268,8 @@ class ClipCaptionModel(_HipModule):
             raise CapdecError("ClipCaptionModel has no weights: call load_state_dict(checkpoint) first")
         eng.load_gpt2(self._sd, "gpt.", n_head=self.gpt_dims.n_head, ln_eps=self.gpt_dims.ln_eps)
         self.clip_project._upload(eng)
+        if self.mapping_type == MappingType.TransformerDecoder:
+            eng.train_set_encdec(self.clip_project._requires_grad)
 
     def forward(self, tokens, prefix, mask=None, labels=None):
         """The forward pass of the reference's TRAIN step (train.py:251-260,348; gpt2_prefix.py:145-155), inference only
@@ -338,3 +341,42 @@ class _Gpt2Facade:
         if inputs_embeds is None or kw.get("labels") is not None:
             raise CapdecError("model.gpt(...) supports inference on inputs_embeds only")
         return SimpleNamespace(logits=self._owner.engine.gpt2_logits(inputs_embeds, all_positions=True))
+
+
+def train(dataset, model: ClipCaptionModel, batch_size: int, epochs: int, lr: float = 2e-5, warmup_steps: int = 5000,
+          output_dir: str = ".", output_prefix: str = "", save_model_on_epoch: bool = True, args=None):
+    """reference gpt2_prefix.py:219-261, for any of the three mapping types: no noise injection, ``dataset`` items
+    ``(tokens, mask, prefix, *rest)``; after every epoch ``model.state_dict()`` goes to ``{output_prefix}-{epoch:03d}.pt``
+    when ``epoch % args.save_every == 0`` or the epoch is the last, to ``{output_prefix}_latest.pt`` otherwise.  Calling it
+    is the request to train: an encoder-decoder mapper's ``requires_grad_()`` is turned on here.  The steps of an epoch are
+    enqueued without waiting for the device, as in ``capdec_amd.train.train``."""
+    import os
+    import sys
+    from torch.utils.data import DataLoader
+    from . import train as TR
+    os.makedirs(output_dir, exist_ok=True)
+    model = model.to(TR.device)
+    model.train()
+    if model.mapping_type == MappingType.TransformerDecoder:
+        model.clip_project.requires_grad_(True)
+    optimizer = TR.AdamW(model.parameters(), lr=lr)
+    loader = DataLoader(dataset, batch_size=batch_size, shuffle=True, drop_last=True)
+    scheduler = TR.get_linear_schedule_with_warmup(optimizer, num_warmup_steps=warmup_steps,
+                                                   num_training_steps=epochs * len(loader))
+    for epoch in range(epochs):
+        print(f">>> Training epoch {epoch}")
+        sys.stdout.flush()
+        model.engine.train_loss(reset=True)
+        for tokens, mask, prefix, *_ in loader:
+            TR.train_step(model, optimizer, tokens, mask, prefix.to(TR.device, dtype=torch.float32), wait=False)
+            scheduler.step()
+        _, total, counted = model.engine.train_loss()
+        if counted != len(loader):
+            raise IndexError(f"train: {len(loader) - counted} batch(es) of epoch {epoch} held a token id out of range (the "
+                             "reference's embedding lookup raises on the first of them); no weight was updated by those steps")
+        print(f"loss: {total / max(1, len(loader)):.6f}")
+        if epoch % args.save_every == 0 or epoch == epochs - 1:
+            torch.save(model.state_dict(), os.path.join(output_dir, f"{output_prefix}-{epoch:03d}.pt"))
+        else:
+            torch.save(model.state_dict(), os.path.join(output_dir, f"{output_prefix}_latest.pt"))
+    return model

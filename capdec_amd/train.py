@@ -128,7 +128,8 @@ def train_step(model: ClipCaptionModel, optimizer: AdamW, tokens: torch.Tensor, 
     from a Philox stream seeded from torch's global seed -- or from ``dropout_masks`` (uint8, 1 = keep: every site of the
     step concatenated in call order, include/capdec.h), the hook the parity test uses.  ``wait=False`` enqueues the step
     and returns None (``model.engine.train_loss()`` reads losses later)."""
-    if model.mapping_type == MappingType.TransformerDecoder:
+    encdec = model.mapping_type == MappingType.TransformerDecoder
+    if encdec and not model.clip_project._requires_grad:      # (off by default: clip_project.requires_grad_() turns it on)
         raise CapdecError("train_step: the encoder-decoder mapper is inference-only")
     full = not isinstance(model, ClipCaptionPrefix)      # a plain ClipCaptionModel trains GPT-2 too (reference train.py:306-308)
     if model._train_gpt != full:
@@ -136,6 +137,8 @@ def train_step(model: ClipCaptionModel, optimizer: AdamW, tokens: torch.Tensor, 
         model._train_gpt = full
     eng = model.engine
     eng.train_set_scope(full)
+    if encdec:
+        eng.train_set_encdec(True)
     p_drop = float(model.gpt.config.resid_pdrop) if (full and model.training) else 0.0
     # (the probability and the Philox key live in the HIP CONTEXT and a new context starts at p = 0: what was last set is
     #  remembered on the Engine object, so a model that moved to another device / build sets its dropouts up again)

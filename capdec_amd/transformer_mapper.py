@@ -1,5 +1,5 @@
 """Drop-in surface of reference ``transformer_mapper.py``: ``TransformerMapper`` (:113-127) and
-``TransformerEncoderDecoder`` (:130-145, MappingType.TransformerDecoder; inference only).
+``TransformerEncoderDecoder`` (:130-145, MappingType.TransformerDecoder; trained once ``requires_grad_()`` asks for it).
 The layer stack (Mlp :4-19, MultiHeadAttention :22-51, TransformerLayer :54-73, Transformer
 :76-110) runs as HIP kernels inside ``capdec_mapper_forward``."""
 from __future__ import annotations
@@ -76,6 +76,17 @@ class TransformerEncoderDecoder(_TransformerMapperBase):
     def __init__(self, dim_clip: int, dim_embedding: int, prefix_length: int, clip_length: int, num_layers: int = 4,
                  _owner: Optional[_HipModule] = None):
         super().__init__(dim_clip, dim_embedding, prefix_length, clip_length, num_layers, _owner)
+        self._requires_grad = False
+
+    def requires_grad_(self, flag: bool = True):
+        """torch's own name: ask for (or give up) the training of this mapper.  Off by default -- a model that was merely
+        built and loaded is refused by ``train.train_step``; ``gpt2_prefix.train`` turns it on itself"""
+        if not flag and self._requires_grad and self._owner is not None:
+            self._owner._pull_mapper()          # weights that only the device holds are read back while the switch is on
+        self._requires_grad = bool(flag)
+        if self._owner is not None and self._owner._engine is not None:
+            self._owner._engine.train_set_encdec(self._requires_grad)
+        return self
 
     def _keys(self):
         """the reference class's ``state_dict()`` keys, in its order"""

@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define CAPDEC_ABI_VERSION 6   /* 6: capdec_load_mapper_encdec (MappingType.TransformerDecoder, inference only);
+#define CAPDEC_ABI_VERSION 6   /* 6: capdec_load_mapper_encdec (MappingType.TransformerDecoder; inference only until
+                                     capdec_train_set_encdec, added without a new number, turns its training on);
                                      (capdec_decode_sample was added WITHOUT a new number: the addition changes no existing
                                      symbol, and a library built from older sources is refused through capdec_build_id)
                                   5: capdec_set_compact, capdec_decode_step_rows (the workload in which captions stop);
@@ -165,8 +166,9 @@ struct capdec_edmapper_weights {
                                                 ones (self: keys from the residual stream, which norm1 does NOT touch) */
 };
 
-/* TransformerEncoderDecoder: reference transformer_mapper.py:130-145 (MappingType.TransformerDecoder).  Inference only:
- * capdec_mapper_forward and everything built on it serve it; capdec_train_step refuses it. */
+/* TransformerEncoderDecoder: reference transformer_mapper.py:130-145 (MappingType.TransformerDecoder).  Inference only by
+ * default: capdec_mapper_forward and everything built on it serve it; capdec_train_step refuses it until
+ * capdec_train_set_encdec(ctx, 1) asks for its training. */
 int capdec_load_mapper_encdec(capdec_ctx *ctx, const capdec_edmapper_weights *h_w);
 
 /* ---- prefix stage -------------------------------------------------------------------- */
@@ -291,7 +293,21 @@ int capdec_gpt2_logits(capdec_ctx *ctx, const float *d_embeds, int n, int L, int
  * norm2.weight, .bias, mlp.fc1.weight, .bias, mlp.fc2.weight, .bias.  Scope 1 continues with wte (the tied lm_head), wpe,
  * per layer ln_1.weight, ln_1.bias, attn.c_attn.weight, .bias, attn.c_proj.weight, .bias, ln_2.weight, .bias,
  * mlp.c_fc.weight, .bias, mlp.c_proj.weight, .bias, then ln_f.weight, ln_f.bias; Conv1D weights (and their gradients)
- * are returned in the checkpoint's [in, out] layout. */
+ * are returned in the checkpoint's [in, out] layout.
+ *
+ * The encoder-decoder mapper (capdec_load_mapper_encdec) trains only after capdec_train_set_encdec(ctx, 1): a context
+ * setting like the scope -- off at capdec_create, kept by capdec_train_reset and by mapper loads, without effect on the
+ * other two mappers.  While off, capdec_train_step and capdec_train_get refuse that mapper ("... is inference-only").  Its
+ * 3 + 36 num_layers tensors come in the key order of the reference module's state_dict(): prefix_const; per ref_encoder
+ * layer the twelve tensors listed above (at width enc_dim); per prefix_decoder layer (2 num_layers of them) the same twelve,
+ * attn.to_keys_values.weight being [2d, enc_dim] in the even (cross) layers and [2d, d] in the odd (self) ones; then
+ * linear.weight, linear.bias.  Its attention backward keeps one head's tiles in LDS and has no fallback: with Sq queries
+ * and Sk keys of heads hd wide it needs Sq, Sk <= 128 and
+ *     (2 max(Sq, Sk) (hd + 1) + 2 Sq (Sk + 1) + 16 (2 hd + Sk)) * 4 <= 153600 bytes
+ * for the encoder (clip_length x clip_length, hd = enc_dim / heads = 64), the cross layers (prefix_length x clip_length,
+ * hd = 96) and the self layers (prefix_length x prefix_length, hd = 96: at most 90 x 90); a geometry beyond that is refused
+ * before the first launch and the context goes on working.  d must be 768 and enc_dim 512. */
+int capdec_train_set_encdec(capdec_ctx *ctx, int on);
 int capdec_train_step(capdec_ctx *ctx, const float *d_prefix, const int32_t *d_tokens, int batch, int length, float lr,
                       float beta1, float beta2, float eps, float weight_decay, int apply_update, float *loss);
 int capdec_train_get(capdec_ctx *ctx, int kind, int which, float *d_out, size_t n);
