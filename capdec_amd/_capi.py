@@ -169,6 +169,8 @@ SIGNATURES = {
                                      _VP, _VP]),
     "capdec_decode_beam_groups": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float,
                                             _VP, _VP, _VP, _VP, _VP]),
+    "capdec_decode_beam_constrained": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                 _VP, _VP, _VP, _VP, _VP]),
     "capdec_decode_contrastive": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                             _VP, _VP, _VP]),
     "capdec_decode_guided": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,

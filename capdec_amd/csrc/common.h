@@ -420,6 +420,32 @@ int launch_group_beam_step(hipStream_t st, const BeamState &s, const float *lse,
                            int vocab, int stop_id, const int *cmap = nullptr);
 // logp_out[cap, rank] = s.logp[cap, order[cap, rank]]: the unpenalised sums in the order launch_beam_finalize returned
 int launch_group_beam_logp(hipStream_t st, const BeamState &s, int ncap, int beam, const int *order, float *logp_out);
+// constrained.hip: lexically constrained beam search by dynamic beam allocation (capdec_decode_beam_constrained; the
+// contract: include/capdec.h).  phrases [ncap, 4, 4] (unused places -1), state [ncap, beam]: a slot's (met, cur, pos) packed
+// into one int (0: nothing met, nothing in progress), permuted with the rest of the BeamState.
+struct ConstraintState {
+    const int *phrases = nullptr;   // [ncap, CON_PHRASES, CON_LEN]
+    int *state = nullptr;           // [ncap, beam]
+};
+constexpr int CON_PHRASES = 4, CON_LEN = 4, CON_SPECIAL = CON_PHRASES + 1, CON_BEAM_MAX = 8;
+constexpr int CON_LIST = CON_SPECIAL + CON_BEAM_MAX;     // a row's list: the special tokens' places, then its best `beam` others
+// logsumexp and the list of every row of materialised logits [rows, ld], one pass: lse [rows]; top_val / top_idx
+// [rows, CON_LIST] -- places 0..4 the row's special tokens (top_idx -1: unused), places 5..5+beam-1 its best `beam` tokens
+// outside them; the stop token counts as -inf while the row's phrases are not all met.  Logits row r is activation row
+// row0 + r and finds its caption and slot through cmap and beam as launch_logits_process finds its history (step 0: one
+// row per caption, the empty state).
+int launch_logits_select_forced(hipStream_t st, const float *logits, int ld, int rows, int row0, int V, int beam,
+                                float inv_temp, const ConstraintState &cs, const int *cmap, int step, int stop_id,
+                                float *lse, float *top_val, int *top_idx);
+int launch_constrained_beam_init(hipStream_t st, const BeamState &s, const ConstraintState &cs, const float *lse,
+                                 const float *top_val, const int *top_idx, int ncap, int beam, int T, int ctx, int vocab,
+                                 int stop_id);
+int launch_constrained_beam_step(hipStream_t st, const BeamState &s, const ConstraintState &cs, const float *lse,
+                                 const float *top_val, const int *top_idx, int ncap, int beam, int T, int ctx, int step,
+                                 int pos_new, int vocab, int stop_id, const int *cmap = nullptr);
+// launch_beam_finalize with the rows ordered by (phrases met, score / seq, slot); met [ncap, beam] (may be nullptr)
+int launch_constrained_finalize(hipStream_t st, const BeamState &s, const ConstraintState &cs, int ncap, int beam, int T,
+                                int *ids, int *lens, float *scores, int *order, int *met);
 // contrastive.hip: contrastive search (capdec_decode_contrastive; the contract: include/capdec.h).  K candidate rows per
 // caption in the beam layout (row = caption * K + c); hist [ncap, ctx, d] holds ln_f of every position of the chosen path,
 // L2-normalised.

@@ -201,6 +201,7 @@ struct capdec_ctx {
     DBuf h, x, qkv, att, ff, xl, tmax, tsum, cval, cidx, lse, topv, topi, kc, vc;
     DBuf tokens, scores, seq, stopped, done, anc, next_tok, alive, gids, glens, cmap, kvstat;
     DBuf glogp;            // diverse beam search (capdec_decode_beam_groups): the unpenalised log-prob sums [rows] (BeamState::logp)
+    DBuf cstate;           // constrained beam search (capdec_decode_beam_constrained): a slot's (met, cur, pos) [rows] (ConstraintState::state)
     DBuf cs_hist, cs_last, cs_sel;   // contrastive search (contrastive.hip): the L2-normalised ln_f history [captions, ctx, d],
                                      // the chosen candidate's residual row by caption and by compact activation row [captions, d]
     capdec::TrainState *train = nullptr;     // created by the first capdec_train_step, freed by train_release
@@ -396,6 +397,10 @@ struct DecodeCall {
     int groups = 0;
     float diversity = 0.f;
     float *glogp = nullptr;     // [n, beam] or nullptr: the unpenalised log-prob sums, in the returned order
+    // constrained beam search (capdec_decode_beam_constrained): `phrases` sends every step through the materialised logits and
+    // constrained.hip's selection and bookkeeping kernels
+    const int *phrases = nullptr;   // [n, 4, 4]
+    int *met = nullptr;         // [n, beam] or nullptr: the met masks, in the returned order
     int cap_off = 0;            // index of the chunk's first caption within the call: the Philox counter's caption offset, and
                                 // the offset of the chunk's slice of the per-call K/V-slot statistic (BeamState::kv_stat)
 };
@@ -428,6 +433,7 @@ struct DecodeState {
     GreedyState gs;
     const int *hist = nullptr;      // the rows' own histories, for the logits processors: ids (greedy) or bs.tokens
     uint8_t *anc = nullptr;         // bs.anc (nullptr: greedy)
+    ConstraintState cs;             // constrained beam search: the chunk's phrases and the slots' states
 };
 int decode_state(capdec_ctx *c, int nc, const DecodeCall &a, int halves, DecodeState *s);
 int decode_advance(capdec_ctx *c, const DecodeCall &a, const DecodeState &s, int R, int step, int k, const int *cmap);

@@ -303,6 +303,33 @@ int lm_head_rows(capdec_ctx *c, const float *h0, int ldh, int R, int k, float in
     return 0;
 }
 
+// lm_head_rows for the constrained beam search (constrained.hip), which always takes this route: per block of rows the
+// logits, with `proc` the processors in place, then the one-pass selection that bans the stop token while the row's phrases
+// are unmet and leaves the row's list -- its special tokens' places, then its best `beam` others -- CON_LIST entries per row
+// at the block's offset into c->lse / c->topv / c->topi.
+static int lm_head_rows_forced(capdec_ctx *c, const float *h0, int ldh, int R, float inv_temp, const DecodeCall &a,
+                               const DecodeState &s, bool proc, int step, const int *cmap) {
+    const int V = c->gpt.vocab, ld = pad64(V), blk = std::min(R, std::max(1, c->tune.sample_rows));
+    const float *bias = c->proc_bias_n > 0 ? c->pbias.as<float>() : nullptr;
+    CAPDEC_TRY(c->slogits.ensure((size_t)blk * ld * 4));
+    CAPDEC_TRY(c->lse.ensure((size_t)R * 4));
+    CAPDEC_TRY(c->topv.ensure((size_t)R * CON_LIST * 4));
+    CAPDEC_TRY(c->topi.ensure((size_t)R * CON_LIST * 4));
+    float *lg = c->slogits.as<float>();
+    for (int r0 = 0; r0 < R; r0 += blk) {
+        const int nr = std::min(blk, R - r0);
+        CAPDEC_TRY(lm_head_logits(c, h0 + (size_t)r0 * ldh, ldh, nr, lg, ld));
+        ProfScope ps(c, F_SELECT);
+        if (proc)
+            CAPDEC_TRY(launch_logits_process(c->stream, lg, ld, nr, r0, V, cmap, step == 0 ? 1 : a.beam, s.hist, a.T, step,
+                                             c->proc, bias, a.stop_id, a.alt_stop_id));
+        CAPDEC_TRY(launch_logits_select_forced(c->stream, lg, ld, nr, r0, V, a.beam, inv_temp, s.cs, cmap, step, a.stop_id,
+                                               c->lse.as<float>() + r0, c->topv.as<float>() + (size_t)r0 * CON_LIST,
+                                               c->topi.as<int>() + (size_t)r0 * CON_LIST));
+    }
+    return 0;
+}
+
 // geometry only (the CLIP towers attend straight from the qkv activations and never touch a cache)
 void kv_geometry(KvCache &kv, int rows, int ctx, int heads, int hd) {
     kv.rows = rows;
@@ -421,6 +448,8 @@ DecodeCall chunk_call(const DecodeCall &call, int c0) {
     if (a.u) a.u += (size_t)c0 * T;
     if (a.logp) a.logp += (size_t)c0 * T;
     if (a.glogp) a.glogp += (size_t)c0 * beam;
+    if (a.phrases) a.phrases += (size_t)c0 * CON_PHRASES * CON_LEN;
+    if (a.met) a.met += (size_t)c0 * beam;
     a.cap_off = c0;
     return a;
 }
@@ -457,6 +486,12 @@ int decode_state(capdec_ctx *c, int nc, const DecodeCall &a, int halves, DecodeS
             CAPDEC_TRY(c->glogp.ensure((size_t)rows * 4));
             bs.logp = c->glogp.as<float>();
         }
+        if (a.phrases) {            // the chunk's phrases by chunk-local caption, every slot in the empty state
+            CAPDEC_TRY(c->cstate.ensure((size_t)rows * 4));
+            s->cs.phrases = a.phrases;
+            s->cs.state = c->cstate.as<int>();
+            CAPDEC_HIP(hipMemsetAsync(s->cs.state, 0, (size_t)rows * 4, c->stream));
+        }
         // (distinct-K/V-slot statistic: this chunk's slice of the per-call array decode_call_begin zeroed; nothing is read
         //  back here -- capdec_decode_counters sums it when somebody asks)
         bs.kv_stat = c->kvstat.p ? c->kvstat.as<unsigned>() + (size_t)a.cap_off * 2 : nullptr;
@@ -491,6 +526,11 @@ int decode_advance(capdec_ctx *c, const DecodeCall &a, const DecodeState &s, int
     const float *lse = c->lse.as<float>(), *topv = c->topv.as<float>();
     const int *topi = c->topi.as<int>();
     if (a.greedy) return launch_greedy_step(c->stream, s.gs, topi, R, step, k, a.forced, topv, lse, a.stats);
+    if (a.phrases) {                // (the lists are lm_head_rows_forced's: CON_LIST places per row)
+        if (step == 0) return launch_constrained_beam_init(c->stream, s.bs, s.cs, lse, topv, topi, R, beam, T, ctx, V, a.stop_id);
+        return launch_constrained_beam_step(c->stream, s.bs, s.cs, lse, topv, topi, R / beam, beam, T, ctx, step, P + step - 1, V,
+                                            a.stop_id, cmap);
+    }
     if (a.groups > 0) {
         if (step == 0)
             return launch_group_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, a.groups, a.diversity, k, T, ctx, P, a.stop_id);
@@ -569,7 +609,8 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
     // kernel of the decode.  hbeam: rows per caption for the history lookup; cmap: the compaction in force.
     auto select_and_advance = [&](const float *h0, int ldh, int R, int step, int hbeam, const int *cmap) -> int {
         s.gs.cmap = cmap;
-        if (proc || a.sample) CAPDEC_TRY(lm_head_rows(c, h0, ldh, R, k, inv_temp, a, s.gs, proc, step, hbeam, s.hist));
+        if (a.phrases) CAPDEC_TRY(lm_head_rows_forced(c, h0, ldh, R, inv_temp, a, s, proc, step, cmap));
+        else if (proc || a.sample) CAPDEC_TRY(lm_head_rows(c, h0, ldh, R, k, inv_temp, a, s.gs, proc, step, hbeam, s.hist));
         else CAPDEC_TRY(lm_head_select(c, h0, ldh, R, k, inv_temp));
         if (a.sample) return 0;                         // (the sampling kernel has advanced the state)
         return decode_advance(c, a, s, R, step, k, cmap);
@@ -600,7 +641,8 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
     }));
     if (!a.greedy) {
         ProfScope ps(c, F_SELECT);
-        CAPDEC_TRY(launch_beam_finalize(c->stream, s.bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
+        if (a.phrases) CAPDEC_TRY(launch_constrained_finalize(c->stream, s.bs, s.cs, nc, beam, T, a.ids, a.lens, a.scores, a.order, a.met));
+        else CAPDEC_TRY(launch_beam_finalize(c->stream, s.bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
         if (a.glogp) CAPDEC_TRY(launch_group_beam_logp(c->stream, s.bs, nc, beam, a.order, a.glogp));
     }
     return 0;
@@ -736,6 +778,44 @@ int capdec_decode_beam_groups(capdec_ctx *c, const float *prefix, int n, int P, 
     const int rc = decode_common(c, prefix, n, a);
     own_order.release();
     return rc;
+}
+
+int capdec_decode_beam_constrained(capdec_ctx *c, const float *prefix, const int32_t *phrases, int n, int P, int beam,
+                                   int stop_id, int entry_length, float temperature, int32_t *ids, int32_t *lens,
+                                   float *scores, int32_t *order, int32_t *met) {
+    const char *who = "decode_beam_constrained: ";
+    CAPDEC_CHECK(beam >= 1 && beam <= 8, "decode_beam_constrained: beam size must be in 1..8");
+    CAPDEC_CHECK(c && (n == 0 || (prefix && phrases && ids && lens && scores)), "decode_beam_constrained: null argument");
+    CAPDEC_CHECK(c->gpt.loaded && c->gpt.vocab >= beam, "decode_beam_constrained: vocabulary smaller than the beam");
+    CAPDEC_CHECK(n >= 0, "decode_beam_constrained: bad sizes");
+    if (n > 0) {                    // the phrase tables are read on the host before anything is launched
+        CAPDEC_HIP(hipSetDevice(c->device));
+        std::vector<int32_t> ph((size_t)n * CON_PHRASES * CON_LEN);
+        CAPDEC_HIP(hipMemcpyAsync(ph.data(), phrases, ph.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        CAPDEC_HIP(hipStreamSynchronize(c->stream));
+        const int V = c->gpt.vocab;
+        for (int r = 0; r < n; ++r) {
+            bool empty_seen = false;
+            for (int p = 0; p < CON_PHRASES; ++p) {
+                const int32_t *w = ph.data() + ((size_t)r * CON_PHRASES + p) * CON_LEN;
+                const std::string at = " (caption " + std::to_string(r) + ", phrase " + std::to_string(p) + ")";
+                bool end_seen = false;
+                for (int q = 0; q < CON_LEN; ++q) {
+                    if (w[q] == -1) { end_seen = true; continue; }
+                    CAPDEC_CHECK(w[q] >= 0 && w[q] < V, who + std::string("a token id outside the vocabulary") + at);
+                    CAPDEC_CHECK(w[q] != stop_id, who + std::string("a phrase holds the stop token") + at);
+                    CAPDEC_CHECK(!end_seen, who + std::string("a hole in front of a used place") + at);
+                    CAPDEC_CHECK(!empty_seen, who + std::string("a hole in front of a used place: an empty phrase in front") + at);
+                }
+                if (w[0] == -1) empty_seen = true;
+            }
+        }
+    }
+    DecodeCall a;
+    a.P = P; a.beam = beam; a.greedy = false; a.stop_id = stop_id; a.T = entry_length; a.temperature = temperature;
+    a.ids = ids; a.lens = lens; a.scores = scores; a.order = order;
+    a.phrases = phrases; a.met = met;
+    return decode_common(c, prefix, n, a);
 }
 
 

@@ -62,6 +62,27 @@ class LogitsProcessors:
         return p if p.active else None
 
 
+MAX_PHRASES, MAX_PHRASE_TOKENS = 4, 4       # capdec_decode_beam_constrained's phrase table: [n, 4, 4]
+
+
+def pack_phrases(phrases_per_caption) -> np.ndarray:
+    """[[phrase, ...] per caption], a phrase a sequence of token ids -> the int32 [n, 4, 4] table of
+    capdec_decode_beam_constrained, unused places -1.  More than 4 phrases for a caption, an empty phrase or one of more
+    than 4 tokens is a CapdecError."""
+    rows = [list(phs) for phs in phrases_per_caption]
+    out = np.full((len(rows), MAX_PHRASES, MAX_PHRASE_TOKENS), -1, dtype=np.int32)
+    for r, phs in enumerate(rows):
+        if len(phs) > MAX_PHRASES:
+            raise CapdecError(f"constrained beam search: caption {r} has {len(phs)} phrases, at most {MAX_PHRASES} are supported")
+        for c, ph in enumerate(phs):
+            ph = [int(t) for t in ph]
+            if not 1 <= len(ph) <= MAX_PHRASE_TOKENS:
+                raise CapdecError(f"constrained beam search: phrase {c} of caption {r} has {len(ph)} tokens, 1..{MAX_PHRASE_TOKENS} "
+                                  f"are supported")
+            out[r, c, :len(ph)] = ph
+    return out
+
+
 class Engine:
     """One context per GPU / rank."""
 
@@ -594,6 +615,50 @@ class Engine:
                                                      lens.data_ptr(), scores.data_ptr(), order.data_ptr(), logp.data_ptr()),
                   "capdec_decode_beam_groups")
         return ids, lens, scores, order, logp
+
+    def decode_beam_constrained(self, prefix_embed: torch.Tensor, phrases, stop_id: int, beam_size: int = 5,
+                                entry_length: int = 67, temperature: float = 1.0, *,
+                                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                                min_length: Optional[int] = None, logit_bias=None):
+        """lexically constrained beam search (capdec_decode_beam_constrained): the beam decode in which every phrase of a
+        caption must occur as a contiguous token run (dynamic beam allocation; ``force_words_ids`` of
+        ``transformers.generate``).  ``phrases``: per caption a list of up to 4 phrases of 1..4 token ids (see
+        :func:`pack_phrases`), or an int32 array / tensor [n, 4, 4] with -1 in the unused places.  -> ids [n, beam, T], lens
+        [n, beam], scores [n, beam] (mean log-probs), order [n, beam] (the slot of each returned row) and met [n, beam] (the
+        bitmask of the phrases each returned row holds); rows sorted by phrases met, then score, descending.  No phrases
+        is :meth:`decode_beam` through materialised logits.  The keyword-only processors as in :meth:`decode_greedy`."""
+        if isinstance(beam_size, bool) or not isinstance(beam_size, (int, np.integer)) or not 1 <= beam_size <= 8:
+            raise CapdecError(f"decode_beam_constrained: beam_size must be an integer in 1..8, got {beam_size!r}")
+        n = int(prefix_embed.shape[0])
+        if isinstance(phrases, torch.Tensor):
+            ph = phrases.detach().to("cpu", torch.int32).numpy()
+        elif isinstance(phrases, np.ndarray):
+            ph = phrases.astype(np.int32)
+        else:
+            ph = pack_phrases(phrases)
+        if ph.shape != (n, 4, 4):
+            raise CapdecError(f"decode_beam_constrained: phrases must be [n, 4, 4] = ({n}, 4, 4), got {tuple(ph.shape)}")
+        with self._processors(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                              min_length=min_length, logit_bias=logit_bias):
+            return self._decode_beam_constrained(prefix_embed, np.ascontiguousarray(ph), stop_id, beam_size, entry_length,
+                                                 temperature)
+
+    def _decode_beam_constrained(self, prefix_embed, phrases, stop_id, beam_size, entry_length, temperature):
+        p = self._dev(prefix_embed)
+        n, P, _ = p.shape
+        ph = torch.from_numpy(phrases).to(self.device)
+        ids = torch.empty(n, beam_size, entry_length, device=self.device, dtype=torch.int32)
+        lens = torch.empty(n, beam_size, device=self.device, dtype=torch.int32)
+        scores = torch.empty(n, beam_size, device=self.device, dtype=torch.float32)
+        order = torch.empty(n, beam_size, device=self.device, dtype=torch.int32)
+        met = torch.empty(n, beam_size, device=self.device, dtype=torch.int32)
+        self._sync_stream()
+        self._chk(self.lib.capdec_decode_beam_constrained(self._h, p.data_ptr(), ph.data_ptr(), n, P, int(beam_size),
+                                                          int(stop_id), int(entry_length), float(temperature),
+                                                          ids.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                                          order.data_ptr(), met.data_ptr()),
+                  "capdec_decode_beam_constrained")
+        return ids, lens, scores, order, met
 
     def decode_contrastive(self, prefix_embed: torch.Tensor, top_k: int = 4, penalty_alpha: float = 0.6, stop_id: int = 13,
                            alt_stop_id: int = -1, entry_length: int = 67, return_trace: bool = False, *,

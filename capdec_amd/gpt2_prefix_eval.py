@@ -4,7 +4,9 @@
 no-cache re-forward and the per-token host syncs of the reference are replaced by one call
 into the KV-cached HIP decode (``capdec_decode_greedy`` / ``capdec_decode_beam``).  ``generate_diverse_beam`` /
 ``generate_diverse_beam_batch`` are ``generate_beam`` with diverse (group) beam search (``capdec_decode_beam_groups``:
-``num_beam_groups`` / ``diversity_penalty``), for callers who want beams that differ.  ``generate_samples`` /
+``num_beam_groups`` / ``diversity_penalty``), for callers who want beams that differ.  ``generate_constrained_beam`` /
+``generate_constrained_beam_batch`` are ``generate_beam`` with words that must occur in the caption
+(``capdec_decode_beam_constrained``: ``force_words_ids`` of ``transformers.generate``).  ``generate_samples`` /
 ``generate_samples_batch`` make ``top_p``, ``temperature`` and ``entry_count`` live: nucleus sampling
 (``capdec_decode_sample``), the multinomial line the reference leaves commented out (:178).  ``generate_guided`` /
 ``generate_guided_batch`` decode under classifier-free guidance against a negative prefix (``capdec_decode_guided``:
@@ -28,7 +30,7 @@ import numpy as np
 import torch
 
 from ._capi import CapdecError
-from .engine import LogitsProcessors, get_engine
+from .engine import MAX_PHRASE_TOKENS, MAX_PHRASES, LogitsProcessors, get_engine, pack_phrases
 from .gpt2_prefix import ClipCaptionModel
 from .train import _next_seed
 
@@ -96,6 +98,52 @@ def decode_diverse_beam_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_t
     kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     return model.engine.decode_beam_groups(embed, stop_token_index, beam_size, num_beam_groups, diversity_penalty, entry_length,
                                            temperature, **kw)
+
+
+def encode_force_words(tokenizer, words: Sequence[str]) -> List[List[int]]:
+    """the phrases of one caption from its words: ``tokenizer.encode(" " + word)`` each (GPT-2's BPE marks the leading
+    space, so this is the word as it stands inside a sentence).  More than 4 words, or a word of more than 4 tokens (or of
+    none), is a CapdecError that names the word."""
+    words = list(words)
+    if len(words) > MAX_PHRASES:
+        raise CapdecError(f"force_words: at most {MAX_PHRASES} words per caption, got {len(words)}: {words!r} (first one too many: "
+                          f"{words[MAX_PHRASES]!r})")
+    out = []
+    for w in words:
+        if not isinstance(w, str):
+            raise CapdecError(f"force_words: a word must be a string, got {w!r}")
+        ids = [int(t) for t in tokenizer.encode(" " + w)]
+        if not 1 <= len(ids) <= MAX_PHRASE_TOKENS:
+            raise CapdecError(f"force_words: the word {w!r} encodes to {len(ids)} tokens, 1..{MAX_PHRASE_TOKENS} are supported")
+        out.append(ids)
+    return out
+
+
+def _phrases_of(tokenizer, n: int, force_words, force_words_ids) -> np.ndarray:
+    """the [n, 4, 4] phrase table from per-caption words or per-caption id lists (both None: no phrases)"""
+    if force_words is not None and force_words_ids is not None:
+        raise CapdecError("give force_words or force_words_ids, not both")
+    if force_words is not None:
+        per_caption = [encode_force_words(tokenizer, ws) for ws in force_words]
+    elif force_words_ids is not None:
+        per_caption = [list(p) for p in force_words_ids]
+    else:
+        per_caption = [[] for _ in range(n)]
+    if len(per_caption) != n:
+        raise CapdecError(f"constrained beam search: {len(per_caption)} lists of forced words for {n} captions")
+    return pack_phrases(per_caption)
+
+
+def decode_constrained_beam_ids(model: ClipCaptionModel, embed: torch.Tensor, phrases, stop_token_index: int,
+                                beam_size: int = 5, entry_length: int = 67, temperature: float = 1.0, *,
+                                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                                min_length: Optional[int] = None, logit_bias=None):
+    """embed [N, P, d], phrases (per caption a list of up to 4 id lists of 1..4 tokens, or int32 [N, 4, 4] with -1 in the
+    unused places) -> (ids [N, beam, T], lens [N, beam], scores [N, beam], order [N, beam], met [N, beam]) of the lexically
+    constrained beam search (``capdec_decode_beam_constrained``): rows sorted by the number of phrases they hold, then by
+    mean log-prob, descending; ``met`` is the bitmask of the phrases a row holds."""
+    kw = _processor_kw(model, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
+    return model.engine.decode_beam_constrained(embed, phrases, stop_token_index, beam_size, entry_length, temperature, **kw)
 
 
 def sample_ids(model: ClipCaptionModel, embed: torch.Tensor, stop_token_index: int, entry_length: int = 67,
@@ -207,6 +255,26 @@ def generate_diverse_beam_batch(model, tokenizer, embed: torch.Tensor, beam_size
     return out
 
 
+def generate_constrained_beam_batch(model, tokenizer, embed: torch.Tensor, beam_size: int = 5, force_words=None,
+                                    force_words_ids=None, entry_length: int = 67, temperature: float = 1.,
+                                    stop_token: str = '.', return_met: bool = False, *,
+                                    repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                                    min_length: Optional[int] = None, logit_bias=None):
+    """``generate_beam_batch`` with words every caption must contain: ``force_words`` is one list of up to 4 words per
+    caption (each encoded as ``" " + word``, up to 4 tokens), ``force_words_ids`` one list of up to 4 token-id lists per
+    caption.  -> per caption the ``beam_size`` texts, the rows that hold the most words first, then by score; with
+    ``return_met`` also the int array [N, beam] of the bitmasks of the words each row holds (a row lacks a word only when
+    ``entry_length`` ran out first)."""
+    stop = tokenizer.encode(stop_token)[0]
+    phrases = _phrases_of(tokenizer, int(embed.shape[0]), force_words, force_words_ids)
+    ids, lens, _, _, met = decode_constrained_beam_ids(model, embed, phrases, stop, beam_size, entry_length, temperature,
+                                                       repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                                       min_length=min_length, logit_bias=logit_bias)
+    ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+    texts = [[tokenizer.decode(ids[r, b, :int(lens[r, b])]) for b in range(ids.shape[1])] for r in range(ids.shape[0])]
+    return (texts, met.cpu().numpy()) if return_met else texts
+
+
 # --------------------------------------------------------------------------- reference signatures
 def generate_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 5, prompt=None, embed=None,
                   entry_length=67, temperature=1., stop_token: str = '.'):
@@ -224,6 +292,31 @@ def generate_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 5, prompt
         toks = ids[b, :int(lens[b])]
         if prompt_ids is not None:   # reference :86-87: prompt tokens stay in the output
             # seq_lengths counts generated tokens only (+ the reference slices the concatenated row)
+            toks = np.concatenate([np.asarray(prompt_ids, dtype=toks.dtype), ids[b]])[:int(lens[b])]
+        out.append(tokenizer.decode(toks))
+    return out
+
+
+def generate_constrained_beam(model: ClipCaptionModel, tokenizer, beam_size: int = 5, prompt=None, embed=None,
+                              force_words=None, force_words_ids=None, entry_length=67, temperature=1.,
+                              stop_token: str = '.'):
+    """``generate_beam`` with words the caption must contain: one caption ([1, P, d], or a prompt), ``force_words`` a list
+    of up to 4 words (each encoded as ``" " + word``, up to 4 tokens) or ``force_words_ids`` a list of up to 4 token-id
+    lists -> ``beam_size`` texts ordered like ``generate_beam``'s, the rows that hold the most words in front.  Prompt
+    tokens stay in front as in ``generate_beam``.  (Logits processors: ``model.logits_processors``.)"""
+    model.eval()
+    prefix, prompt_ids = _prefix_from(model, tokenizer, None, prompt, embed)
+    if prefix.shape[0] != 1:
+        raise CapdecError("generate_constrained_beam takes one caption ([1, P, d]); use generate_constrained_beam_batch for [N, P, d]")
+    stop = tokenizer.encode(stop_token)[0]
+    phrases = _phrases_of(tokenizer, 1, None if force_words is None else [force_words],
+                          None if force_words_ids is None else [force_words_ids])
+    ids, lens = decode_constrained_beam_ids(model, prefix, phrases, stop, beam_size, entry_length, temperature)[:2]
+    ids, lens = ids.cpu().numpy()[0], lens.cpu().numpy()[0]
+    out = []
+    for b in range(beam_size):
+        toks = ids[b, :int(lens[b])]
+        if prompt_ids is not None:   # as generate_beam: the prompt tokens stay in the output, the row is cut at seq_lengths
             toks = np.concatenate([np.asarray(prompt_ids, dtype=toks.dtype), ids[b]])[:int(lens[b])]
         out.append(tokenizer.decode(toks))
     return out

@@ -18,10 +18,11 @@ import numpy as np
 import torch
 
 from . import distributed as cdist
+from ._capi import CapdecError
 from .engine import Engine, get_engine
 from .gpt2_prefix import ClipCaptionModel, MappingType  # noqa: F401
-from .gpt2_prefix_eval import (decode_beam_ids, decode_greedy_ids, generate2, generate2_batch,  # noqa: F401
-                               generate_beam, generate_beam_batch)
+from .gpt2_prefix_eval import (_phrases_of, decode_beam_ids, decode_constrained_beam_ids, decode_greedy_ids,  # noqa: F401
+                               generate2, generate2_batch, generate_beam, generate_beam_batch)
 
 
 class Timer:
@@ -86,15 +87,22 @@ def caption_ids(model: ClipCaptionModel, embeddings: torch.Tensor, stop_token_in
                 beam_size: int = 5, entry_length: int = 67, dont_normalize_prefix: bool = False,
                 modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1, *,
                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                min_length: Optional[int] = None, logit_bias=None, modality_bridger=None):
+                min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, phrases=None):
     """The whole device-side path for this rank's shard of ``embeddings`` [N, D].
     Returns (ids [n_local, T] int32 of the best caption, lens [n_local]) and, for beam, the
     mean-log-prob score of the best beam.  The keyword-only logits processors (None: ``model.logits_processors``'s) are
-    those of ``decode_beam_ids`` / ``decode_greedy_ids``."""
+    those of ``decode_beam_ids`` / ``decode_greedy_ids``.  ``phrases`` (int32 [N, 4, 4], beam only; None: the plain beam):
+    the phrases every caption must contain (``decode_constrained_beam_ids``)."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     lo, hi = cdist.shard_bounds(embeddings.shape[0], rank, world)
     pe = prefix_from_embeddings(model, embeddings[lo:hi], dont_normalize_prefix, modality_offset,
                                 **_given(modality_bridger=modality_bridger))
+    if phrases is not None:
+        if not beam:
+            raise CapdecError("caption_ids: forced words need the beam decode (beam=True)")
+        ids, lens, scores = decode_constrained_beam_ids(model, pe, np.asarray(phrases)[lo:hi], stop_token_index, beam_size,
+                                                        entry_length, **pk)[:3]
+        return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
     if beam:
         ids, lens, scores, _ = decode_beam_ids(model, pe, stop_token_index, beam_size, entry_length, **pk)
         return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
@@ -107,9 +115,10 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
                dont_normalize_prefix: bool = False, modality_offset: Optional[torch.Tensor] = None,
                rank: int = 0, world: int = 1, timer: Optional[Timer] = None, *,
                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-               min_length: Optional[int] = None, logit_bias=None, modality_bridger=None) -> List[Dict]:
+               min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, force_words=None) -> List[Dict]:
     """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  ``modality_bridger`` (--modality_bridger): see
-    ``prefix_from_embeddings``.  Writes the
+    ``prefix_from_embeddings``.  ``force_words`` (beam only; None: the plain beam): per caption a list of up to 4 words its
+    caption must contain (``generate_constrained_beam_batch``).  Writes the
     reference's predictions JSON (``[{"caption": lower-cased text, "image_id": id}]``, :260-261,
     :301) -- the whole list, not only every 99th flush."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias,
@@ -118,6 +127,8 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
     if len(data) != embeddings.shape[0]:
         raise ValueError(f"make_preds: {len(data)} data entries but {embeddings.shape[0]} embeddings")
     stop = tokenizer.encode('.')[0]
+    if force_words is not None:
+        pk["phrases"] = _phrases_of(tokenizer, len(data), force_words, None)
     if timer is not None:           # the reference's `with timer:` (:214-233) around this rank's share of the batch
         with timer.bind(model):
             ids, lens, _ = caption_ids(model, embeddings, stop, beam, 5, entry_length, dont_normalize_prefix,

@@ -403,6 +403,51 @@ int capdec_decode_beam_groups(capdec_ctx *ctx, const float *d_prefix, int n, int
                               int32_t *d_ids, int32_t *d_lens, float *d_scores,
                               int32_t *d_order,
                               float *d_logp /* [n, beam] or NULL */);
+/* Lexically constrained beam search (Anderson et al. 2017) by dynamic beam allocation (Post & Vilar 2018; `force_words_ids`
+ * of transformers.generate) on the beam decode: capdec_decode_beam's inputs plus, per caption, phrases that must occur in
+ * it.  d_phrases is int32 [n, 4, 4]: caption r has up to 4 phrases of 1..4 token ids each; unused places hold -1; a phrase
+ * is the leading non-negative run of its row, a caption's phrases are its leading non-empty rows.  EVERY phrase of a caption
+ * must occur in the caption as a contiguous token run (conjunctive constraints).
+ * Hypothesis state, following each beam slot through every permutation next to tokens, seq, scores and stopped:
+ *   met  bitmask of the phrases fully matched;  cur  the phrase in progress, or none;  pos  tokens of cur already matched,
+ *   1..len-1.
+ * Transition adv(state, t):
+ *   1. if cur is set and phrase[cur][pos] == t: pos += 1; when pos == len, the bit of cur is set in met and cur, pos are
+ *      cleared.  Nothing else happens to the state in this case.
+ *   2. otherwise cur and pos are cleared -- the progress is lost, there is no back-tracking inside a phrase (as in
+ *      transformers' PhrasalConstraint) -- and
+ *   3. with c the lowest-index unmet phrase with phrase[c][0] == t, if there is one: len == 1 sets its bit, otherwise
+ *      cur = c, pos = 1.
+ * bank(state) = sum of len over the met phrases + pos.  The special tokens S(state) are the next token of cur, if any, and
+ * the first token of every unmet phrase: at most 5.  Every token outside S leads to the same state (met, none, 0).
+ * Per step, for a live row, in this order: the logits processors that are set (steps 1-4 of
+ * capdec_set_logits_processors); if the row's met is not complete, l[stop_id] <- -inf (a caption cannot end before its
+ * phrases are in it); the division by the temperature; lp = log_softmax.  A stopped row keeps its single candidate (token
+ * 0, log-prob 0, state unchanged), as in capdec_decode_beam.  key = (scores[row] + lp) / seq_new[row], fp32 in that
+ * operation order: the plain beam's key.
+ * Selection per caption: every candidate (row, token) with a finite key belongs to bank bank(adv(state_row, token)).  The
+ * non-empty banks are taken in descending order and passed over repeatedly from the highest to the lowest; each visit takes
+ * the bank's best remaining candidate (larger key, then smaller flat index = slot * vocab + token); the passes end when
+ * `beam` candidates are taken; the slots are filled in the order taken.  Step 0 has one row per caption with the empty
+ * state and is selected the same way.  scores[slot] = key * seq_new[src]; tokens, seq, stopped, the state and the ancestor
+ * table follow the winners.  A caption is done when every slot is stopped.
+ * End: the returned rows are sorted by the number of phrases fully met (descending), then scores / seq (descending), then
+ * slot (ascending); d_ids, d_lens, d_scores, d_order as in capdec_decode_beam; d_met [n, beam] (may be NULL) receives each
+ * returned row's met mask, so that a caller sees when entry_length ran out before the phrases were in.  With no phrases
+ * there is one bank, nothing is banned, and the call is capdec_decode_beam on the same logits route bit for bit.
+ * The call always materialises the logits (CAPDEC_SAMPLE_ROWS rows at a time, as the processors do): the special tokens'
+ * logits come from the same arithmetic as the rest of the row.  A row's list -- S, then its best `beam` tokens outside S,
+ * ties to the smaller column -- is enough for an exact selection: all tokens outside S land in one bank, of which at most
+ * `beam` can be taken.  Logits processors and the bias compose (they act before the stop ban); capdec_set_compact,
+ * capdec_set_kv_budget, capdec_set_batch_invariant and the GEMM mode are honoured; a caption's result does not depend on
+ * the batch size, the chunking or the compaction.  Guidance and beam groups are separate entry points and do not take
+ * constraints.  capdec_set_debug_diverge is not honoured here.  Refused before any launch (capdec_last_error): a token id
+ * outside the vocabulary, a phrase that holds stop_id, a hole in front of a used place (a used place behind a -1 of its
+ * phrase, a phrase behind an empty one), beam outside 1..8. */
+int capdec_decode_beam_constrained(capdec_ctx *ctx, const float *d_prefix, const int32_t *d_phrases, int n, int P,
+                                   int beam, int stop_id, int entry_length, float temperature,
+                                   int32_t *d_ids, int32_t *d_lens, float *d_scores, int32_t *d_order,
+                                   int32_t *d_met /* [n, beam] or NULL */);
 /* Contrastive search (Su et al. 2022; `penalty_alpha` / `top_k` of transformers.generate): the one decode that reads the
  * model's hidden states.  top_k = K in 1..8, penalty_alpha = a in [0, 1] (finite), prefix_length + entry_length <=
  * min(1024, n_positions) -- one position more than capdec_decode_greedy, because every emitted token is chosen after its
