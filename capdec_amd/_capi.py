@@ -177,6 +177,7 @@ SIGNATURES = {
                                        C.c_float, _VP, _VP, _VP, _VP]),
     "capdec_gemm_f32": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                   _VP, C.c_int, C.c_int]),
+    "capdec_gemm_tn_f32": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_int]),
     "capdec_preprocess_images": (C.c_int, [_VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                            C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, _VP]),
     "capdec_comm_unique_id": (C.c_int, [C.c_char_p]),

@@ -1,6 +1,7 @@
 // The GEMM dispatch behind every projection of the path: the cache of packed weight planes, which operand format a launch
 // takes in the context's precision mode, the LayerNorm -> GEMM and packed-chain forms of the block stack, the fused lm_head
-// (LayerNorm -> GEMM -> per-tile top-k), and capdec_gemm_f32 (the test / micro-benchmark hook onto the same launchers).
+// (LayerNorm -> GEMM -> per-tile top-k), and capdec_gemm_f32 / capdec_gemm_tn_f32 (the test / micro-benchmark hooks onto the
+// same launchers).
 // Every packed launch goes through launch_packed, which asks gemm_plan() (gemm_plan.h: a pure host function, tested without
 // a GPU) for the kernel, tile geometry, split-K slices, grid and workspace size, attaches the workspace and hands the plan
 // to the launcher -- nothing about a launch is decided anywhere else.
@@ -371,5 +372,13 @@ int capdec_gemm_f32(capdec_ctx *c, const float *a, int lda, const float *bt, int
     return gemm(c, a, lda, bt, ldb, cc, ldc, M, N, K, bias, act, resid, ldr, /*weight=*/cache);
 }
 
+// test hook onto gemm_tn, the weight-gradient product of the train step, as it stands: no routing of its own
+int capdec_gemm_tn_f32(capdec_ctx *c, const float *xa, int lda, const float *xb, int ldb, int rows, int n1, int n2, float *cc,
+                       int ldc) {
+    CAPDEC_CHECK(c && xa && xb && cc, "gemm_tn: null argument");
+    CAPDEC_CHECK(rows > 0 && n1 > 0 && n2 > 0 && lda >= n1 && ldb >= n2 && ldc >= n2, "gemm_tn: bad shape or row stride");
+    CAPDEC_HIP(hipSetDevice(c->device));
+    return gemm_tn(c, xa, lda, xb, ldb, rows, n1, n2, cc, ldc);
+}
 
 }  // extern "C"

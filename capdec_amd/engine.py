@@ -1277,6 +1277,26 @@ class Engine:
                   "capdec_gemm_f32")
         return out
 
+    def gemm_tn(self, xa: torch.Tensor, xb: torch.Tensor, out=None) -> torch.Tensor:
+        """out [N1, N2] = xa^T . xb for xa [rows, N1], xb [rows, N2]: the weight-gradient product of the train step
+        (dW = dY^T X) through the launch the train step uses.  Both operands and ``out=`` may be row-strided views (their
+        real row strides are passed as lda / ldb / ldc)."""
+        xa, xb = self._rows(xa, "xa"), self._rows(xb, "xb")
+        rows, N1 = xa.shape
+        N2 = xb.shape[1]
+        if xb.shape[0] != rows:
+            raise CapdecError(f"gemm_tn: xa is [{rows}, {N1}] but xb is {list(xb.shape)}")
+        if out is None:
+            out = torch.empty(N1, N2, device=self.device, dtype=torch.float32)
+        else:
+            out = self._rows(out, "out")
+            if tuple(out.shape) != (N1, N2):
+                raise CapdecError(f"gemm_tn: out= must be [{N1}, {N2}], got {list(out.shape)}")
+        self._sync_stream()
+        self._chk(self.lib.capdec_gemm_tn_f32(self._h, xa.data_ptr(), xa.stride(0), xb.data_ptr(), xb.stride(0), rows, N1, N2,
+                                              out.data_ptr(), out.stride(0)), "capdec_gemm_tn_f32")
+        return out
+
     def set_gemm_mode(self, mode: str):
         """'f16x2' (default: fp32-accurate, operands as two fp16 planes, 3 MFMAs per product), 'bf16x3' (fp32-accurate,
         three bf16 planes, 6 MFMAs per product), 'f32' (native fp32 MFMA), 'bf16' (bf16 GEMM operands and KV cache, fp32

@@ -802,6 +802,10 @@ int capdec_gather_ids(capdec_ctx *ctx, const int32_t *d_ids, const int32_t *d_le
 int capdec_gemm_f32(capdec_ctx *ctx, const float *d_a, int lda, const float *d_bt, int ldb,
                     float *d_c, int ldc, int M, int N, int K, const float *d_bias,
                     const float *d_resid, int ldr, int act);
+/* C[n1,n2] = Xa[rows,n1]^T . Xb[rows,n2] (row strides lda / ldb / ldc): the weight-gradient product of the train step
+ * (dW = dY^T X, reduction over the token rows), exactly as the train step calls it. */
+int capdec_gemm_tn_f32(capdec_ctx *ctx, const float *d_xa, int lda, const float *d_xb, int ldb, int rows, int n1, int n2,
+                       float *d_c, int ldc);
 /* hipEvent timers on the context's stream -- the reference's Timer (predictions_runner.py:125-150) */
 int capdec_timer_start(capdec_ctx *ctx);
 int capdec_timer_stop_ms(capdec_ctx *ctx, float *ms);   /* records, synchronises, returns elapsed */
