@@ -405,18 +405,21 @@ struct BeamState {
     float *logp = nullptr;      // [ncap, beam]  diverse beam search only (diverse.hip): running sum of the UNPENALISED log-probs
 };
 int launch_beam_init(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
-                     int ncap, int beam, int k, int T, int ctx, int P, int stop_id);
+                     int ncap, int beam, int k, int T, int stop_id);
+// pos_cur: the position this step's token was fed at (the step's attention read positions 0 .. pos_cur)
 int launch_beam_step(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
-                     int ncap, int beam, int k, int T, int ctx, int step, int pos_new, int vocab, int stop_id,
+                     int ncap, int beam, int k, int T, int ctx, int step, int pos_cur, int vocab, int stop_id,
                      const int *cmap = nullptr);
+// rows ordered by (score / seq, slot); with con_state (ConstraintState::state) by (phrases met, score / seq, slot), and
+// met [ncap, beam] (may be nullptr) receives the rows' met masks
 int launch_beam_finalize(hipStream_t st, const BeamState &s, int ncap, int beam, int T, int *ids, int *lens,
-                         float *scores, int *order);
+                         float *scores, int *order, const int *con_state = nullptr, int *met = nullptr);
 // diverse.hip: diverse (group) beam search -- the beam step run per group of beam / groups slots, with the tokens that the
 // earlier groups of the caption took at this step penalised by `diversity` each (the contract: include/capdec.h)
 int launch_group_beam_init(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
-                           int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int P, int stop_id);
+                           int ncap, int beam, int groups, float diversity, int k, int T, int stop_id);
 int launch_group_beam_step(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
-                           int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int step, int pos_new,
+                           int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int step, int pos_cur,
                            int vocab, int stop_id, const int *cmap = nullptr);
 // logp_out[cap, rank] = s.logp[cap, order[cap, rank]]: the unpenalised sums in the order launch_beam_finalize returned
 int launch_group_beam_logp(hipStream_t st, const BeamState &s, int ncap, int beam, const int *order, float *logp_out);
@@ -438,14 +441,10 @@ int launch_logits_select_forced(hipStream_t st, const float *logits, int ld, int
                                 float inv_temp, const ConstraintState &cs, const int *cmap, int step, int stop_id,
                                 float *lse, float *top_val, int *top_idx);
 int launch_constrained_beam_init(hipStream_t st, const BeamState &s, const ConstraintState &cs, const float *lse,
-                                 const float *top_val, const int *top_idx, int ncap, int beam, int T, int ctx, int vocab,
-                                 int stop_id);
+                                 const float *top_val, const int *top_idx, int ncap, int beam, int T, int vocab, int stop_id);
 int launch_constrained_beam_step(hipStream_t st, const BeamState &s, const ConstraintState &cs, const float *lse,
                                  const float *top_val, const int *top_idx, int ncap, int beam, int T, int ctx, int step,
-                                 int pos_new, int vocab, int stop_id, const int *cmap = nullptr);
-// launch_beam_finalize with the rows ordered by (phrases met, score / seq, slot); met [ncap, beam] (may be nullptr)
-int launch_constrained_finalize(hipStream_t st, const BeamState &s, const ConstraintState &cs, int ncap, int beam, int T,
-                                int *ids, int *lens, float *scores, int *order, int *met);
+                                 int pos_cur, int vocab, int stop_id, const int *cmap = nullptr);
 // contrastive.hip: contrastive search (capdec_decode_contrastive; the contract: include/capdec.h).  K candidate rows per
 // caption in the beam layout (row = caption * K + c); hist [ncap, ctx, d] holds ln_f of every position of the chosen path,
 // L2-normalised.

@@ -21,25 +21,19 @@
 //   5. so a row's list is S followed by its best `beam` tokens outside S: at most 8 x 13 = 104 candidates per caption, two
 //      per lane of one wavefront.
 // With no phrases S is empty, nothing is banned, there is one bank, and the round-robin takes the best `beam` in order:
-// the plain beam bit for bit (the row pass below is logits_select_kernel's arithmetic, operation for operation).
+// the plain beam bit for bit (the row pass is the one logits_select_kernel runs: row_select.h's logits_row_pass; staging,
+// write-back and the end are the plain beam's own code: beam_state.h and select.hip's beam_finalize_kernel).
 // BeamState::diverge is not honoured here.
-#include "row_select.h"
+#include "beam_state.h"
 
 namespace capdec {
 
 namespace {
 
-constexpr int CON_THREADS = 256, CON_WAVES = CON_THREADS / WAVE;
-constexpr int CON_T_MAX = 1024, CON_CTX_MAX = 1024;               // select.hip's limits
+constexpr int CON_THREADS = 256;
 constexpr int CON_NONE = 0x7fffffff;
 
-// ---- the state of a slot in one int: met in bits 0..3, cur + 1 in bits 4..6 (0: none), pos in bits 8..10
-__device__ __forceinline__ int con_pack(int met, int cur, int pos) { return met | ((cur + 1) << 4) | (pos << 8); }
-__device__ __forceinline__ int con_met(int st) { return st & 15; }
-__device__ __forceinline__ int con_cur(int st) { return ((st >> 4) & 7) - 1; }
-__device__ __forceinline__ int con_pos(int st) { return (st >> 8) & 7; }
-
-// ph: the caption's phrase table, CON_PHRASES x CON_LEN ints
+// (a slot's state packed into one int: beam_state.h)  ph: the caption's phrase table, CON_PHRASES x CON_LEN ints
 __device__ __forceinline__ int con_len(const int *ph, int c) {
     int n = 0;
     while (n < CON_LEN && ph[c * CON_LEN + n] >= 0) ++n;
@@ -94,12 +88,7 @@ __device__ __forceinline__ void con_round_robin(float k0, int f0, int b0, float 
             if (f1 != CON_NONE && b1 == b && (q < 0 || better(k1, f1, v, i))) { v = k1; i = f1; q = 1; }
             float gv = v;
             int gi = i;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(gv, o, 64);
-                const int oi = __shfl_xor(gi, o, 64);
-                if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-            }
+            wave_best(gv, gi);
             if (gi == CON_NONE) { present &= ~(1u << b); continue; }     // the bank is used up
             if (q == 0 && gi == f0) { won0 = taken; f0 = CON_NONE; }
             if (q == 1 && gi == f1) { won1 = taken; f1 = CON_NONE; }
@@ -108,9 +97,17 @@ __device__ __forceinline__ void con_round_robin(float k0, int f0, int b0, float 
     }
 }
 
-// ---- logsumexp, the special tokens' values and the best K tokens outside them, one pass over the row: logits_select_kernel
-// with the stop ban and the exclusion.  Row r of the launch is activation row row0 + r: caption (row0 + r) / rpc through
-// cmap, slot (row0 + r) % rpc; state == nullptr (step 0): the empty state.
+// ---- logsumexp, the special tokens' values and the best K tokens outside them, one pass over the row: row_select.h's
+// logits_row_pass (what logits_select_kernel runs) under the policy below.  Row r of the launch is activation row row0 + r:
+// caption (row0 + r) / rpc through cmap, slot (row0 + r) % rpc; state == nullptr (step 0): the empty state.
+struct RowForced {                      // the stop token banned while phrases are unmet; the special tokens kept off the list
+    static constexpr bool filtered = true;
+    int ban, s0, s1, s2, s3, s4;
+    bool any;                           // (false: -1 everywhere, no special token)
+    __device__ __forceinline__ bool excluded(int j) const {
+        return any && (j == s0 || j == s1 || j == s2 || j == s3 || j == s4);
+    }
+};
 template <int K>
 __global__ __launch_bounds__(CON_THREADS) void logits_select_forced_kernel(const float *__restrict__ logits, int ld, int V,
                                                                            int row0, float inv_temp,
@@ -120,14 +117,12 @@ __global__ __launch_bounds__(CON_THREADS) void logits_select_forced_kernel(const
                                                                            int stop_id, float *__restrict__ lse,
                                                                            float *__restrict__ top_val,
                                                                            int *__restrict__ top_idx) {
-    __shared__ float wm[CON_WAVES], ws[CON_WAVES];
-    __shared__ float cv[CON_WAVES * K];
-    __shared__ int ci[CON_WAVES * K];
     __shared__ int ph[CON_PHRASES * CON_LEN];
     __shared__ int sp[CON_SPECIAL + 1];                          // the special tokens (-1: unused place), then the ban flag
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const float *x = logits + (size_t)r * ld;
-    const int R = row0 + r;
+    const int tid = threadIdx.x;
+    const size_t r = blockIdx.x;
+    const float *x = logits + r * ld;
+    const int R = row0 + (int)r;
     const int cap = cmap ? cmap[R / rpc] : R / rpc;
     if (tid < CON_PHRASES * CON_LEN) ph[tid] = phrases[(size_t)cap * CON_PHRASES * CON_LEN + tid];
     __syncthreads();
@@ -144,72 +139,18 @@ __global__ __launch_bounds__(CON_THREADS) void logits_select_forced_kernel(const
         sp[CON_SPECIAL] = met != (1 << np) - 1;
     }
     __syncthreads();
-    const int s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3], s4 = sp[4];
-    const bool any = (s0 & s1 & s2 & s3 & s4) >= 0;              // (-1 everywhere: no special token)
-    const int ban = sp[CON_SPECIAL] ? stop_id : -1;
-    float m = -INFINITY, s = 0.f;
-    LaneTopk<K> best;
-    best.clear();
-    auto offer = [&](float v, int j) {
-        if (any && (j == s0 || j == s1 || j == s2 || j == s3 || j == s4)) return;
-        best.push(v, j);
-    };
-    const int V4 = V & ~3;
-    for (int j = tid * 4; j < V4; j += CON_THREADS * 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(x + j);
-        float v0 = q.x * inv_temp, v1 = q.y * inv_temp, v2 = q.z * inv_temp, v3 = q.w * inv_temp;
-        if ((unsigned)(ban - j) < 4u) {
-            if (ban == j) v0 = -INFINITY;
-            if (ban == j + 1) v1 = -INFINITY;
-            if (ban == j + 2) v2 = -INFINITY;
-            if (ban == j + 3) v3 = -INFINITY;
-        }
-        online_rescale(m, s, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
-        if (m > -INFINITY) s += ((expf(v0 - m) + expf(v1 - m)) + expf(v2 - m)) + expf(v3 - m);
-        offer(v0, j);
-        offer(v1, j + 1);
-        offer(v2, j + 2);
-        offer(v3, j + 3);
-    }
-    for (int j = V4 + tid; j < V; j += CON_THREADS) {
-        const float v = j == ban ? -INFINITY : x[j] * inv_temp;
-        online_rescale(m, s, v);
-        if (m > -INFINITY) s += expf(v - m);
-        offer(v, j);
-    }
+    RowForced pol;
+    pol.s0 = sp[0]; pol.s1 = sp[1]; pol.s2 = sp[2]; pol.s3 = sp[3]; pol.s4 = sp[4];
+    pol.any = (pol.s0 & pol.s1 & pol.s2 & pol.s3 & pol.s4) >= 0;
+    pol.ban = sp[CON_SPECIAL] ? stop_id : -1;
     // the special tokens at their fixed places (a phrase never holds the stop token: the ban does not reach them)
     if (tid < CON_SPECIAL) {
         const int t = sp[tid];
-        top_idx[(size_t)r * CON_LIST + tid] = t;
-        top_val[(size_t)r * CON_LIST + tid] = t >= 0 ? x[t] * inv_temp : -INFINITY;
+        top_idx[r * CON_LIST + tid] = t;
+        top_val[r * CON_LIST + tid] = t >= 0 ? x[t] * inv_temp : -INFINITY;
     }
-    // logsumexp: lanes -> wavefront -> workgroup, each in a fixed order
-    const float M = wave_max(m);
-    const float t = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
-    if (lane == 0) { wm[wave] = M; ws[wave] = t; }
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        float gv;
-        int gi;
-        best.pop_best(gv, gi);
-        if (lane == 0) { cv[wave * K + q] = gv; ci[wave * K + q] = gi; }
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    float Mb = wm[0];
-#pragma unroll
-    for (int w = 1; w < CON_WAVES; ++w) Mb = fmaxf(Mb, wm[w]);
-    float S = 0.f;
-#pragma unroll
-    for (int w = 0; w < CON_WAVES; ++w) S += wm[w] > -INFINITY ? ws[w] * expf(wm[w] - Mb) : 0.f;
-    lse[r] = Mb + logf(S);
-    best.clear();
-    for (int q = 0; q < CON_WAVES * K; ++q) best.push(cv[q], ci[q]);
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        top_val[(size_t)r * CON_LIST + CON_SPECIAL + j] = best.v[j];
-        top_idx[(size_t)r * CON_LIST + CON_SPECIAL + j] = best.i[j];
-    }
+    logits_row_pass<K, CON_THREADS>(x, V, inv_temp, pol, lse + r, top_val + r * CON_LIST + CON_SPECIAL,
+                                    top_idx + r * CON_LIST + CON_SPECIAL);
 }
 
 // ---- step 0: one logits row per caption (prefill last position), the empty state.  lane p < CON_LIST holds place p of the
@@ -217,15 +158,14 @@ __global__ __launch_bounds__(CON_THREADS) void logits_select_forced_kernel(const
 __global__ __launch_bounds__(64) void constrained_beam_init_kernel(BeamState s, ConstraintState cs,
                                                                    const float *__restrict__ lse,
                                                                    const float *__restrict__ top_val,
-                                                                   const int *__restrict__ top_idx, int ncap, int beam,
-                                                                   int T, int vocab, int stop_id) {
+                                                                   const int *__restrict__ top_idx, int beam, int T,
+                                                                   int vocab, int stop_id) {
     __shared__ int ph[CON_PHRASES * CON_LEN];
-    __shared__ int w_tok[CON_BEAM_MAX], w_cst[CON_BEAM_MAX];
-    __shared__ float w_key[CON_BEAM_MAX];
+    __shared__ int w_tok[BEAM_MAX], w_cst[BEAM_MAX];
+    __shared__ float w_key[BEAM_MAX];
     const int cap = blockIdx.x, lane = threadIdx.x;
-    const size_t cb0 = (size_t)cap * beam;
     if (lane < CON_PHRASES * CON_LEN) ph[lane] = cs.phrases[(size_t)cap * CON_PHRASES * CON_LEN + lane];
-    if (lane < CON_BEAM_MAX) { w_tok[lane] = 0; w_cst[lane] = 0; w_key[lane] = -INFINITY; }
+    if (lane < BEAM_MAX) { w_tok[lane] = 0; w_cst[lane] = 0; w_key[lane] = -INFINITY; }
     __syncthreads();
     float key = -INFINITY;
     int flat = CON_NONE, nst = 0, bank = 0;
@@ -246,61 +186,38 @@ __global__ __launch_bounds__(64) void constrained_beam_init_kernel(BeamState s, 
     __syncthreads();
     bool stop = true;
     if (lane < beam) {
-        const size_t cb = cb0 + lane;
-        const int tok = w_tok[lane];
-        s.tokens[cb * T] = tok;
-        s.scores[cb] = w_key[lane];
-        s.seq[cb] = 1.0f;
-        stop = tok == stop_id;
-        s.stopped[cb] = stop;
-        s.next_tok[cb] = tok;
+        const size_t cb = (size_t)cap * beam + lane;
+        stop = beam_init_slot(s, cb, T, w_tok[lane], w_key[lane], stop_id);
         cs.state[cb] = w_cst[lane];
     }
-    const bool all = __all(stop);
-    if (lane == 0) {
-        s.done[cap] = all;
-        if (!all) atomicAdd(s.alive_count, 1);
-    }
+    beam_init_done(s, cap, stop);
 }
 
-// ---- step i >= 1: beam_step_kernel with the states, the banks and the round-robin.  Candidate c < beam * CON_LIST is
-// (b = c / CON_LIST, place p = c % CON_LIST); a lane holds candidates lane and lane + 64.
+// ---- step i >= 1: beam_state.h's stage and commit around the states, the banks and the round-robin.  Candidate
+// c < beam * CON_LIST is (b = c / CON_LIST, place p = c % CON_LIST); a lane holds candidates lane and lane + 64.
 __global__ __launch_bounds__(64) void constrained_beam_step_kernel(BeamState s, ConstraintState cs,
                                                                    const float *__restrict__ lse,
                                                                    const float *__restrict__ top_val,
-                                                                   const int *__restrict__ top_idx, int ncap, int beam,
-                                                                   int T, int ctx, int step, int pos_cur, int vocab,
-                                                                   int stop_id, const int *__restrict__ cmap) {
-    extern __shared__ int con_dyn[];                            // [beam][T] token history, then [beam][ctx] ancestor bytes
-    int *tok_old = con_dyn;
-    uint8_t *anc_old = reinterpret_cast<uint8_t *>(con_dyn + beam * T);
-    __shared__ int ph[CON_PHRASES * CON_LEN];
-    __shared__ int w_src[CON_BEAM_MAX], w_tok[CON_BEAM_MAX], w_cst[CON_BEAM_MAX], cst_old[CON_BEAM_MAX];
-    __shared__ float w_key[CON_BEAM_MAX], seq_new[CON_BEAM_MAX], sc_old[CON_BEAM_MAX];
-    __shared__ uint8_t st_old[CON_BEAM_MAX];
+                                                                   const int *__restrict__ top_idx, int beam, int T,
+                                                                   int ctx, int step, int pos_cur, int vocab, int stop_id,
+                                                                   const int *__restrict__ cmap) {
+    __shared__ struct : BeamStepLds {                           // + the phrases, the winners' and the old slots' states, the old scores
+        int ph[CON_PHRASES * CON_LEN];
+        int w_cst[BEAM_MAX], cst_old[BEAM_MAX];
+        float sc_old[BEAM_MAX];
+    } L;
     const int lane = threadIdx.x;
     const int cap = cmap ? cmap[blockIdx.x] : blockIdx.x;       // state (tokens, scores, anc ...) by original caption
     if (s.done[cap]) return;
     const size_t cb0 = (size_t)cap * beam;
     const size_t ab0 = (size_t)blockIdx.x * beam;               // lm_head outputs by (compact) activation row
-    // stage the state that is permuted in place
-    for (int i = lane; i < beam * step; i += 64) {
-        const int b = i / step, t = i - b * step;
-        tok_old[b * T + t] = s.tokens[(cb0 + b) * T + t];
-    }
-    for (int i = lane; i < beam * pos_cur; i += 64) {
-        const int b = i / pos_cur, p = i - b * pos_cur;
-        anc_old[b * ctx + p] = s.anc[(cb0 + b) * ctx + p];
-    }
-    if (lane < CON_PHRASES * CON_LEN) ph[lane] = cs.phrases[(size_t)cap * CON_PHRASES * CON_LEN + lane];
-    if (lane < CON_BEAM_MAX) {
+    beam_stage(s, L, cap, beam, T, ctx, step, pos_cur);
+    if (lane < CON_PHRASES * CON_LEN) L.ph[lane] = cs.phrases[(size_t)cap * CON_PHRASES * CON_LEN + lane];
+    if (lane < BEAM_MAX) {
         const int b = lane < beam ? lane : 0;
-        const bool stp = s.stopped[cb0 + b];
-        st_old[lane] = stp;
-        seq_new[lane] = s.seq[cb0 + b] + (stp ? 0.0f : 1.0f);
-        sc_old[lane] = s.scores[cb0 + b];
-        cst_old[lane] = cs.state[cb0 + b];
-        w_src[lane] = b; w_tok[lane] = 0; w_key[lane] = -INFINITY; w_cst[lane] = cst_old[lane];
+        L.sc_old[lane] = s.scores[cb0 + b];
+        L.cst_old[lane] = cs.state[cb0 + b];
+        L.w_src[lane] = b; L.w_tok[lane] = 0; L.w_key[lane] = -INFINITY; L.w_cst[lane] = L.cst_old[lane];
     }
     __syncthreads();
     // the two candidates of this lane
@@ -313,102 +230,32 @@ __global__ __launch_bounds__(64) void constrained_beam_step_kernel(BeamState s, 
         const int cb = c / CON_LIST, p = c - cb * CON_LIST;
         csrc[q] = cb;
         if (cb >= beam || p >= CON_SPECIAL + beam) continue;
-        if (st_old[cb]) {                                        // the single candidate: token 0, log-prob 0, the state stays
+        if (L.st_old[cb]) {                                        // the single candidate: token 0, log-prob 0, the state stays
             if (p != 0) continue;
-            key[q] = (sc_old[cb] + 0.0f) / seq_new[cb];
+            key[q] = (L.sc_old[cb] + 0.0f) / L.seq_new[cb];
             flat[q] = cb * vocab;
-            nst[q] = cst_old[cb];
+            nst[q] = L.cst_old[cb];
         } else {
             const size_t arow = ab0 + cb;
             const int tok = top_idx[arow * CON_LIST + p];
             if ((unsigned)tok >= (unsigned)vocab) continue;      // an unused place
             const float logp = top_val[arow * CON_LIST + p] - lse[arow];
-            const float k = (sc_old[cb] + logp) / seq_new[cb];
+            const float k = (L.sc_old[cb] + logp) / L.seq_new[cb];
             if (!(k > -INFINITY)) continue;
             key[q] = k;
             ctok[q] = tok;
             flat[q] = cb * vocab + tok;
-            nst[q] = con_adv(ph, cst_old[cb], tok);
+            nst[q] = con_adv(L.ph, L.cst_old[cb], tok);
         }
-        bank[q] = con_bank(ph, nst[q]);
+        bank[q] = con_bank(L.ph, nst[q]);
     }
     int won0, won1;
     con_round_robin(key[0], flat[0], bank[0], key[1], flat[1], bank[1], beam, won0, won1);
-    if (won0 >= 0) { w_src[won0] = csrc[0]; w_tok[won0] = ctok[0]; w_key[won0] = key[0]; w_cst[won0] = nst[0]; }
-    if (won1 >= 0) { w_src[won1] = csrc[1]; w_tok[won1] = ctok[1]; w_key[won1] = key[1]; w_cst[won1] = nst[1]; }
+    if (won0 >= 0) { L.w_src[won0] = csrc[0]; L.w_tok[won0] = ctok[0]; L.w_key[won0] = key[0]; L.w_cst[won0] = nst[0]; }
+    if (won1 >= 0) { L.w_src[won1] = csrc[1]; L.w_tok[won1] = ctok[1]; L.w_key[won1] = key[1]; L.w_cst[won1] = nst[1]; }
     __syncthreads();
-    // write the permuted state
-    bool stop = true;
-    if (lane < beam) {
-        const int src = w_src[lane], tok = w_tok[lane];
-        const float sq = seq_new[src];
-        s.seq[cb0 + lane] = sq;
-        s.scores[cb0 + lane] = w_key[lane] * sq;
-        stop = st_old[src] || tok == stop_id;
-        s.stopped[cb0 + lane] = stop;
-        s.next_tok[cb0 + lane] = tok;
-        s.tokens[(cb0 + lane) * T + step] = tok;
-        cs.state[cb0 + lane] = w_cst[lane];
-    }
-    for (int i = lane; i < beam * step; i += 64) {
-        const int b = i / step, t = i - b * step;
-        s.tokens[(cb0 + b) * T + t] = tok_old[w_src[b] * T + t];
-    }
-    for (int i = lane; i < beam * (pos_cur + 1); i += 64) {
-        const int b = i / (pos_cur + 1), p = i - b * (pos_cur + 1);
-        s.anc[(cb0 + b) * ctx + p] = (p < pos_cur) ? anc_old[w_src[b] * ctx + p] : (uint8_t)w_src[b];
-    }
-    if (s.kv_stat) {     // distinct slots the NEXT step's attention reads at each of its pos_cur + 1 cached positions
-        int cnt = 0;
-        for (int p = lane; p <= pos_cur; p += 64) {
-            unsigned seen = 0;
-            for (int b = 0; b < beam; ++b)
-                seen |= 1u << ((p < pos_cur) ? anc_old[w_src[b] * ctx + p] : (uint8_t)w_src[b]);
-            cnt += __popc(seen);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-        if (lane == 0) { s.kv_stat[2 * cap] += (unsigned)cnt; s.kv_stat[2 * cap + 1] += (unsigned)(pos_cur + 1); }
-    }
-    const bool all = __all(stop);
-    if (lane == 0) {
-        if (all) s.done[cap] = 1;
-        else atomicAdd(s.alive_count, 1);
-    }
-}
-
-// ---- the end: beam_finalize_kernel with the rows ordered by (phrases met, scores / seq, slot), and the met masks
-__global__ __launch_bounds__(64) void constrained_finalize_kernel(BeamState s, ConstraintState cs, int ncap, int beam, int T,
-                                                                  int *__restrict__ ids, int *__restrict__ lens,
-                                                                  float *__restrict__ scores, int *__restrict__ order,
-                                                                  int *__restrict__ met) {
-    __shared__ float f[CON_BEAM_MAX];
-    __shared__ int nmet[CON_BEAM_MAX], rank_of[CON_BEAM_MAX];
-    const int cap = blockIdx.x, lane = threadIdx.x;
-    const size_t cb0 = (size_t)cap * beam;
-    if (lane < beam) {
-        f[lane] = s.scores[cb0 + lane] / s.seq[cb0 + lane];
-        nmet[lane] = __popc(con_met(cs.state[cb0 + lane]));
-    }
-    __syncthreads();
-    if (lane < beam) {
-        int rank = 0;
-        for (int o = 0; o < beam; ++o) {
-            const bool ahead = nmet[o] != nmet[lane] ? nmet[o] > nmet[lane]
-                                                     : (f[o] > f[lane] || (f[o] == f[lane] && o < lane));
-            if (o != lane && ahead) ++rank;
-        }
-        rank_of[lane] = rank;
-        scores[cb0 + rank] = f[lane];
-        lens[cb0 + rank] = (int)s.seq[cb0 + lane];
-        if (order) order[cb0 + rank] = lane;
-        if (met) met[cb0 + rank] = con_met(cs.state[cb0 + lane]);
-    }
-    __syncthreads();
-    for (int i = lane; i < beam * T; i += 64) {
-        const int b = i / T, t = i - b * T;
-        ids[(cb0 + rank_of[b]) * T + t] = s.tokens[(cb0 + b) * T + t];
-    }
+    if (lane < beam) cs.state[cb0 + lane] = L.w_cst[lane];
+    beam_commit(s, L, cap, beam, T, ctx, step, pos_cur, stop_id);
 }
 
 }  // namespace
@@ -429,13 +276,12 @@ int launch_logits_select_forced(hipStream_t st, const float *logits, int ld, int
 }
 
 int launch_constrained_beam_init(hipStream_t st, const BeamState &s, const ConstraintState &cs, const float *lse,
-                                 const float *top_val, const int *top_idx, int ncap, int beam, int T, int ctx, int vocab,
-                                 int stop_id) {
-    CAPDEC_CHECK(beam >= 1 && beam <= CON_BEAM_MAX, "constrained beam: beam size must be in 1..8");
+                                 const float *top_val, const int *top_idx, int ncap, int beam, int T, int vocab, int stop_id) {
+    CAPDEC_CHECK(beam >= 1 && beam <= BEAM_MAX, "constrained beam: beam size must be in 1..8");
     CAPDEC_CHECK(cs.phrases && cs.state, "constrained beam: no constraint state");
     if (ncap <= 0) return 0;
-    hipLaunchKernelGGL(constrained_beam_init_kernel, dim3(ncap), dim3(64), 0, st, s, cs, lse, top_val, top_idx, ncap, beam, T,
-                       vocab, stop_id);
+    hipLaunchKernelGGL(constrained_beam_init_kernel, dim3(ncap), dim3(64), 0, st, s, cs, lse, top_val, top_idx, beam, T, vocab,
+                       stop_id);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -443,25 +289,11 @@ int launch_constrained_beam_init(hipStream_t st, const BeamState &s, const Const
 int launch_constrained_beam_step(hipStream_t st, const BeamState &s, const ConstraintState &cs, const float *lse,
                                  const float *top_val, const int *top_idx, int ncap, int beam, int T, int ctx, int step,
                                  int pos_cur, int vocab, int stop_id, const int *cmap) {
-    CAPDEC_CHECK(beam >= 1 && beam <= CON_BEAM_MAX, "constrained beam: beam size must be in 1..8");
-    CAPDEC_CHECK(T <= CON_T_MAX && ctx <= CON_CTX_MAX && step >= 1 && step < T && pos_cur >= 0 && pos_cur < ctx,
-                 "constrained beam: entry_length / context too long");
-    CAPDEC_CHECK((long long)beam * vocab < 0x7fffffffLL, "constrained beam: beam*vocab overflows int");
+    CAPDEC_TRY(beam_step_checks("constrained beam", beam, T, ctx, step, pos_cur, vocab));
     CAPDEC_CHECK(cs.phrases && cs.state, "constrained beam: no constraint state");
     if (ncap <= 0) return 0;
-    const size_t lds = (size_t)beam * T * sizeof(int) + (((size_t)beam * ctx + 3) & ~(size_t)3);
-    hipLaunchKernelGGL(constrained_beam_step_kernel, dim3(ncap), dim3(64), lds, st, s, cs, lse, top_val, top_idx, ncap, beam,
-                       T, ctx, step, pos_cur, vocab, stop_id, cmap);
-    CAPDEC_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_constrained_finalize(hipStream_t st, const BeamState &s, const ConstraintState &cs, int ncap, int beam, int T,
-                                int *ids, int *lens, float *scores, int *order, int *met) {
-    if (ncap <= 0) return 0;
-    CAPDEC_CHECK(beam >= 1 && beam <= CON_BEAM_MAX && cs.state, "constrained beam: no constraint state");
-    hipLaunchKernelGGL(constrained_finalize_kernel, dim3(ncap), dim3(64), 0, st, s, cs, ncap, beam, T, ids, lens, scores,
-                       order, met);
+    hipLaunchKernelGGL(constrained_beam_step_kernel, dim3(ncap), dim3(64), beam_step_lds(beam, T, ctx), st, s, cs, lse, top_val,
+                       top_idx, beam, T, ctx, step, pos_cur, vocab, stop_id, cmap);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

@@ -527,17 +527,17 @@ int decode_advance(capdec_ctx *c, const DecodeCall &a, const DecodeState &s, int
     const int *topi = c->topi.as<int>();
     if (a.greedy) return launch_greedy_step(c->stream, s.gs, topi, R, step, k, a.forced, topv, lse, a.stats);
     if (a.phrases) {                // (the lists are lm_head_rows_forced's: CON_LIST places per row)
-        if (step == 0) return launch_constrained_beam_init(c->stream, s.bs, s.cs, lse, topv, topi, R, beam, T, ctx, V, a.stop_id);
+        if (step == 0) return launch_constrained_beam_init(c->stream, s.bs, s.cs, lse, topv, topi, R, beam, T, V, a.stop_id);
         return launch_constrained_beam_step(c->stream, s.bs, s.cs, lse, topv, topi, R / beam, beam, T, ctx, step, P + step - 1, V,
                                             a.stop_id, cmap);
     }
     if (a.groups > 0) {
         if (step == 0)
-            return launch_group_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, a.groups, a.diversity, k, T, ctx, P, a.stop_id);
+            return launch_group_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, a.groups, a.diversity, k, T, a.stop_id);
         return launch_group_beam_step(c->stream, s.bs, lse, topv, topi, R / beam, beam, a.groups, a.diversity, k, T, ctx, step,
                                       P + step - 1, V, a.stop_id, cmap);
     }
-    if (step == 0) return launch_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, k, T, ctx, P, a.stop_id);
+    if (step == 0) return launch_beam_init(c->stream, s.bs, lse, topv, topi, R, beam, k, T, a.stop_id);
     return launch_beam_step(c->stream, s.bs, lse, topv, topi, R / beam, beam, k, T, ctx, step, P + step - 1, V, a.stop_id, cmap);
 }
 
@@ -641,8 +641,7 @@ static int decode_chunk(capdec_ctx *c, const float *prefix, int nc, const Decode
     }));
     if (!a.greedy) {
         ProfScope ps(c, F_SELECT);
-        if (a.phrases) CAPDEC_TRY(launch_constrained_finalize(c->stream, s.bs, s.cs, nc, beam, T, a.ids, a.lens, a.scores, a.order, a.met));
-        else CAPDEC_TRY(launch_beam_finalize(c->stream, s.bs, nc, beam, T, a.ids, a.lens, a.scores, a.order));
+        CAPDEC_TRY(launch_beam_finalize(c->stream, s.bs, nc, beam, T, a.ids, a.lens, a.scores, a.order, s.cs.state, a.met));  // (both null without phrases)
         if (a.glogp) CAPDEC_TRY(launch_group_beam_logp(c->stream, s.bs, nc, beam, a.order, a.glogp));
     }
     return 0;

@@ -1,6 +1,6 @@
-// Diverse (group) beam search (Vijayakumar et al. 2016) on the beam decode: the bookkeeping of select.hip's
+// Diverse (group) beam search (Vijayakumar et al. 2016) on the beam decode: the winner selection of select.hip's
 // beam_init_kernel / beam_step_kernel run per GROUP of Bg = beam / groups slots (capdec_decode_beam_groups; the contract:
-// include/capdec.h).  Slots g*Bg .. (g+1)*Bg-1 of a caption form group g; within a step the groups are processed in order,
+// include/capdec.h); staging, write-back and the limits are the shared ones of beam_state.h.  Slots g*Bg .. (g+1)*Bg-1 of a caption form group g; within a step the groups are processed in order,
 // and a token that h hypotheses of the earlier groups took AT THIS STEP (from sources that were not stopped) costs a row of
 // a later group lambda * h of its log-prob.  Everything around these two kernels is the plain beam's: the fused lm_head +
 // per-tile top-k with k = beam candidates per row, the ancestor-table attention (the ancestor bytes hold caption-level
@@ -16,11 +16,9 @@
 // Rounding: lp_pen = lp - lambda * (float)cnt is one multiplication and one subtraction, each rounded (no fma), so cnt = 0
 // leaves lp as it is and groups = 1 is the plain beam bit for bit.  `scores` accumulates the PENALISED values (the classic
 // algorithm); BeamState::logp carries the unpenalised sum next to it.  BeamState::diverge is not honoured here.
-#include "row_select.h"
+#include "beam_state.h"
 
 namespace capdec {
-
-constexpr int GRP_T_MAX = 1024, GRP_CTX_MAX = 1024, GRP_BEAM_MAX = 8;      // select.hip's limits
 
 __device__ __forceinline__ float penalised(float lp, float lambda, int cnt) {
     return __fsub_rn(lp, __fmul_rn(lambda, (float)cnt));
@@ -32,19 +30,18 @@ __device__ __forceinline__ float penalised(float lp, float lambda, int cnt) {
 // entries in order: beam_init_kernel
 __global__ __launch_bounds__(64) void group_beam_init_kernel(BeamState s, const float *__restrict__ lse,
                                                              const float *__restrict__ top_val,
-                                                             const int *__restrict__ top_idx, int ncap, int beam, int groups,
-                                                             float lambda, int k, int T, int ctx, int stop_id) {
-    __shared__ int w_tok[GRP_BEAM_MAX];
+                                                             const int *__restrict__ top_idx, int beam, int groups,
+                                                             float lambda, int k, int T, int stop_id) {
+    __shared__ int w_tok[BEAM_MAX];
     const int cap = blockIdx.x, lane = threadIdx.x;
     const int bg = beam / groups;
-    const size_t cb0 = (size_t)cap * beam;
     int tok = 0x7fffffff;
     float lp = -INFINITY;
     if (lane < k) {
         tok = top_idx[(size_t)cap * k + lane];
         lp = top_val[(size_t)cap * k + lane] - lse[cap];          // log softmax
     }
-    if (lane < GRP_BEAM_MAX) w_tok[lane] = -1;
+    if (lane < BEAM_MAX) w_tok[lane] = -1;
     __syncthreads();
     bool stop = true;
     for (int g = 0; g < groups; ++g) {
@@ -55,83 +52,50 @@ __global__ __launch_bounds__(64) void group_beam_init_kernel(BeamState s, const 
         for (int r = 0; r < bg; ++r) {
             float gv = key;
             int gi = idx;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(gv, o, 64);
-                const int oi = __shfl_xor(gi, o, 64);
-                if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-            }
+            wave_best(gv, gi);
             if (gi == idx && gv == key && idx != 0x7fffffff) {     // winner (list places are unique)
                 const int slot = g * bg + r;
-                const size_t cb = cb0 + slot;
                 w_tok[slot] = tok;
-                s.tokens[cb * T] = tok;
-                s.scores[cb] = key;
-                s.logp[cb] = lp;
-                s.seq[cb] = 1.0f;
-                s.stopped[cb] = tok == stop_id;
-                s.next_tok[cb] = tok;
-                if (tok != stop_id) stop = false;
+                s.logp[(size_t)cap * beam + slot] = lp;
+                if (!beam_init_slot(s, (size_t)cap * beam + slot, T, tok, key, stop_id)) stop = false;
                 key = -INFINITY; idx = 0x7fffffff;
             }
         }
         __syncthreads();                                           // the next group reads this group's w_tok
     }
-    const bool all = __all(stop);
-    if (lane == 0) {
-        s.done[cap] = all;
-        if (!all) atomicAdd(s.alive_count, 1);
-    }
+    beam_init_done(s, cap, stop);
 }
 
 int launch_group_beam_init(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
-                           int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int P, int stop_id) {
-    CAPDEC_CHECK(beam >= 1 && beam <= GRP_BEAM_MAX && k >= beam && k <= 64, "beam groups: beam size must be in 1..8");
+                           int ncap, int beam, int groups, float diversity, int k, int T, int stop_id) {
+    CAPDEC_CHECK(beam >= 1 && beam <= BEAM_MAX && k >= beam && k <= 64, "beam groups: beam size must be in 1..8");
     CAPDEC_CHECK(groups >= 1 && groups <= beam && beam % groups == 0, "beam groups: groups must divide the beam size");
     CAPDEC_CHECK(s.logp, "beam groups: no log-prob accumulator");
     if (ncap <= 0) return 0;
-    hipLaunchKernelGGL(group_beam_init_kernel, dim3(ncap), dim3(64), 0, st, s, lse, top_val, top_idx, ncap, beam, groups,
-                       diversity, k, T, ctx, stop_id);
+    hipLaunchKernelGGL(group_beam_init_kernel, dim3(ncap), dim3(64), 0, st, s, lse, top_val, top_idx, beam, groups, diversity,
+                       k, T, stop_id);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
 
-// ---- step i >= 1: beam_step_kernel with the group loop.  lane c < beam*k is candidate (b = c / k, j = c % k) and belongs
-// to group b / Bg; w_src / w_tok of the slots already filled this step are the (token, live) table of the penalty.  B
-// winner rounds per step, as in the plain beam: Bg per group, in which only that group's lanes compete.
+// ---- step i >= 1: beam_state.h's stage and commit around the group loop.  lane c < beam*k is candidate (b = c / k,
+// j = c % k) and belongs to group b / Bg; w_src / w_tok of the slots already filled this step are the (token, live) table of
+// the penalty.  B winner rounds per step, as in the plain beam: Bg per group, in which only that group's lanes compete.
 __global__ __launch_bounds__(64) void group_beam_step_kernel(BeamState s, const float *__restrict__ lse,
                                                              const float *__restrict__ top_val,
-                                                             const int *__restrict__ top_idx, int ncap, int beam, int groups,
+                                                             const int *__restrict__ top_idx, int beam, int groups,
                                                              float lambda, int k, int T, int ctx, int step, int pos_cur,
                                                              int vocab, int stop_id, const int *__restrict__ cmap) {
-    extern __shared__ int grp_dyn[];                            // [beam][T] token history, then [beam][ctx] ancestor bytes
-    int *tok_old = grp_dyn;
-    uint8_t *anc_old = reinterpret_cast<uint8_t *>(grp_dyn + beam * T);
-    __shared__ int w_src[GRP_BEAM_MAX], w_tok[GRP_BEAM_MAX];
-    __shared__ float w_key[GRP_BEAM_MAX], w_lp[GRP_BEAM_MAX], seq_new[GRP_BEAM_MAX], lp_old[GRP_BEAM_MAX];
-    __shared__ uint8_t st_old[GRP_BEAM_MAX];
+    __shared__ struct : BeamStepLds { float w_lp[BEAM_MAX], lp_old[BEAM_MAX]; } L;     // + the winners' and the old slots' log-probs
     const int lane = threadIdx.x;
     const int cap = cmap ? cmap[blockIdx.x] : blockIdx.x;       // state (tokens, scores, anc ...) by original caption
     if (s.done[cap]) return;
     const int bg = beam / groups;
     const size_t cb0 = (size_t)cap * beam;
     const size_t ab0 = (size_t)blockIdx.x * beam;               // lm_head outputs by (compact) activation row
-    // stage the state that is permuted in place
-    for (int i = lane; i < beam * step; i += 64) {
-        const int b = i / step, t = i - b * step;
-        tok_old[b * T + t] = s.tokens[(cb0 + b) * T + t];
-    }
-    for (int i = lane; i < beam * pos_cur; i += 64) {
-        const int b = i / pos_cur, p = i - b * pos_cur;
-        anc_old[b * ctx + p] = s.anc[(cb0 + b) * ctx + p];
-    }
-    if (lane < beam) {
-        const bool stp = s.stopped[cb0 + lane];
-        st_old[lane] = stp;
-        seq_new[lane] = s.seq[cb0 + lane] + (stp ? 0.0f : 1.0f);
-        lp_old[lane] = s.logp[cb0 + lane];
-    }
-    if (lane < GRP_BEAM_MAX) { w_src[lane] = lane < beam ? lane : 0; w_tok[lane] = 0; w_key[lane] = -INFINITY; w_lp[lane] = 0.0f; }
+    beam_stage(s, L, cap, beam, T, ctx, step, pos_cur);
+    if (lane < beam) L.lp_old[lane] = s.logp[cb0 + lane];
+    if (lane < BEAM_MAX) { L.w_src[lane] = lane < beam ? lane : 0; L.w_tok[lane] = 0; L.w_key[lane] = -INFINITY; L.w_lp[lane] = 0.0f; }
     __syncthreads();
     // candidate of this lane
     int ctok = 0, cb = 0, j = 0;
@@ -141,7 +105,7 @@ __global__ __launch_bounds__(64) void group_beam_step_kernel(BeamState s, const 
         cb = lane / k;
         j = lane - cb * k;
         sc = s.scores[cb0 + cb];
-        if (!st_old[cb]) {
+        if (!L.st_old[cb]) {
             ctok = top_idx[(ab0 + cb) * k + j];
             lp = top_val[(ab0 + cb) * k + j] - lse[ab0 + cb];
         }
@@ -151,85 +115,41 @@ __global__ __launch_bounds__(64) void group_beam_step_kernel(BeamState s, const 
         float key = -INFINITY;
         int flat = 0x7fffffff;
         if (cand && grp == g) {
-            if (st_old[cb]) {
-                if (j == 0) key = (sc + 0.0f) / seq_new[cb];       // the single candidate: neither penalised nor counted
+            if (L.st_old[cb]) {
+                if (j == 0) key = (sc + 0.0f) / L.seq_new[cb];     // the single candidate: neither penalised nor counted
             } else {
                 int cnt = 0;
-                for (int r = 0; r < g * bg; ++r) cnt += (w_tok[r] == ctok) & !st_old[w_src[r]];
-                key = (sc + penalised(lp, lambda, cnt)) / seq_new[cb];
+                for (int r = 0; r < g * bg; ++r) cnt += (L.w_tok[r] == ctok) & !L.st_old[L.w_src[r]];
+                key = (sc + penalised(lp, lambda, cnt)) / L.seq_new[cb];
             }
-            if (key > -INFINITY || (st_old[cb] && j == 0)) flat = cb * vocab + ctok;
+            if (key > -INFINITY || (L.st_old[cb] && j == 0)) flat = cb * vocab + ctok;
         }
         for (int r = 0; r < bg; ++r) {
             float gv = key;
             int gi = flat;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(gv, o, 64);
-                const int oi = __shfl_xor(gi, o, 64);
-                if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-            }
+            wave_best(gv, gi);
             if (gi == flat && gv == key && flat != 0x7fffffff) {   // winner (flat indices are unique)
                 const int slot = g * bg + r;
-                w_src[slot] = cb; w_tok[slot] = ctok; w_key[slot] = key; w_lp[slot] = st_old[cb] ? 0.0f : lp;
+                L.w_src[slot] = cb; L.w_tok[slot] = ctok; L.w_key[slot] = key; L.w_lp[slot] = L.st_old[cb] ? 0.0f : lp;
                 key = -INFINITY; flat = 0x7fffffff;
             }
         }
-        __syncthreads();                                           // the next group (and the write phase) reads the winners
+        __syncthreads();                                           // the next group (and the commit) reads the winners
     }
-    // write the permuted state
-    bool stop = true;
-    if (lane < beam) {
-        const int src = w_src[lane], tok = w_tok[lane];
-        const float sq = seq_new[src];
-        s.seq[cb0 + lane] = sq;
-        s.scores[cb0 + lane] = w_key[lane] * sq;
-        s.logp[cb0 + lane] = lp_old[src] + w_lp[lane];
-        stop = st_old[src] || tok == stop_id;
-        s.stopped[cb0 + lane] = stop;
-        s.next_tok[cb0 + lane] = tok;
-        s.tokens[(cb0 + lane) * T + step] = tok;
-    }
-    for (int i = lane; i < beam * step; i += 64) {
-        const int b = i / step, t = i - b * step;
-        s.tokens[(cb0 + b) * T + t] = tok_old[w_src[b] * T + t];
-    }
-    for (int i = lane; i < beam * (pos_cur + 1); i += 64) {
-        const int b = i / (pos_cur + 1), p = i - b * (pos_cur + 1);
-        s.anc[(cb0 + b) * ctx + p] = (p < pos_cur) ? anc_old[w_src[b] * ctx + p] : (uint8_t)w_src[b];
-    }
-    if (s.kv_stat) {     // distinct slots the NEXT step's attention reads at each of its pos_cur + 1 cached positions
-        int cnt = 0;
-        for (int p = lane; p <= pos_cur; p += 64) {
-            unsigned seen = 0;
-            for (int b = 0; b < beam; ++b)
-                seen |= 1u << ((p < pos_cur) ? anc_old[w_src[b] * ctx + p] : (uint8_t)w_src[b]);
-            cnt += __popc(seen);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-        if (lane == 0) { s.kv_stat[2 * cap] += (unsigned)cnt; s.kv_stat[2 * cap + 1] += (unsigned)(pos_cur + 1); }
-    }
-    const bool all = __all(stop);
-    if (lane == 0) {
-        if (all) s.done[cap] = 1;
-        else atomicAdd(s.alive_count, 1);
-    }
+    if (lane < beam) s.logp[cb0 + lane] = L.lp_old[L.w_src[lane]] + L.w_lp[lane];
+    beam_commit(s, L, cap, beam, T, ctx, step, pos_cur, stop_id);
 }
 
 int launch_group_beam_step(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
                            int ncap, int beam, int groups, float diversity, int k, int T, int ctx, int step, int pos_cur,
                            int vocab, int stop_id, const int *cmap) {
-    CAPDEC_CHECK(beam >= 1 && beam <= GRP_BEAM_MAX && beam * k <= 64, "beam groups: beam*k must fit one wavefront");
+    CAPDEC_TRY(beam_step_checks("beam groups", beam, T, ctx, step, pos_cur, vocab));
+    CAPDEC_CHECK(beam * k <= 64, "beam groups: beam*k must fit one wavefront");
     CAPDEC_CHECK(groups >= 1 && groups <= beam && beam % groups == 0, "beam groups: groups must divide the beam size");
-    CAPDEC_CHECK(T <= GRP_T_MAX && ctx <= GRP_CTX_MAX && step >= 1 && step < T && pos_cur >= 0 && pos_cur < ctx,
-                 "beam groups: entry_length / context too long");
-    CAPDEC_CHECK((long long)beam * vocab < 0x7fffffffLL, "beam groups: beam*vocab overflows int");
     CAPDEC_CHECK(s.logp, "beam groups: no log-prob accumulator");
     if (ncap <= 0) return 0;
-    const size_t lds = (size_t)beam * T * sizeof(int) + (((size_t)beam * ctx + 3) & ~(size_t)3);
-    hipLaunchKernelGGL(group_beam_step_kernel, dim3(ncap), dim3(64), lds, st, s, lse, top_val, top_idx, ncap, beam, groups,
-                       diversity, k, T, ctx, step, pos_cur, vocab, stop_id, cmap);
+    hipLaunchKernelGGL(group_beam_step_kernel, dim3(ncap), dim3(64), beam_step_lds(beam, T, ctx), st, s, lse, top_val, top_idx,
+                       beam, groups, diversity, k, T, ctx, step, pos_cur, vocab, stop_id, cmap);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

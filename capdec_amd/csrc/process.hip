@@ -11,7 +11,8 @@
 //   5. top_k (sampling only): j stays iff fewer than top_k entries are strictly greater than l[j]; the rest become -inf
 //
 // logits_process_kernel   steps 1-4 in place, one workgroup per row
-// logits_select_kernel<K> logsumexp and the K best (value, column) pairs of a row in ONE pass over it -- exactly what
+// logits_select_kernel<K> logsumexp and the K best (value, column) pairs of a row in ONE pass over it (row_select.h's
+//                         logits_row_pass with nothing banned and nothing excluded) -- exactly what
 //                         launch_topk_merge (select.hip) leaves in lse / top_val / top_idx: values scaled by inv_temp, ties
 //                         to the smaller column -- so the greedy / beam step kernels run unchanged behind it
 // logits_topk_kernel      step 5 in place: the top_k-th largest value by a count-based bisection over the order-preserving
@@ -28,7 +29,7 @@ namespace capdec {
 
 namespace {
 
-constexpr int PRC_THREADS = 256, PRC_WAVES = PRC_THREADS / WAVE;
+constexpr int PRC_THREADS = 256;
 constexpr int PRC_HIST_MAX = 1024;      // entry_length <= 1024 (decode_call_checks)
 constexpr int TOPK_THREADS = 1024, TOPK_WAVES = TOPK_THREADS / WAVE;
 
@@ -99,56 +100,8 @@ template <int K>
 __global__ __launch_bounds__(PRC_THREADS) void logits_select_kernel(const float *__restrict__ logits, int ld, int V,
                                                                     float inv_temp, float *__restrict__ lse,
                                                                     float *__restrict__ top_val, int *__restrict__ top_idx) {
-    __shared__ float wm[PRC_WAVES], ws[PRC_WAVES];
-    __shared__ float cv[PRC_WAVES * K];
-    __shared__ int ci[PRC_WAVES * K];
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const float *x = logits + (size_t)r * ld;
-    float m = -INFINITY, s = 0.f;
-    LaneTopk<K> best;
-    best.clear();
-    const int V4 = V & ~3;
-    for (int j = tid * 4; j < V4; j += PRC_THREADS * 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(x + j);
-        const float v0 = q.x * inv_temp, v1 = q.y * inv_temp, v2 = q.z * inv_temp, v3 = q.w * inv_temp;
-        online_rescale(m, s, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
-        if (m > -INFINITY) s += ((expf(v0 - m) + expf(v1 - m)) + expf(v2 - m)) + expf(v3 - m);
-        best.push(v0, j);
-        best.push(v1, j + 1);
-        best.push(v2, j + 2);
-        best.push(v3, j + 3);
-    }
-    for (int j = V4 + tid; j < V; j += PRC_THREADS) {
-        const float v = x[j] * inv_temp;
-        online_rescale(m, s, v);
-        if (m > -INFINITY) s += expf(v - m);
-        best.push(v, j);
-    }
-    // logsumexp: lanes -> wavefront -> workgroup, each in a fixed order
-    const float M = wave_max(m);
-    const float t = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
-    if (lane == 0) { wm[wave] = M; ws[wave] = t; }
-    // the wavefront's K best: K rounds of an arg-max butterfly, the lane that held the winner pops it
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        float gv;
-        int gi;
-        best.pop_best(gv, gi);
-        if (lane == 0) { cv[wave * K + q] = gv; ci[wave * K + q] = gi; }
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    float Mb = wm[0];
-#pragma unroll
-    for (int w = 1; w < PRC_WAVES; ++w) Mb = fmaxf(Mb, wm[w]);
-    float S = 0.f;
-#pragma unroll
-    for (int w = 0; w < PRC_WAVES; ++w) S += wm[w] > -INFINITY ? ws[w] * expf(wm[w] - Mb) : 0.f;
-    lse[r] = Mb + logf(S);
-    best.clear();
-    for (int q = 0; q < PRC_WAVES * K; ++q) best.push(cv[q], ci[q]);
-#pragma unroll
-    for (int j = 0; j < K; ++j) { top_val[(size_t)r * K + j] = best.v[j]; top_idx[(size_t)r * K + j] = best.i[j]; }
+    const size_t r = blockIdx.x;
+    logits_row_pass<K, PRC_THREADS>(logits + r * ld, V, inv_temp, RowUnfiltered(), lse + r, top_val + r * K, top_idx + r * K);
 }
 
 // tau = the largest key with at least top_k keys >= tau: the top_k-th largest value, built bit by bit from the top (32

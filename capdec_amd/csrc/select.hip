@@ -3,14 +3,11 @@
 // per-caption state lives in a few hundred bytes, so these kernels are launch-latency sized).
 // The tie rule, the lane lists, the winner-pops round and the tile logsumexp come from row_select.h; the three merge
 // kernels are entry points over merge_tile_lists.
-#include "row_select.h"
+// The beam kernels are beam_state.h's stage / commit around the plain candidate tournament; beam_finalize_kernel also ends
+// the constrained beam.
+#include "beam_state.h"
 
 namespace capdec {
-
-constexpr int SEL_T_MAX = 1024;    // max entry_length
-constexpr int SEL_CTX_MAX = 1024;  // max context (prefix + generated): GPT-2's n_positions, the reference's only limit
-                                   // (the beam step stages beam x (T ints + ctx bytes) of state in dynamic LDS: <= 40 KB)
-constexpr int SEL_BEAM_MAX = 8;
 
 // ---- merge: one wavefront per row; the row's KOUT best of its tiles' KIN-entry lists [ntiles, KIN] -> out_val / out_idx
 // [KOUT].  Returns, for the callers that flag rows, the row's KOUT-th winner and the best LAST-kept candidate among this
@@ -364,34 +361,22 @@ int launch_greedy_step(hipStream_t st, const GreedyState &s, const int *top_idx,
 // one wavefront per caption; top_val/top_idx/lse are per CAPTION row here (prefill last position)
 __global__ __launch_bounds__(64) void beam_init_kernel(BeamState s, const float *__restrict__ lse,
                                                        const float *__restrict__ top_val,
-                                                       const int *__restrict__ top_idx, int ncap, int beam, int k,
-                                                       int T, int ctx, int stop_id) {
+                                                       const int *__restrict__ top_idx, int beam, int k, int T,
+                                                       int stop_id) {
     const int cap = blockIdx.x, b = threadIdx.x;
     bool stop = true;
     if (b < beam) {
-        const int tok = top_idx[(size_t)cap * k + b];
         const float logp = top_val[(size_t)cap * k + b] - lse[cap];   // log softmax
-        const size_t cb = (size_t)cap * beam + b;
-        s.tokens[cb * T] = tok;
-        s.scores[cb] = logp;
-        s.seq[cb] = 1.0f;
-        stop = tok == stop_id;
-        s.stopped[cb] = stop;
-        s.next_tok[cb] = tok;
+        stop = beam_init_slot(s, (size_t)cap * beam + b, T, top_idx[(size_t)cap * k + b], logp, stop_id);
     }
-    const bool all = __all(stop);
-    if (b == 0) {
-        s.done[cap] = all;
-        if (!all) atomicAdd(s.alive_count, 1);
-    }
+    beam_init_done(s, cap, stop);
 }
 
 int launch_beam_init(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
-                     int ncap, int beam, int k, int T, int ctx, int P, int stop_id) {
-    CAPDEC_CHECK(beam >= 1 && beam <= SEL_BEAM_MAX && k >= beam, "beam: beam size must be in 1..8");
+                     int ncap, int beam, int k, int T, int stop_id) {
+    CAPDEC_CHECK(beam >= 1 && beam <= BEAM_MAX && k >= beam, "beam: beam size must be in 1..8");
     if (ncap <= 0) return 0;
-    hipLaunchKernelGGL(beam_init_kernel, dim3(ncap), dim3(64), 0, st, s, lse, top_val, top_idx, ncap, beam, k, T, ctx,
-                       stop_id);
+    hipLaunchKernelGGL(beam_init_kernel, dim3(ncap), dim3(64), 0, st, s, lse, top_val, top_idx, beam, k, T, stop_id);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
@@ -402,34 +387,16 @@ int launch_beam_init(hipStream_t st, const BeamState &s, const float *lse, const
 //   flattened [beam * V]; scores = avg * seq[src].
 __global__ __launch_bounds__(64) void beam_step_kernel(BeamState s, const float *__restrict__ lse,
                                                        const float *__restrict__ top_val,
-                                                       const int *__restrict__ top_idx, int ncap, int beam, int k,
-                                                       int T, int ctx, int step, int pos_cur, int vocab,
-                                                       int stop_id, const int *__restrict__ cmap) {
-    extern __shared__ int sel_dyn[];                            // [beam][T] token history, then [beam][ctx] ancestor bytes
-    int *tok_old = sel_dyn;
-    uint8_t *anc_old = reinterpret_cast<uint8_t *>(sel_dyn + beam * T);
-    __shared__ int w_src[SEL_BEAM_MAX], w_tok[SEL_BEAM_MAX];
-    __shared__ float w_key[SEL_BEAM_MAX], seq_new[SEL_BEAM_MAX];
-    __shared__ uint8_t st_old[SEL_BEAM_MAX];
+                                                       const int *__restrict__ top_idx, int beam, int k, int T, int ctx,
+                                                       int step, int pos_cur, int vocab, int stop_id,
+                                                       const int *__restrict__ cmap) {
+    __shared__ BeamStepLds L;
     const int lane = threadIdx.x;
     const int cap = cmap ? cmap[blockIdx.x] : blockIdx.x;       // state (tokens, scores, anc ...) by original caption
     if (s.done[cap]) return;
     const size_t cb0 = (size_t)cap * beam;
     const size_t ab0 = (size_t)blockIdx.x * beam;               // lm_head outputs by (compact) activation row
-    // stage the state that is permuted in place
-    for (int i = lane; i < beam * step; i += 64) {
-        const int b = i / step, t = i - b * step;
-        tok_old[b * T + t] = s.tokens[(cb0 + b) * T + t];
-    }
-    for (int i = lane; i < beam * pos_cur; i += 64) {
-        const int b = i / pos_cur, p = i - b * pos_cur;
-        anc_old[b * ctx + p] = s.anc[(cb0 + b) * ctx + p];
-    }
-    if (lane < beam) {
-        const bool stp = s.stopped[cb0 + lane];
-        st_old[lane] = stp;
-        seq_new[lane] = s.seq[cb0 + lane] + (stp ? 0.0f : 1.0f);
-    }
+    beam_stage(s, L, cap, beam, T, ctx, step, pos_cur);
     __syncthreads();
     // candidate of this lane
     float key = -INFINITY;
@@ -438,102 +405,73 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamState s, const float 
         cb = lane / k;
         const int j = lane - cb * k;
         const size_t row = cb0 + cb, arow = ab0 + cb;
-        if (st_old[cb]) {
-            if (j == 0) { ctok = 0; key = (s.scores[row] + 0.0f) / seq_new[cb]; }
+        if (L.st_old[cb]) {
+            if (j == 0) { ctok = 0; key = (s.scores[row] + 0.0f) / L.seq_new[cb]; }
         } else {
             ctok = top_idx[arow * k + j];
             const float logp = top_val[arow * k + j] - lse[arow];
-            key = (s.scores[row] + logp) / seq_new[cb];
+            key = (s.scores[row] + logp) / L.seq_new[cb];
         }
-        if (key > -INFINITY || (st_old[cb] && j == 0)) flat = cb * vocab + ctok;
+        if (key > -INFINITY || (L.st_old[cb] && j == 0)) flat = cb * vocab + ctok;
         if (s.diverge && j != 0) { key = -INFINITY; flat = 0x7fffffff; }      // measurement only: each beam keeps its own lineage
     }
     for (int r = 0; r < beam; ++r) {
         float gv = key;
         int gi = flat;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(gv, o, 64);
-            const int oi = __shfl_xor(gi, o, 64);
-            if (better(ov, oi, gv, gi)) { gv = ov; gi = oi; }
-        }
+        wave_best(gv, gi);
         if (gi == flat && gv == key && flat != 0x7fffffff) {   // winner (flat indices are unique)
-            w_src[r] = cb; w_tok[r] = ctok; w_key[r] = key;
+            L.w_src[r] = cb; L.w_tok[r] = ctok; L.w_key[r] = key;
             key = -INFINITY; flat = 0x7fffffff;
         }
     }
     __syncthreads();
-    // write the permuted state
-    bool stop = true;
-    if (lane < beam) {
-        const int src = w_src[lane], tok = w_tok[lane];
-        const float sq = seq_new[src];
-        s.seq[cb0 + lane] = sq;
-        s.scores[cb0 + lane] = w_key[lane] * sq;
-        stop = st_old[src] || tok == stop_id;
-        s.stopped[cb0 + lane] = stop;
-        s.next_tok[cb0 + lane] = tok;
-        s.tokens[(cb0 + lane) * T + step] = tok;
-    }
-    for (int i = lane; i < beam * step; i += 64) {
-        const int b = i / step, t = i - b * step;
-        s.tokens[(cb0 + b) * T + t] = tok_old[w_src[b] * T + t];
-    }
-    for (int i = lane; i < beam * (pos_cur + 1); i += 64) {
-        const int b = i / (pos_cur + 1), p = i - b * (pos_cur + 1);
-        s.anc[(cb0 + b) * ctx + p] = (p < pos_cur) ? anc_old[w_src[b] * ctx + p] : (uint8_t)w_src[b];
-    }
-    if (s.kv_stat) {     // distinct slots the NEXT step's attention reads at each of its pos_cur + 1 cached positions
-        int cnt = 0;
-        for (int p = lane; p <= pos_cur; p += 64) {
-            unsigned seen = 0;
-            for (int b = 0; b < beam; ++b)
-                seen |= 1u << ((p < pos_cur) ? anc_old[w_src[b] * ctx + p] : (uint8_t)w_src[b]);
-            cnt += __popc(seen);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-        if (lane == 0) { s.kv_stat[2 * cap] += (unsigned)cnt; s.kv_stat[2 * cap + 1] += (unsigned)(pos_cur + 1); }
-    }
-    const bool all = __all(stop);
-    if (lane == 0) {
-        if (all) s.done[cap] = 1;
-        else atomicAdd(s.alive_count, 1);
-    }
+    beam_commit(s, L, cap, beam, T, ctx, step, pos_cur, stop_id);
 }
 
 int launch_beam_step(hipStream_t st, const BeamState &s, const float *lse, const float *top_val, const int *top_idx,
                      int ncap, int beam, int k, int T, int ctx, int step, int pos_cur, int vocab, int stop_id,
                      const int *cmap) {
+    CAPDEC_TRY(beam_step_checks("beam", beam, T, ctx, step, pos_cur, vocab));
     CAPDEC_CHECK(beam * k <= 64, "beam: beam*k must fit one wavefront");
-    CAPDEC_CHECK(T <= SEL_T_MAX && ctx <= SEL_CTX_MAX, "beam: entry_length / context too long");
-    CAPDEC_CHECK((long long)beam * vocab < 0x7fffffffLL, "beam: beam*vocab overflows int");
     if (ncap <= 0) return 0;
-    const size_t lds = (size_t)beam * T * sizeof(int) + (((size_t)beam * ctx + 3) & ~(size_t)3);
-    hipLaunchKernelGGL(beam_step_kernel, dim3(ncap), dim3(64), lds, st, s, lse, top_val, top_idx, ncap, beam, k, T, ctx,
-                       step, pos_cur, vocab, stop_id, cmap);
+    hipLaunchKernelGGL(beam_step_kernel, dim3(ncap), dim3(64), beam_step_lds(beam, T, ctx), st, s, lse, top_val, top_idx,
+                       beam, k, T, ctx, step, pos_cur, vocab, stop_id, cmap);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }
 
-// ---- end of generate_beam: scores /= seq_lengths; order = argsort(desc) (reference :110-114)
-__global__ __launch_bounds__(64) void beam_finalize_kernel(BeamState s, int ncap, int beam, int T,
+// ---- end of generate_beam: scores /= seq_lengths; order = argsort(desc) (reference :110-114).  With a constraint state
+// (con_state [ncap, beam], constrained.hip) the rows are ordered by (phrases met, scores / seq, slot) and met [ncap, beam]
+// (may be nullptr) receives their met masks; without one every slot has met nothing and the order is (score desc, slot asc).
+// (the phrase counts travel by shuffle, not through LDS)
+__global__ __launch_bounds__(64) void beam_finalize_kernel(BeamState s, const int *__restrict__ con_state, int beam, int T,
                                                            int *__restrict__ ids, int *__restrict__ lens,
-                                                           float *__restrict__ scores, int *__restrict__ order) {
-    __shared__ float f[SEL_BEAM_MAX];
-    __shared__ int rank_of[SEL_BEAM_MAX];
+                                                           float *__restrict__ scores, int *__restrict__ order,
+                                                           int *__restrict__ met) {
+    __shared__ float f[BEAM_MAX];
+    __shared__ int rank_of[BEAM_MAX];
     const int cap = blockIdx.x, lane = threadIdx.x;
     const size_t cb0 = (size_t)cap * beam;
-    if (lane < beam) f[lane] = s.scores[cb0 + lane] / s.seq[cb0 + lane];
-    __syncthreads();
+    float fl = 0.f;
+    int cst = 0;
     if (lane < beam) {
-        int rank = 0;
-        for (int o = 0; o < beam; ++o)
-            if (f[o] > f[lane] || (f[o] == f[lane] && o < lane)) ++rank;
+        f[lane] = fl = s.scores[cb0 + lane] / s.seq[cb0 + lane];
+        if (con_state) cst = con_state[cb0 + lane];
+    }
+    __syncthreads();
+    const int nmet = __popc(con_met(cst));
+    int rank = 0;
+    for (int o = 0; o < beam; ++o) {
+        const int no = __shfl(nmet, o, 64);
+        const bool ahead = no != nmet ? no > nmet : (f[o] > fl || (f[o] == fl && o < lane));
+        if (o != lane && ahead) ++rank;
+    }
+    if (lane < beam) {
         rank_of[lane] = rank;
-        scores[cb0 + rank] = f[lane];
+        scores[cb0 + rank] = fl;
         lens[cb0 + rank] = (int)s.seq[cb0 + lane];
         if (order) order[cb0 + rank] = lane;
+        if (met) met[cb0 + rank] = con_met(cst);
     }
     __syncthreads();
     for (int i = lane; i < beam * T; i += 64) {
@@ -543,9 +481,10 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(BeamState s, int ncap
 }
 
 int launch_beam_finalize(hipStream_t st, const BeamState &s, int ncap, int beam, int T, int *ids, int *lens,
-                         float *scores, int *order) {
+                         float *scores, int *order, const int *con_state, int *met) {
     if (ncap <= 0) return 0;
-    hipLaunchKernelGGL(beam_finalize_kernel, dim3(ncap), dim3(64), 0, st, s, ncap, beam, T, ids, lens, scores, order);
+    CAPDEC_CHECK(beam >= 1 && beam <= BEAM_MAX && (con_state || !met), "beam finalize: beam size must be in 1..8");
+    hipLaunchKernelGGL(beam_finalize_kernel, dim3(ncap), dim3(64), 0, st, s, con_state, beam, T, ids, lens, scores, order, met);
     CAPDEC_HIP(hipGetLastError());
     return 0;
 }

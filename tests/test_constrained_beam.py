@@ -333,24 +333,33 @@ def test_vs_definition(eng, name):
 @pytest.mark.parametrize("n,B,T", [(16, 5, T12), (4, 8, 67)])
 def test_no_phrases_is_the_plain_beam_bit_for_bit(eng, n, B, T):
     """no phrases: ids, lens, scores and order are Engine.decode_beam's on the same route (an all-zero logit_bias sends it
-    through the materialised logits), array_equal; met is zero; once more with processors set"""
+    through the materialised logits), array_equal, and so is the distinct-K/V-slot statistic (kv_slots_per_position, in
+    [1, B]); met is zero; once more with processors set (logits_select_kernel against logits_select_forced_kernel on the
+    same processed logits)"""
     dims, sd, prefix, stop = TD._tiny_case()
     eng.load_gpt2(sd, n_head=dims.n_head)
     none = np.full((n, 4, 4), -1, dtype=np.int32)
     zero = np.zeros(dims.vocab, dtype=np.float32)
+    kv_of = lambda: eng.decode_counters()["kv_slots_per_position"]
     want = _np(eng.decode_beam(prefix[:n], stop, B, T, logit_bias=zero))
+    kv_want = kv_of()
     for kw in (dict(logit_bias=zero), {}):                     # (without any processor the call takes the same route)
         got = _np(eng.decode_beam_constrained(prefix[:n], none, stop, B, T, **kw))
+        kv = kv_of()
         for a, b in zip(got[:4], want):
             np.testing.assert_array_equal(a, b)
         assert not got[4].any()
+        assert kv == kv_want and 1.0 <= kv <= B, (kv, kv_want)
     if T == T12:
         kw = dict(PD.Proc(**PROC).kw(), logit_bias=zero)
         want = _np(eng.decode_beam(prefix[:n], stop, B, T, **kw))
+        kv_want = kv_of()
         got = _np(eng.decode_beam_constrained(prefix[:n], none, stop, B, T, **kw))
+        kv = kv_of()
         for a, b in zip(got[:4], want):
             np.testing.assert_array_equal(a, b)
         assert not got[4].any()
+        assert kv == kv_want and 1.0 <= kv <= B, (kv, kv_want)
 
 
 @pytest.mark.gpu

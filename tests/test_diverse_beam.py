@@ -287,8 +287,8 @@ def _check_structure(got, B, G, T, stop):
 @pytest.mark.parametrize("n,B,T", [(16, 5, T12), (4, 8, 67)])
 def test_one_group_is_the_plain_beam_bit_for_bit(eng, n, B, T):
     """G = 1: ids, lens, scores and order are Engine.decode_beam's, array_equal, for lambda 0 and 0.7 (beam 8 at T 67: the
-    long history through the LDS staging); logp is finite and, nothing being penalised, the score's sum; once more with
-    processors set"""
+    long history through the LDS staging), and so is the distinct-K/V-slot statistic (kv_slots_per_position, in [1, B]);
+    logp is finite and, nothing being penalised, the score's sum; once more with processors set"""
     dims, sd, prefix, stop = _tiny_case()
     eng.load_gpt2(sd, n_head=dims.n_head)
     runs = [({}, 0.0), ({}, 0.7)]
@@ -296,9 +296,12 @@ def test_one_group_is_the_plain_beam_bit_for_bit(eng, n, B, T):
         runs.append((PD.Proc(**PROC).kw(), 0.7))
     for kw, lam in runs:
         want = _np(eng.decode_beam(prefix[:n], stop, B, T, **kw))
+        kv_want = eng.decode_counters()["kv_slots_per_position"]
         got = _np(eng.decode_beam_groups(prefix[:n], stop, B, 1, lam, T, **kw))
+        kv = eng.decode_counters()["kv_slots_per_position"]
         for a, b in zip(got[:4], want):
             np.testing.assert_array_equal(a, b)
+        assert kv == kv_want and 1.0 <= kv <= B, (kv, kv_want)
         assert np.isfinite(got[4]).all()
         np.testing.assert_allclose(got[4], got[2] * got[1], atol=1e-5 * T, rtol=1e-5)
 

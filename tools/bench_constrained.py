@@ -11,8 +11,8 @@ for the per-family split (capdec_profile_get).
 Workload: P 10 prefix rows per caption (Gaussian rows with the norm of wte rows), GPT-2-small geometry, hot synthetic
 weights, beam 5, a stop id outside the vocabulary (every caption runs all steps), the default GEMM mode.  Phrases: two
 random tokens each, drawn once.  Between the yardstick and the 0-phrase call with the same zero bias only the
-selection kernel (logits_select_forced_kernel for logits_select_kernel), the bookkeeping kernels (constrained_beam_* for
-beam_*) and the finalize differ, all timed in the `select` family; without the bias the constrained call also saves the
+selection kernel (logits_select_forced_kernel for logits_select_kernel) and the bookkeeping kernels (constrained_beam_*
+for beam_init / beam_step; beam_finalize_kernel ends both) differ, all timed in the `select` family; without the bias the constrained call also saves the
 processors' pass over the logits; with phrases the trajectories differ too.  Needs an MI355X."""
 from __future__ import annotations
 
@@ -122,8 +122,8 @@ def main():
     e.close()
     lines += ["The selection kernel, the bookkeeping kernels and the finalize are timed in the `select` family, next to the logits",
               "processors.  `constrained, 0 phrases, zero bias` is the like-for-like comparison: the yardstick's launches with",
-              "logits_select_forced_kernel, constrained_beam_* and constrained_finalize_kernel in the place of logits_select_kernel,",
-              "beam_* and beam_finalize_kernel.  The constrained calls WITHOUT the bias are faster than the yardstick by what the",
+              "logits_select_forced_kernel and constrained_beam_* in the place of logits_select_kernel and beam_init / beam_step",
+              "(beam_finalize_kernel ends both).  The constrained calls WITHOUT the bias are faster than the yardstick by what the",
               "yardstick pays for being forced onto this route: logits_process_kernel reads and writes every logits row once more to",
               "add the zero bias, a pass the constrained call does not need (the `select` deltas above).  With phrases the other",
               "families run the same launches on other tokens and ancestor tables: the banks keep hypotheses that the plain beam",
