@@ -165,6 +165,9 @@ SIGNATURES = {
     "capdec_bridger_eval": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "capdec_bridger_loss": (C.c_int, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
     "capdec_bridger_get": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),
+    "capdec_memory_load": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
+    "capdec_memory_free": (C.c_int, [_VP]),
+    "capdec_memory_project": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP, _VP]),
     "capdec_decode_beam": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP,
                                      _VP, _VP]),
     "capdec_decode_beam_groups": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float,

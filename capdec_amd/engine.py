@@ -875,6 +875,57 @@ class Engine:
                                                   out.data_ptr() if groups else None), "capdec_group_distances")
         return out
 
+    # ------------------------------------------------------------------ projection onto a support memory (memory.hip)
+    MEMORY_MAX_ROWS, MEMORY_MAX_D = 4194304, 640
+
+    def memory_load(self, mem: torch.Tensor):
+        """keep the rows of ``mem`` [M, d] (text embeddings), L2-normalised, as the context's support memory
+        (capdec_memory_load; the contract: include/capdec.h).  One memory per engine: a second load replaces the first.  M in
+        1..4 194 304, d a multiple of 32 in 32..640.  A row holding a NaN or an inf makes the load fail and leaves the memory
+        that was loaded before in place."""
+        if mem.dim() != 2:
+            raise CapdecError(f"memory_load: mem must be [M, d], got {tuple(mem.shape)}")
+        rows, d = int(mem.shape[0]), int(mem.shape[1])
+        if not 1 <= rows <= self.MEMORY_MAX_ROWS or d % 32 or not 32 <= d <= self.MEMORY_MAX_D:
+            raise CapdecError(f"memory_load: M must be in 1..{self.MEMORY_MAX_ROWS} and d a multiple of 32 in 32..{self.MEMORY_MAX_D}, "
+                              f"got {tuple(mem.shape)}")
+        ms = self._dev(mem)
+        self._sync_stream()
+        self._chk(self.lib.capdec_memory_load(self._h, ms.data_ptr(), rows, d), "capdec_memory_load")
+        self.memory = (rows, d)
+        self._memory_owner = None          # (a SupportMemory that loads itself writes its own name here afterwards)
+
+    def memory_free(self):
+        """drop the support memory (capdec_memory_free); :meth:`memory_project` raises until the next load"""
+        self._chk(self.lib.capdec_memory_free(self._h), "capdec_memory_free")
+        self.memory = None
+        self._memory_owner = None
+
+    def memory_project(self, x: torch.Tensor, temperature: float = 0.01, return_info: bool = False):
+        """every row of ``x`` [..., d] replaced by the softmax-weighted combination of the memory's unit rows, weights
+        ``softmax(cosine / temperature)``, L2-normalised (capdec_memory_project; DeCap's projection) -> fp32 [..., d] on the
+        device.  With ``return_info`` also ``{"lse": logsumexp of the scaled similarities, "nearest": int32 index of the most
+        similar memory row (the lowest among equals), "max_sim": its cosine}``, each [...].  A row holding a NaN or an inf
+        comes back as NaN (``nearest`` -1).  A row's results do not depend on the other rows of the call."""
+        if x.dim() < 1:
+            raise CapdecError("memory_project: x must be [..., d]")
+        lead, d = tuple(x.shape[:-1]), int(x.shape[-1])
+        xs = self._dev(x).reshape(-1, d)
+        rows = int(xs.shape[0])
+        out = torch.empty(rows, d, device=self.device, dtype=torch.float32)
+        info = None
+        if return_info:
+            info = {"lse": torch.empty(rows, device=self.device, dtype=torch.float32),
+                    "nearest": torch.empty(rows, device=self.device, dtype=torch.int32),
+                    "max_sim": torch.empty(rows, device=self.device, dtype=torch.float32)}
+        ptr = lambda t: t.data_ptr() if t is not None and rows else None      # noqa: E731
+        self._sync_stream()
+        self._chk(self.lib.capdec_memory_project(self._h, ptr(xs), rows, d, float(temperature), ptr(out),
+                                                 ptr(info["lse"]) if info else None, ptr(info["nearest"]) if info else None,
+                                                 ptr(info["max_sim"]) if info else None), "capdec_memory_project")
+        out = out.view(*lead, d)
+        return (out, {k: v.view(*lead) for k, v in info.items()}) if return_info else out
+
     # ------------------------------------------------------------------ supervised modality bridger (bridger.hip)
     BRIDGER_MAX_LAYERS, BRIDGER_MAX_WIDTH, BRIDGER_MAX_BATCH = 16, 1024, 64
 

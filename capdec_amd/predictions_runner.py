@@ -70,16 +70,29 @@ def _given(**kw) -> Dict:
     return {k: v for k, v in kw.items() if v is not None}
 
 
+def _memory_kw(support_memory, projection_temperature) -> Dict:
+    """the projection keywords, only when a support memory was given: without one every call runs what it always ran"""
+    return {} if support_memory is None else {"support_memory": support_memory, "projection_temperature": projection_temperature}
+
+
 def prefix_from_embeddings(model: ClipCaptionModel, embeddings: torch.Tensor, dont_normalize_prefix: bool = False,
-                           modality_offset: Optional[torch.Tensor] = None, *, modality_bridger=None) -> torch.Tensor:
+                           modality_offset: Optional[torch.Tensor] = None, *, modality_bridger=None, support_memory=None,
+                           projection_temperature: float = 0.01) -> torch.Tensor:
     """reference :221-228 for a batch: ``prefix / prefix.norm(2,-1)``; ``+ offset``; with ``modality_bridger`` (the callable
     of ``supervised_embedding_bridger.get_map_to_text_space_using_modality_bridger`` or its ``MLP``; --modality_bridger)
     ``prefix = modality_bridger(prefix)``, NOT normalised again (:227 computes the quotient and drops it);
-    ``clip_project(prefix).reshape(N, P, -1)``."""
+    ``clip_project(prefix).reshape(N, P, -1)``.  With ``support_memory`` (a ``support_memory.SupportMemory``; not in the
+    reference) the prefix is instead replaced, at the same place, by its projection onto the memory of text embeddings at
+    ``projection_temperature`` -- a unit vector, which goes to ``clip_project`` as it is.  Both at once is an error."""
+    if support_memory is not None and modality_bridger is not None:
+        raise CapdecError("prefix_from_embeddings: support_memory and modality_bridger are two ways across the same gap: "
+                          "pass one of them")
     eng = model.engine
     x = eng.normalize_prefix(embeddings, normalize=not dont_normalize_prefix, offset=modality_offset)
     if modality_bridger is not None:
         x = modality_bridger(x)
+    if support_memory is not None:
+        x = support_memory.project(x, temperature=projection_temperature)
     return model.clip_project(x).reshape(x.shape[0], model.prefix_length, -1)
 
 
@@ -87,16 +100,18 @@ def caption_ids(model: ClipCaptionModel, embeddings: torch.Tensor, stop_token_in
                 beam_size: int = 5, entry_length: int = 67, dont_normalize_prefix: bool = False,
                 modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1, *,
                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, phrases=None):
+                min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, phrases=None, support_memory=None,
+                projection_temperature: float = 0.01):
     """The whole device-side path for this rank's shard of ``embeddings`` [N, D].
     Returns (ids [n_local, T] int32 of the best caption, lens [n_local]) and, for beam, the
     mean-log-prob score of the best beam.  The keyword-only logits processors (None: ``model.logits_processors``'s) are
     those of ``decode_beam_ids`` / ``decode_greedy_ids``.  ``phrases`` (int32 [N, 4, 4], beam only; None: the plain beam):
-    the phrases every caption must contain (``decode_constrained_beam_ids``)."""
+    the phrases every caption must contain (``decode_constrained_beam_ids``).  ``support_memory``,
+    ``projection_temperature``: see ``prefix_from_embeddings``."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     lo, hi = cdist.shard_bounds(embeddings.shape[0], rank, world)
     pe = prefix_from_embeddings(model, embeddings[lo:hi], dont_normalize_prefix, modality_offset,
-                                **_given(modality_bridger=modality_bridger))
+                                **_given(modality_bridger=modality_bridger), **_memory_kw(support_memory, projection_temperature))
     if phrases is not None:
         if not beam:
             raise CapdecError("caption_ids: forced words need the beam decode (beam=True)")
@@ -115,14 +130,16 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
                dont_normalize_prefix: bool = False, modality_offset: Optional[torch.Tensor] = None,
                rank: int = 0, world: int = 1, timer: Optional[Timer] = None, *,
                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-               min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, force_words=None) -> List[Dict]:
-    """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  ``modality_bridger`` (--modality_bridger): see
-    ``prefix_from_embeddings``.  ``force_words`` (beam only; None: the plain beam): per caption a list of up to 4 words its
+               min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, force_words=None,
+               support_memory=None, projection_temperature: float = 0.01) -> List[Dict]:
+    """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  ``modality_bridger`` (--modality_bridger),
+    ``support_memory`` and ``projection_temperature``: see ``prefix_from_embeddings``.  ``force_words`` (beam only; None: the plain beam): per caption a list of up to 4 words its
     caption must contain (``generate_constrained_beam_batch``).  Writes the
     reference's predictions JSON (``[{"caption": lower-cased text, "image_id": id}]``, :260-261,
     :301) -- the whole list, not only every 99th flush."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias,
                 modality_bridger=modality_bridger)
+    pk.update(_memory_kw(support_memory, projection_temperature))
     cdist.check_world(rank, world)
     if len(data) != embeddings.shape[0]:
         raise ValueError(f"make_preds: {len(data)} data entries but {embeddings.shape[0]} embeddings")
@@ -154,7 +171,8 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
                            entry_length: int = 67, dont_normalize_prefix: bool = False,
                            modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
                            image_batch: int = 256, *, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                           min_length: Optional[int] = None, logit_bias=None, modality_bridger=None) -> List[Dict]:
+                           min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, support_memory=None,
+                           projection_temperature: float = 0.01) -> List[Dict]:
     """The image half of the reference loop in front of ``make_preds`` (:156-161, :207-220): ``images[i]`` is what
     ``Image.open(filename).convert("RGB")`` gave for ``data[i]`` (a PIL image or a uint8 [H, W, 3] array), or ``None``
     for a file the reference would skip (:207-210: the entry is left out of the output).  ``preprocess`` and
@@ -184,7 +202,8 @@ def make_preds_from_images(data: Sequence[Dict], images: Sequence, clip_model, p
     if feats:
         ids, lens, _ = caption_ids(model, torch.cat(feats), stop, beam, 5, T, dont_normalize_prefix, modality_offset,
                                    **_given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias,
-                                            modality_bridger=modality_bridger))
+                                            modality_bridger=modality_bridger),
+                                   **_memory_kw(support_memory, projection_temperature))
     else:                              # an empty shard (more ranks than images) still takes part in the gather
         dev = next(model.parameters()).device
         ids, lens = torch.zeros(0, T, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)

@@ -713,6 +713,39 @@ int capdec_bridger_eval(capdec_ctx *ctx, const float *d_x, const float *d_y, int
                         long long *batches);
 int capdec_bridger_loss(capdec_ctx *ctx, float *last, double *sum, long long *steps, int reset);
 int capdec_bridger_get(capdec_ctx *ctx, int kind, int which, float *d_out, size_t n);
+/* ---- projection onto a support memory of text embeddings -------------------------------- */
+/* The training-free way across the modality gap (DeCap, Li et al., ICLR 2023): keep the CLIP text embeddings of the training
+ * captions as a support memory m [M, d] and replace an image embedding x by its softmax-weighted combination of memory rows,
+ *     xn = x / max(||x||, 1e-12)        mn_j = m_j / max(||m_j||, 1e-12)
+ *     w  = softmax_j(<xn, mn_j> / temperature)          (0.01 in the paper)
+ *     v  = sum_j w_j mn_j               d_out = v / max(||v||, 1e-12)
+ * so the result lies in the span of the text embeddings the decoder was trained on.  Also returned, each optional (NULL):
+ * d_lse[r] = logsumexp_j(<xn, mn_j> / temperature); d_nearest[r] = argmax_j <xn, mn_j>, the lowest index among bit-equal
+ * similarities -- the retrieval baseline; d_max_sim[r] = that similarity.
+ *   - One fused pass, flash attention with K = V = the memory: neither the [rows, M] similarities nor the weights reach HBM.
+ *   - fp32 arithmetic whatever the context's GEMM mode: both products run on the fp32 matrix instruction (a k-ordered chain
+ *     of fp32 FMAs), the exponentials and the sums are fp32.  No fp16 plane holds a similarity or a weight.
+ *   - capdec_memory_load normalises every row of d_mem (device, [rows, d]) once and keeps the unit rows in the context, fp32,
+ *     d padded to a multiple of 128 -- 1.2 GB for 566 747 x 512 -- for every later call.  One memory per context: a second
+ *     load replaces the first, capdec_memory_free and capdec_destroy drop it.  rows 1..4 194 304, d a multiple of 32 in
+ *     32..640.  A memory row holding a NaN or an inf makes the load FAIL with the previous memory untouched; an all-zero row
+ *     stays a zero row (similarity 0 to everything).
+ *   - Deterministic and batch-invariant, no atomics: the memory is split into chunks of a fixed 2048 rows, every chunk is
+ *     reduced from a fresh (max, sum, vector) state into a partial in a workspace of the context, and the partials are folded
+ *     in chunk order by one formula.  The split depends on the memory alone, so a row's four outputs are bit-identical on
+ *     every call, whatever the other rows of the call are.  One query row against a large memory still fills the chip (one
+ *     block per chunk).  Query rows are processed in blocks sized so that the partials stay below 256 MiB.
+ *   - A query row holding a NaN or an inf gets a NaN d_out row, NaN d_lse and d_max_sim and d_nearest -1; the call succeeds
+ *     and the other rows are unaffected.  An all-zero query row has similarity 0 to every row: uniform weights.
+ *   - Errors, each with capdec_last_error and the context left usable: no memory loaded, d differs from the memory's,
+ *     temperature <= 0 or not finite, rows < 0.  rows == 0 succeeds and touches nothing.
+ *   - The calls enqueue on the context's stream and synchronise before they return.
+ * (Added without a new ABI number, like capdec_nearest_tokens.) */
+int capdec_memory_load(capdec_ctx *ctx, const float *d_mem /* [rows, d] */, int rows, int d);
+int capdec_memory_free(capdec_ctx *ctx);
+int capdec_memory_project(capdec_ctx *ctx, const float *d_x /* [rows, d] */, int rows, int d, float temperature,
+                          float *d_out /* [rows, d] */, float *d_lse /* [rows] or NULL */,
+                          int32_t *d_nearest /* [rows] or NULL */, float *d_max_sim /* [rows] or NULL */);
 /* Image preprocessing in front of capdec_clip_encode_image: the `preprocess` transform clip.load returns
  * (reference predictions_runner.py:212, embeddings_generator.py:72) = Resize(n_px, BICUBIC) -> CenterCrop(n_px) ->
  * ToTensor -> Normalize(mean, std); stretch != 0 = clip_transform_full (predictions_runner.py:116-122): Resize((n_px,
