@@ -158,6 +158,7 @@ SIGNATURES = {
     "capdec_nearest_tokens": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
     "capdec_embed_moments": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP]),
     "capdec_group_distances": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, c_int_p, C.c_int, _VP]),
+    "capdec_clip_score": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, c_int_p, C.c_int, _VP, C.c_int, c_int_p, C.c_float, _VP, _VP]),
     "capdec_bridger_load": (C.c_int, [_VP, C.c_int, c_int_p, C.POINTER(c_float_p), C.POINTER(c_float_p)]),
     "capdec_bridger_forward": (C.c_int, [_VP, _VP, C.c_int, _VP]),
     "capdec_bridger_train_step": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]),

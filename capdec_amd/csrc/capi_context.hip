@@ -168,7 +168,7 @@ void capdec_destroy(capdec_ctx *c) {
     DBuf *bufs[] = {&c->h, &c->x, &c->qkv, &c->att, &c->ff, &c->xl, &c->tmax, &c->tsum, &c->cval, &c->cidx,
                     &c->lse, &c->topv, &c->topi, &c->kc, &c->vc, &c->tokens, &c->scores, &c->seq, &c->stopped,
                     &c->done, &c->anc, &c->next_tok, &c->alive, &c->gids, &c->glens, &c->m_hid, &c->m_lin, &c->m_seq,
-                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->glogp, &c->cstate, &c->cs_hist, &c->cs_last, &c->cs_sel, &c->lmflag, &c->xpk2, &c->lmsp, &c->slogits, &c->s_plan, &c->s_rows, &c->s_logit, &c->s_bad, &c->pbias, &c->pcorr, &c->wte_n, &c->n_tab, &c->n_bad, &c->gap_ws, &c->gap_ws2, &c->gap_off, &c->br_f0, &c->br_f1, &c->br_ev, &c->mem_n, &c->mem_q, &c->mem_part, &c->mem_bad, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
+                    &c->m_x, &c->m_qkv, &c->m_att, &c->m_ff, &c->m_kvc, &c->t_idx, &c->t_patch, &c->t_pout, &c->xpk, &c->apk, &c->fpk, &c->cmap, &c->kvstat, &c->glogp, &c->cstate, &c->cs_hist, &c->cs_last, &c->cs_sel, &c->lmflag, &c->xpk2, &c->lmsp, &c->slogits, &c->s_plan, &c->s_rows, &c->s_logit, &c->s_bad, &c->pbias, &c->pcorr, &c->wte_n, &c->n_tab, &c->n_bad, &c->gap_ws, &c->gap_ws2, &c->gap_off, &c->clipscore_off, &c->br_f0, &c->br_f1, &c->br_ev, &c->mem_n, &c->mem_q, &c->mem_part, &c->mem_bad, &c->p_desc, &c->p_inter, &c->splitk, &c->absmax, &c->a_tmp,
                     &c->r_a, &c->r_b, &c->r_c, &c->r_d, &c->r_e, &c->r_f, &c->r_col, &c->r_pk1, &c->r_pk2, &c->r_xpk,
                     &c->r_ypk, &c->r_xi, &c->r_idp, &c->r_zero};
     for (DBuf *b : bufs) b->release();

@@ -13,6 +13,7 @@
 //   score.hip         capdec_score: teacher-forced log-probabilities of given captions (chunk planning, its three kernels)
 //   nearest.hip       capdec_nearest_tokens: nearest table rows by cosine similarity (the normalised-wte cache, row blocks)
 //   gap_stats.hip     capdec_embed_moments, capdec_group_distances: modality offset and paraphrase spread, fp64 sums
+//   clipscore.hip     capdec_clip_score: CLIPScore / RefCLIPScore of candidate captions and their order per image, fp64 sums
 //   memory.hip        capdec_memory_*: image embeddings projected onto a support memory of text embeddings (one fused pass)
 //   bridger.hip       capdec_bridger_*: the supervised modality bridger (an MLP trained with MSE and SGD with momentum), fp32
 //   mapper.hip        the prefix stage and the three mapping networks; the one TransformerLayer forward they and the train
@@ -222,6 +223,7 @@ struct capdec_ctx {
     capdec::Bridger bridger;               // bridger.hip: at most one supervised modality bridger
     DBuf br_f0, br_f1, br_ev;              // ... capdec_bridger_forward / _eval: activations of n rows, two in turn; a loss per batch
     DBuf gap_ws, gap_ws2, gap_off;         // gap_stats.hip: fp64 partial sums per slab and their folds; [flag | group offsets]
+    DBuf clipscore_off;                    // clipscore.hip: [candidate offsets | reference offsets] of the call
     DBuf mem_n;                            // memory.hip: the support memory, every row L2-normalised, fp32 [rows up to MEM_MTILE, d up
     int mem_rows = 0, mem_d = 0;           // to 128], zero padded (mem_rows == 0: none loaded) -- one per context
     DBuf mem_q, mem_part, mem_bad;         // ... a row block's normalised queries, its per-chunk partials, [flag | one flag per row]

@@ -875,6 +875,53 @@ class Engine:
                                                   out.data_ptr() if groups else None), "capdec_group_distances")
         return out
 
+    # ------------------------------------------------------------------ CLIPScore and candidate order (clipscore.hip)
+    def _host_offsets(self, what: str, offsets) -> np.ndarray:
+        raw = (offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)).reshape(-1)
+        if raw.shape[0] < 1:
+            raise CapdecError(f"{what}: offsets must have groups + 1 entries")
+        if not np.issubdtype(raw.dtype, np.integer) or int(raw.min()) < -2 ** 31 or int(raw.max()) >= 2 ** 31:
+            raise CapdecError(f"{what}: offsets must be integers that fit 32 bits")      # (astype would wrap them)
+        return np.ascontiguousarray(raw.astype(np.int32))
+
+    def clip_score(self, cand: torch.Tensor, img: torch.Tensor, offsets, ref: Optional[torch.Tensor] = None, ref_offsets=None,
+                   w: float = 2.5) -> Tuple[torch.Tensor, torch.Tensor]:
+        """CLIPScore / RefCLIPScore of candidate captions and their order per image (capdec_clip_score; the contract:
+        include/capdec.h).  Image g (row g of ``img`` [groups, d]) owns the rows ``offsets[g]:offsets[g + 1]`` of ``cand``
+        [rows, d], 0 to 64 of them, and the rows ``ref_offsets[g]:ref_offsets[g + 1]`` of ``ref`` [ref_rows, d]; both offset
+        vectors are host vectors [groups + 1].  All rows are raw tower outputs.  -> (scores fp32 [rows, 4] = cos, w max(cos, 0),
+        max(0, best reference cosine), their harmonic mean -- the last two NaN without references; order int32 [rows]: the row
+        numbers of every image's candidates, best first), both on the device.  Needs no loaded weights."""
+        if cand.dim() != 2 or img.dim() != 2 or int(img.shape[1]) != int(cand.shape[1]):
+            raise CapdecError("clip_score: cand must be [rows, d] and img [groups, d]")
+        if ref is not None and (ref.dim() != 2 or int(ref.shape[1]) != int(cand.shape[1])):
+            raise CapdecError("clip_score: ref must be [ref_rows, d]")
+        off = self._host_offsets("clip_score", offsets)
+        groups = int(off.shape[0]) - 1
+        if int(img.shape[0]) != groups:
+            raise CapdecError(f"clip_score: {groups} groups but {int(img.shape[0])} image rows")
+        roff = None
+        if ref_offsets is not None:
+            roff = self._host_offsets("clip_score", ref_offsets)
+            if int(roff.shape[0]) != groups + 1:
+                raise CapdecError(f"clip_score: ref_offsets must have {groups + 1} entries, got {int(roff.shape[0])}")
+        rows, d = int(cand.shape[0]), int(cand.shape[1])
+        xc, xi = self._dev(cand), self._dev(img)
+        xr = self._dev(ref) if ref is not None else None
+        scores = torch.empty(rows, 4, device=self.device, dtype=torch.float32)
+        order = torch.empty(rows, device=self.device, dtype=torch.int32)
+        ptr = lambda t: t.data_ptr() if t.numel() else None      # noqa: E731
+        ref_ptr = None
+        if xr is not None:       # an empty reference array is still "given" (the library refuses half a pair): it gets a
+            held = xr if xr.numel() else torch.zeros(4, device=self.device)      # pointer that is not NULL; none of it is read
+            ref_ptr = held.data_ptr()
+        self._sync_stream()
+        self._chk(self.lib.capdec_clip_score(self._h, ptr(xc), rows, d, ptr(xi), off.ctypes.data_as(_capi.c_int_p), groups,
+                                             ref_ptr, int(xr.shape[0]) if xr is not None else 0,
+                                             roff.ctypes.data_as(_capi.c_int_p) if roff is not None else None, float(w),
+                                             ptr(scores), ptr(order)), "capdec_clip_score")
+        return scores, order
+
     # ------------------------------------------------------------------ projection onto a support memory (memory.hip)
     MEMORY_MAX_ROWS, MEMORY_MAX_D = 4194304, 640
 

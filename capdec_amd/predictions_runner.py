@@ -101,28 +101,55 @@ def caption_ids(model: ClipCaptionModel, embeddings: torch.Tensor, stop_token_in
                 modality_offset: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1, *,
                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                 min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, phrases=None, support_memory=None,
-                projection_temperature: float = 0.01):
+                projection_temperature: float = 0.01, pick=None):
     """The whole device-side path for this rank's shard of ``embeddings`` [N, D].
     Returns (ids [n_local, T] int32 of the best caption, lens [n_local]) and, for beam, the
     mean-log-prob score of the best beam.  The keyword-only logits processors (None: ``model.logits_processors``'s) are
     those of ``decode_beam_ids`` / ``decode_greedy_ids``.  ``phrases`` (int32 [N, 4, 4], beam only; None: the plain beam):
     the phrases every caption must contain (``decode_constrained_beam_ids``).  ``support_memory``,
-    ``projection_temperature``: see ``prefix_from_embeddings``."""
+    ``projection_temperature``: see ``prefix_from_embeddings``.  ``pick`` (beam only; None: beam 0, the best under the language
+    model): a callable ``(ids [n_local, beam, T], lens [n_local, beam], lo, hi) -> int64 [n_local]``, the beam to return for
+    every caption of the shard ``embeddings[lo:hi]`` (``make_preds``'s ``clip_rerank``)."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias)
     lo, hi = cdist.shard_bounds(embeddings.shape[0], rank, world)
     pe = prefix_from_embeddings(model, embeddings[lo:hi], dont_normalize_prefix, modality_offset,
                                 **_given(modality_bridger=modality_bridger), **_memory_kw(support_memory, projection_temperature))
+    if pick is not None and not beam:
+        raise CapdecError("caption_ids: picking among the beams needs the beam decode (beam=True)")
+
+    def best(ids, lens, scores):
+        if pick is None:
+            return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
+        b = pick(ids, lens, lo, hi).to(ids.device)
+        r = torch.arange(ids.shape[0], device=ids.device)
+        return ids[r, b].contiguous(), lens[r, b].contiguous(), scores[r, b].contiguous()
+
     if phrases is not None:
         if not beam:
             raise CapdecError("caption_ids: forced words need the beam decode (beam=True)")
         ids, lens, scores = decode_constrained_beam_ids(model, pe, np.asarray(phrases)[lo:hi], stop_token_index, beam_size,
                                                         entry_length, **pk)[:3]
-        return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
+        return best(ids, lens, scores)
     if beam:
         ids, lens, scores, _ = decode_beam_ids(model, pe, stop_token_index, beam_size, entry_length, **pk)
-        return ids[:, 0].contiguous(), lens[:, 0].contiguous(), scores[:, 0].contiguous()
+        return best(ids, lens, scores)
     ids, lens = decode_greedy_ids(model, pe, stop_token_index, entry_length, **pk)
     return ids, lens, None
+
+
+def _clip_pick(clip_model, clip_tokenize, tokenizer, embeddings: torch.Tensor):
+    """``caption_ids``'s ``pick``: the beam whose text, as ``make_preds`` would write it, has the largest CLIP cosine to the
+    caption's own embedding -- the tensor its prefix was made from"""
+    from .clip_score import clip_score
+
+    def pick(ids, lens, lo, hi):
+        ids_h, lens_h = ids.cpu().numpy(), lens.cpu().numpy()
+        texts = [[tokenizer.decode(list(ids_h[r, b, :int(lens_h[r, b])])).lower() for b in range(ids_h.shape[1])]
+                 for r in range(ids_h.shape[0])]
+        order = clip_score(clip_model, embeddings[lo:hi], texts, tokenize=clip_tokenize)["order"]
+        return torch.tensor([int(o[0]) for o in order], dtype=torch.int64)
+
+    return pick
 
 
 def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptionModel, tokenizer,
@@ -131,10 +158,13 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
                rank: int = 0, world: int = 1, timer: Optional[Timer] = None, *,
                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                min_length: Optional[int] = None, logit_bias=None, modality_bridger=None, force_words=None,
-               support_memory=None, projection_temperature: float = 0.01) -> List[Dict]:
+               support_memory=None, projection_temperature: float = 0.01, clip_rerank=None, clip_tokenize=None) -> List[Dict]:
     """``data[i]`` = {"image_id": ...}; ``embeddings[i]`` its CLIP embedding.  ``modality_bridger`` (--modality_bridger),
     ``support_memory`` and ``projection_temperature``: see ``prefix_from_embeddings``.  ``force_words`` (beam only; None: the plain beam): per caption a list of up to 4 words its
-    caption must contain (``generate_constrained_beam_batch``).  Writes the
+    caption must contain (``generate_constrained_beam_batch``).  ``clip_rerank`` (beam only; None: the beam the language model
+    scores best, as ever): a ``ClipModel`` with a text tower -- all five beams of this rank's captions (with the forced words,
+    when given) go through its text tower (``clip_tokenize``: ``list[str] -> int [N, 77]``, default ``clip.tokenize`` with
+    truncation) and the beam closest to ``embeddings[i]`` is written (``capdec_amd.clip_score``).  Writes the
     reference's predictions JSON (``[{"caption": lower-cased text, "image_id": id}]``, :260-261,
     :301) -- the whole list, not only every 99th flush."""
     pk = _given(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, logit_bias=logit_bias,
@@ -146,6 +176,10 @@ def make_preds(data: Sequence[Dict], embeddings: torch.Tensor, model: ClipCaptio
     stop = tokenizer.encode('.')[0]
     if force_words is not None:
         pk["phrases"] = _phrases_of(tokenizer, len(data), force_words, None)
+    if clip_rerank is not None:
+        if not beam:
+            raise CapdecError("make_preds: clip_rerank needs the beam decode (beam=True): one candidate is nothing to rerank")
+        pk["pick"] = _clip_pick(clip_rerank, clip_tokenize, tokenizer, embeddings)
     if timer is not None:           # the reference's `with timer:` (:214-233) around this rank's share of the batch
         with timer.bind(model):
             ids, lens, _ = caption_ids(model, embeddings, stop, beam, 5, entry_length, dont_normalize_prefix,

@@ -670,6 +670,37 @@ int capdec_group_distances(capdec_ctx *ctx, const float *d_x /* [rows, W] */, in
                            const int32_t *d_index /* [h_offsets[groups]] row numbers, or NULL = identity */,
                            const int32_t *h_offsets /* HOST [groups + 1], ascending */, int groups,
                            float *d_out /* [groups, 8] */);
+/* ---- CLIPScore and the order of candidate captions ------------------------------------- */
+/* CLIPScore / RefCLIPScore (Hessel et al., EMNLP 2021) of candidate captions, and their order per image: the comparison
+ * after capdec_clip_encode_image / capdec_clip_encode_text that says which of an image's candidates fits it.  Group g (one
+ * image, row g of d_img) owns the candidate rows h_offsets[g] .. h_offsets[g + 1] of d_cand, 0 to 64 of them, and the
+ * reference rows h_ref_offsets[g] .. h_ref_offsets[g + 1] of d_ref, any number.  All rows are raw tower outputs: nothing is
+ * normalised beforehand.  d is 1..2048, any value.  Per candidate c of an image v with references R, d_scores[row, 0..4):
+ *   0  cos       = c.v / (||c|| ||v||)
+ *   1  clip_s    = w max(cos, 0)                               (w = 2.5 in the paper)
+ *   2  ref_sim   = max(0, max over r in R of cos(c, r));       NaN when the group has no references or d_ref is NULL
+ *   3  refclip_s = 2 clip_s ref_sim / (clip_s + ref_sim), 0 when both are 0;      NaN when column 2 is NaN
+ *   - Every sum (squared norms, dots) is fp64; each column is computed in fp64 and rounded to fp32 once.
+ *   - A candidate or image row that holds a NaN or an inf, or is all zero, gives NaN in all four columns.  A reference row of
+ *     that kind makes columns 2 and 3 of its whole group NaN, and nothing else.
+ *   - d_order[h_offsets[g] + j] is the absolute row number of the j-th best candidate of group g: descending by the fp32 cos
+ *     as written to column 0, NaN rows last, equal values (and the NaN rows among themselves) by ascending row.
+ *   - A candidate's four values and a group's order depend only on that group's own rows: they are bit-identical whatever
+ *     else is in the call and however the groups are arranged.  No atomics.
+ *   - One block per image: the image row and the reference rows go through LDS once (the references in slabs of 16 KB), a
+ *     wavefront takes each candidate's dots, one wavefront ranks the group.  The [rows, references] similarities never reach
+ *     HBM: the algorithmic traffic is (rows + groups + ref_rows) d 4 bytes.  A group whose references need several slabs
+ *     reads its candidates once per slab.
+ *   - Refused, each with capdec_last_error, nothing launched and no output written, the context left usable: offsets that
+ *     descend, do not start at 0 or do not end at rows / ref_rows; a group of more than 64 candidates; d outside 1..2048;
+ *     exactly one of d_ref / h_ref_offsets given; a negative count.  groups == 0 or rows == 0 is a valid empty call.
+ *   - The call enqueues on the context's stream and synchronises before it returns.
+ * (Added without a new ABI number, like capdec_nearest_tokens.) */
+int capdec_clip_score(capdec_ctx *ctx, const float *d_cand /* [rows, d] */, int rows, int d,
+                      const float *d_img /* [groups, d] */, const int32_t *h_offsets /* HOST [groups + 1] */, int groups,
+                      const float *d_ref /* [ref_rows, d] or NULL */, int ref_rows,
+                      const int32_t *h_ref_offsets /* HOST [groups + 1] or NULL */, float w,
+                      float *d_scores /* [rows, 4] */, int32_t *d_order /* [rows] */);
 /* ---- supervised modality bridger ------------------------------------------------------- */
 /* Reference others/supervised_embedding_bridger.py: an MLP that maps an image embedding to its caption's text embedding,
  * trained with nn.MSELoss and torch.optim.SGD(momentum) on pairs, applied between the normalisation / offset and clip_project
